@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/sec of the dual-refinement detector hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path -- build_net(...)'s forward + Detect -- over one batch of
@@ -10,7 +10,12 @@ bf16, batch 32 per GPU, multihead, synthetic VOC-shaped frames, synthetic weight
 runs its own batch (frames shard, weights arrive by one RCCL broadcast, no per-frame collective):
 weak scaling, value = all ranks' frames / max-over-ranks time.
 
-The JSON line also carries
+A plain run sets up, warms up W steps, times K steps once and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = the time of one timed step, and the run's configuration).  --dump-outputs DIR then writes what the last timed step
+returned (the detections; `conf` with --no-detect) as DIR/<name>.npy in float32; inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
+
+With --full the K-step loop is timed --reps times (default 9, the median is reported) and the JSON line also carries
   roofline     : the dominant kernel family (conv3x3_patch_mfma): algorithmic FLOPs of its launches in one
                  step / their summed hipEvent durations IN THE PRODUCTION SCHEDULE (events recorded by the library on the
                  stream each launch runs on, side lanes on), against the dense bf16 MFMA peak; `single_stream` gives the
@@ -91,6 +96,31 @@ def pmc_traffic(kernel, args, build):
         return e["hbm_bytes_per_launch"], "profiles/pmc_traffic.json (rocprofv3 PMC passes, %s): not measured in this run" % e.get("build", "build not recorded")
     except (OSError, ValueError, KeyError):
         return None, "profiles/pmc_traffic.json unreadable"
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, path, name):
+    """--dump-outputs: the tensors a caller of the timed step receives (`out`: a tensor or a list of them) as <path>/<name>.npy, or
+    <path>/<name>_<i>.npy for a list, in float32 (float64 stays float64).  Above DUMP_MAX_BYTES in all, every array is cut to the same
+    fraction of its elements, drawn by a fixed seed (flattened, in index order), so that two builds dump the same elements."""
+    import numpy as np
+    import torch
+    ts = list(out) if isinstance(out, (list, tuple)) else [out]
+    arrays = []
+    for i, t in enumerate(ts):
+        t = t.detach()
+        a = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+        arrays.append(("%s_%d" % (name, i) if len(ts) > 1 else name, a))
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_MAX_BYTES:
+        rng = np.random.RandomState(0)
+        arrays = [(n, a.reshape(-1)[np.sort(rng.choice(a.size, max(1, a.size * DUMP_MAX_BYTES // total), replace=False))])
+                  for n, a in arrays]
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays:
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 NEAR_EPS = {"fp32": 1e-4, "bf16": 0.03, "fp16": 0.004}   # pixels with a deformable tap this close to a sampling discontinuity
@@ -345,17 +375,19 @@ def pin_rank_to_numa_node():
         NUMA_PIN = tdist.pin_to_gpu_numa_node(int(os.environ.get("LOCAL_RANK", "0")), world)
 
 
-def _timed(stepper, steps, reps, tdist, torch, dev):
+def _timed(stepper, steps, reps, tdist, torch, dev, last=None):
     out = []
     for _ in range(reps):
         tdist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k in range(steps):
-            stepper(k)
+            r = stepper(k)
         torch.cuda.synchronize()
         tdist.barrier()
         out.append(tdist.max_over_ranks(time.perf_counter() - t0, dev))
+    if last is not None:
+        last.append(r)                  # what the last timed step returned (--dump-outputs)
     return out
 
 
@@ -498,6 +530,7 @@ def main_other(args):
 
     NF = 1
     launch_mode, launch_cal = ("hipGraph replay" if args.graph else "eager"), None
+    pipelines = None                                   # the InFlight the timed step launches, if any (its launch(k) returns a batch index)
     trn_flight = None
     if trn and args.graph and batched and args.trn_overlap and args.in_flight > 1 and args.launch == "auto" and NB % 2 == 0:
         # config 5 with two steps in flight: a second pipeline = twins of the static and the temporal model (own engines over the same
@@ -538,7 +571,7 @@ def main_other(args):
                 KEEP_ALIVE.append(fl_)
                 return fl_
             flight, launch_mode, launch_cal = _choose_launch(flight, make_eager, args.steps, world * frames_per_step, tdist, torch, dev)
-        step = flight.launch
+        step, pipelines = flight.launch, flight
         engines = [(e_, 1) for e_ in flight.engines]
     elif args.graph:
         graphs = [GraphedCall(one_step, xb[j]) for j in range(NB)]
@@ -549,17 +582,47 @@ def main_other(args):
                 launch = staticmethod(step)
             chosen, launch_mode, launch_cal = _choose_launch(_Replays, trn_flight, args.steps, world * frames_per_step, tdist, torch, dev)
             if launch_mode == "eager":
-                NF, step = 2, chosen.launch
+                NF, step, pipelines = 2, chosen.launch, chosen
                 engines = [(eng_s, 1), (eng_t, 1)]
     else:
         step = lambda k: one_step(xb[k % NB])
     for k in range(args.warmup):
         step(k)
-    reps = sorted(_timed(step, args.steps, max(1, args.reps), tdist, torch, dev))
+    last = []
+    reps = sorted(_timed(step, args.steps, max(1, args.reps), tdist, torch, dev, last))
     for e_, _m in engines:
         e_.check()                  # tdrn_net_check: a device-side hand-off that timed out inside the replays above fails the run HERE
     dt = reps[len(reps) // 2]
     fps = world * frames_per_step * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pipelines.output(last[0]) if pipelines is not None else last[0], args.dump_outputs, "conf" if args.no_detect else "detections")
+    if rank == 0:
+        line = {
+            "metric": "frames/sec/GPU @%dx%d %s" % (S, S, "TRN 4-frame clips, ssd4scale_vgg" if trn else "dualrefinedet_mobilenet"),
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": "BASELINE config #%d: %s %dx%d, %s, %s per GPU, forward%s, synthetic VOC-shaped frames + synthetic weights" % (
+                           args.config, name, S, S, args.dtype, (("%d clips x 4 frames (per step: 1 static forward over the %d key frames, ONE temporal forward over the %d frames with the key frames' offsets, one Detect call)" % (B, B, 4 * B)) if batched else
+                                                           ("%d clips x 4 frames (per step: 1 static + 4 temporal forwards of %d frames + 4 Detect calls, frame by frame as evaluate_trn.py)" % (B, B))) if trn else "batch %d" % B,
+                           "" if args.no_detect else " + Detect(top_k 200, conf 0.01, nms 0.45)") + ("" if NCLS == 21 else "; %d classes (not BASELINE's 21; the GFLOP figures stay the 21-class ones)" % NCLS),
+                       "global_batch": world * frames_per_step, "parallelism": "%s-sharded x%d, no per-frame collective" % ("clip" if trn else "frame", world),
+                       "launch": launch_mode, "launch_calibration_frames_per_s": launch_cal, "resident_batches": NB, "steps_in_flight": NF},
+            "repetitions": {"n": len(reps), "reported": "median", "timed_steps_total": len(reps) * args.steps, "ms_per_step_min": round(reps[0] / args.steps * 1e3, 4), "ms_per_step_max": round(reps[-1] / args.steps * 1e3, 4)},
+            "fps_per_gpu": round(fps / world, 2), "build": build,
+            "n_ranks_seen": int(torch.distributed.get_world_size()) if tdist.active() else world, "weights_broadcast_ms": round(bcast_ms, 2) if tdist.active() else None,
+            "dist_backend": torch.distributed.get_backend() if tdist.active() else None,
+            "numa_pin": tdist.verify_pin(NUMA_PIN, local_rank),
+        }
+        if trn:
+            line["clips_per_s"] = round(fps / FPC, 2)
+            line["trn_static_net_overlapped"] = bool(batched and args.trn_overlap)
+            line["trn_mode"] = args.trn_mode      # batched: one temporal forward per step (key-frame offsets broadcast); frames: one per frame index
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        tdist.barrier()
+        return
     one_at_a_time = None
     if NF > 1:
         if not trn:
@@ -683,32 +746,11 @@ def main_other(args):
     if rank != 0:
         tdist.barrier()
         return
-    line = {
-        "metric": "frames/sec/GPU @%dx%d %s" % (S, S, "TRN 4-frame clips, ssd4scale_vgg" if trn else "dualrefinedet_mobilenet"),
-        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "BASELINE config #%d: %s %dx%d, %s, %s per GPU, forward%s, synthetic VOC-shaped frames + synthetic weights" % (
-                       args.config, name, S, S, args.dtype, (("%d clips x 4 frames (per step: 1 static forward over the %d key frames, ONE temporal forward over the %d frames with the key frames' offsets, one Detect call)" % (B, B, 4 * B)) if batched else
-                                                       ("%d clips x 4 frames (per step: 1 static + 4 temporal forwards of %d frames + 4 Detect calls, frame by frame as evaluate_trn.py)" % (B, B))) if trn else "batch %d" % B,
-                       "" if args.no_detect else " + Detect(top_k 200, conf 0.01, nms 0.45)") + ("" if NCLS == 21 else "; %d classes (not BASELINE's 21; the GFLOP figures stay the 21-class ones)" % NCLS),
-                   "global_batch": world * frames_per_step, "parallelism": "%s-sharded x%d, no per-frame collective" % ("clip" if trn else "frame", world),
-                   "launch": launch_mode, "launch_calibration_frames_per_s": launch_cal, "resident_batches": NB, "steps_in_flight": NF},
-        "repetitions": {"n": len(reps), "reported": "median", "timed_steps_total": len(reps) * args.steps, "ms_per_step_min": round(reps[0] / args.steps * 1e3, 4), "ms_per_step_max": round(reps[-1] / args.steps * 1e3, 4)},
-        "fps_per_gpu": round(fps / world, 2), "forward_only_ms_per_step": round(fwd_ms, 4), "forward_tflops": round(gflop_step / fwd_ms, 2),
-        "build": build, "roofline": roofline, "kernels": kernels,
-        "n_ranks_seen": int(torch.distributed.get_world_size()) if tdist.active() else world, "weights_broadcast_ms": round(bcast_ms, 2) if tdist.active() else None,
-        "dist_backend": torch.distributed.get_backend() if tdist.active() else None,
-        "numa_pin": tdist.verify_pin(NUMA_PIN, local_rank),
-    }
+    line.update({"forward_only_ms_per_step": round(fwd_ms, 4), "forward_tflops": round(gflop_step / fwd_ms, 2), "roofline": roofline, "kernels": kernels})
     if one_at_a_time is not None:
         line["one_step_at_a_time"] = one_at_a_time
-    if trn:
-        line["clips_per_s"] = round(fps / FPC, 2)
-        line["trn_static_net_overlapped"] = bool(batched and args.trn_overlap)
-        line["trn_mode"] = args.trn_mode      # batched: one temporal forward per step (key-frame offsets broadcast); frames: one per frame index
-        if frame_loop is not None:
-            line["frame_by_frame"] = frame_loop
+    if frame_loop is not None:
+        line["frame_by_frame"] = frame_loop
     if stream_blk is not None:
         line["stream"] = stream_blk
     # ---- parity of the timed dtype against the fp32 CPU oracle on one frame / one clip (decoded boxes, scores) ----
@@ -791,16 +833,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=11)           # evaluate.py:463 drops the first 11 frames
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configuration (2 = the headline)")
     ap.add_argument("--trn-overlap", type=int, default=1, help="config 5, batched mode: 1 = the static net's forward runs on a second stream beside the temporal net's trunk")
-    ap.add_argument("--no-frame-loop", action="store_true", help="config 5, batched mode: skip the side measurement of the frame-by-frame order")
+    ap.add_argument("--no-frame-loop", action="store_true", help="config 5, batched mode, --full: skip the side measurement of the frame-by-frame order")
     ap.add_argument("--trn-mode", default="batched", choices=["batched", "frames"],
                     help="config 5: 'batched' = one temporal forward over all frames of the step's clips (key-frame offsets broadcast); 'frames' = one temporal forward per frame index, the reference loop's order")
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--no-detect", action="store_true", help="time the network forward only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the box / score error and detection-agreement blocks (oracle forwards on the host)")
-    ap.add_argument("--no-modes", action="store_true", help="skip timing the other precisions")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the box / score error and detection-agreement blocks (oracle forwards on the host)")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip timing the other precisions")
     ap.add_argument("--streams", type=int, default=1, help="split each step's batch over this many concurrent HIP streams")
     ap.add_argument("--launch", choices=["auto", "fixed", "eager"], default="auto",
                     help="two steps in flight: auto = time hipGraph replays AND eager pipelines (streams picked by calibration) briefly and run the timed region with the faster (reported in config.launch); "
@@ -809,13 +851,24 @@ def main():
     ap.add_argument("--in-flight", type=int, default=2,
                     help="whole steps in flight (tdrn_amd.engine.InFlight): resident batch j runs on pipeline j %% N (own engine handle, workspace, "
                          "stream and hipGraph; shared weights), so one step's latency-bound tail runs under the next step's trunk; 1 = one step at a time")
-    ap.add_argument("--reps", type=int, default=9, help="the K-step loop is timed this many times; the MEDIAN repetition is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: one step at a time, forward-only time, per-kernel roofline, "
+                         "the streamed mode, the other precisions, parity and detection agreement with the CPU oracle, the CPU baseline "
+                         "(config 5: the frame-by-frame order); without it a run sets up, warms up, times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="the K-step loop is timed this many times; the MEDIAN repetition is reported (default 1; 9 with --full)")
     ap.add_argument("--batches", type=int, default=4, help="distinct resident batches the steps cycle through")
-    ap.add_argument("--stream", type=int, default=1, help="1: also time the streamed mode (pinned uint8 frames H2D -> preprocess -> net -> Detect -> D2H, two slots in flight) and report it beside the resident figure")
-    ap.add_argument("--per-op", action="store_true", help="print per-launch timings of one profiled forward to stderr")
+    ap.add_argument("--stream", type=int, default=1, help="--full, 1: also time the streamed mode (pinned uint8 frames H2D -> preprocess -> net -> Detect -> D2H, two slots in flight) and report it beside the resident figure")
+    ap.add_argument("--per-op", action="store_true", help="--full: print per-launch timings of one profiled forward to stderr")
     ap.add_argument("--cpu-frames", type=int, default=96)      # ~16 s of CPU work on the GPU box host
     ap.add_argument("--classes", type=int, default=21, help="num_classes of the nets and of Detect: 21 = VOC (BASELINE's configs), 31 = VID (the TRN drivers), 81 = COCO")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.reps is None:
+        args.reps = 9 if args.full else 1
     global NCLS
     NCLS = args.classes
     preset = CONFIGS[args.config]
@@ -933,19 +986,21 @@ def main():
         KEEP_ALIVE.append(fl)
         return fl
 
-    def timed(stepper, steps, reps):
+    def timed(stepper, steps, reps, last=None):
         """`reps` repetitions of the K-step loop, each bracketed by barrier + synchronize on both sides and reduced with
-        MAX over ranks; returns the per-repetition times (s)."""
+        MAX over ranks; returns the per-repetition times (s).  `last` (a list) receives what the last step returned."""
         out = []
         for _ in range(reps):
             tdist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k in range(steps):
-                stepper(k)
+                r = stepper(k)
             torch.cuda.synchronize()
             tdist.barrier()
             out.append(tdist.max_over_ranks(time.perf_counter() - t0, dev))
+        if last is not None:
+            last.append(r)
         return out
 
     launch_mode, launch_cal = ("hipGraph replay" if (args.graph and NS == 1) else "eager"), None
@@ -966,11 +1021,48 @@ def main():
         step = make_stepper(eng, det) if NS == 1 else eager_step
     for k in range(args.warmup):
         step(k)
-    reps = sorted(timed(step, args.steps, max(1, args.reps)))
+    last = []
+    reps = sorted(timed(step, args.steps, max(1, args.reps), last))
     for e_ in engines:
         e_.check()                  # tdrn_net_check: a device-side hand-off that timed out inside the replays above fails the run HERE
     dt = reps[len(reps) // 2]                                    # the median repetition
     fps = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(flight.output(last[0]) if NF > 1 else last[0], args.dump_outputs, "conf" if args.no_detect else "detections")
+    if rank == 0:
+        line = {
+            "metric": "frames/sec/GPU @%dx%d dualrefinedet_vggbn; box Linf vs CPU ref" % (args.size, args.size),
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": "dualrefinedet_vggbn %dx%d multihead, %s, batch %d per GPU, forward%s, synthetic "
+                                   "VOC-shaped frames + synthetic weights%s" %
+                                   (args.size, args.size, args.dtype, B, "" if args.no_detect else " + Detect(top_k 200, conf 0.01, nms 0.45)",
+                                    "" if NCLS == 21 else ", %d classes (not BASELINE's 21)" % NCLS),
+                       "global_batch": world * B, "parallelism": "frame-sharded x%d, no per-frame collective" % world,
+                       "launch": launch_mode,
+                       "launch_calibration_frames_per_s": launch_cal,
+                       "eager_stream_calibration": (getattr(flight, "stream_calibration", None) or {}).get("picked") if launch_mode == "eager" else None,
+                       "resident_batches": NB,
+                       "steps_in_flight": NF,
+                       "schedule": ("%d steps in flight: resident batch j runs on pipeline j %% %d (own engine handle, workspace, HIP stream%s; one weight blob); "
+                                    "K steps between two device-wide synchronisations" % (NF, NF, ", hipGraph" if launch_mode != "eager" else ", launched eagerly")) if NF > 1 else "one step at a time"},
+            "repetitions": {"n": len(reps), "reported": "median", "timed_steps_total": len(reps) * args.steps, "ms_per_step_min": round(reps[0] / args.steps * 1e3, 4),
+                            "ms_per_step_max": round(reps[-1] / args.steps * 1e3, 4)},
+            "fps_per_gpu": round(fps / world, 2),
+            "build": build,
+            # N > 1: what the first hardware run should tell -- how many ranks really joined, what the one collective cost, where
+            # each rank's feeder threads were pinned (tdrn_amd/dist.py pin_to_gpu_numa_node; rank 0's record)
+            "n_ranks_seen": int(torch.distributed.get_world_size()) if tdist.active() else world,
+            "weights_broadcast_ms": round(bcast_ms, 2) if tdist.active() else None,
+            "dist_backend": torch.distributed.get_backend() if tdist.active() else None,
+            "numa_pin": tdist.verify_pin(NUMA_PIN, local_rank),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        tdist.barrier()
+        return
     one_at_a_time = None
     if NF > 1:
         # the same steps one at a time (one pipeline, one hipGraph per resident batch), timed in the same process
@@ -1078,38 +1170,12 @@ def main():
         net.set_compute_dtype(args.dtype)
 
     if rank == 0:
-        line = {
-            "metric": "frames/sec/GPU @%dx%d dualrefinedet_vggbn; box Linf vs CPU ref" % (args.size, args.size),
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "dualrefinedet_vggbn %dx%d multihead, %s, batch %d per GPU, forward%s, synthetic "
-                                   "VOC-shaped frames + synthetic weights%s" %
-                                   (args.size, args.size, args.dtype, B, "" if args.no_detect else " + Detect(top_k 200, conf 0.01, nms 0.45)",
-                                    "" if NCLS == 21 else ", %d classes (not BASELINE's 21)" % NCLS),
-                       "global_batch": world * B, "parallelism": "frame-sharded x%d, no per-frame collective" % world,
-                       "launch": launch_mode,
-                       "launch_calibration_frames_per_s": launch_cal,
-                       "eager_stream_calibration": (getattr(flight, "stream_calibration", None) or {}).get("picked") if launch_mode == "eager" else None,
-                       "resident_batches": NB,
-                       "steps_in_flight": NF,
-                       "schedule": ("%d steps in flight: resident batch j runs on pipeline j %% %d (own engine handle, workspace, HIP stream%s; one weight blob); "
-                                    "K steps between two device-wide synchronisations" % (NF, NF, ", hipGraph" if launch_mode != "eager" else ", launched eagerly")) if NF > 1 else "one step at a time"},
-            "repetitions": {"n": len(reps), "reported": "median", "timed_steps_total": len(reps) * args.steps, "ms_per_step_min": round(reps[0] / args.steps * 1e3, 4),
-                            "ms_per_step_max": round(reps[-1] / args.steps * 1e3, 4)},
-            "fps_per_gpu": round(fps / world, 2),
+        line.update({
             "forward_only_ms_per_step": round(fwd_ms, 4),
             "forward_tflops": round((GFLOP_PER_FRAME.get(args.size, 0) + head_gflop_delta(args.size)) * B / fwd_ms, 2),
-            "build": build,
             "roofline": roofline,
             "kernels": kernels,
-            # N > 1: what the first hardware run should tell -- how many ranks really joined, what the one collective cost, where
-            # each rank's feeder threads were pinned (tdrn_amd/dist.py pin_to_gpu_numa_node; rank 0's record)
-            "n_ranks_seen": int(torch.distributed.get_world_size()) if tdist.active() else world,
-            "weights_broadcast_ms": round(bcast_ms, 2) if tdist.active() else None,
-            "dist_backend": torch.distributed.get_backend() if tdist.active() else None,
-            "numa_pin": tdist.verify_pin(NUMA_PIN, local_rank),
-        }
+        })
         if one_at_a_time is not None:
             line["one_step_at_a_time"] = one_at_a_time
             line["roofline"]["mode"] += "; single-pipeline profiling passes of engine 0 (`value` is timed with %d steps in flight)" % NF

@@ -2,7 +2,7 @@
 # A/B of two builds on one box for another BASELINE configuration: bash scripts/dev/ab_cfg.sh <cfg> <lib_a.so> <lib_b.so> [per-op grep pattern]
 CFG=$1; OUT=gpurun_out/ab; mkdir -p $OUT
 PAT=${4:-arm_loc}
-Q="--config $CFG --per-op --no-cpu-baseline --no-parity --stream 0 --reps 5"
+Q="--config $CFG --full --per-op --no-cpu-baseline --no-parity --stream 0 --reps 5"
 for i in 1 2; do
   for L in $2 $3; do
     echo "== $L"

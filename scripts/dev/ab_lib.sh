@@ -2,7 +2,7 @@
 # A/B of two builds of the library on one box: bash scripts/dev/ab_lib.sh <lib_a.so> <lib_b.so> [grep pattern of per-op rows]
 OUT=gpurun_out/ab; mkdir -p $OUT
 PAT=${3:-backbone.3}
-Q="--per-op --no-cpu-baseline --no-parity --no-modes --stream 0 --reps 5"
+Q="--full --per-op --no-cpu-baseline --no-parity --no-modes --stream 0 --reps 5"
 for i in 1 2; do
   for L in $1 $2; do
     echo "== $L" | tee -a $OUT/ab.txt

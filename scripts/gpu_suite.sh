@@ -4,7 +4,7 @@ export OUT=${OUT:-gpurun_out/suite}
 mkdir -p ${OUT:-gpurun_out/suite}
 timeout 2400 python -m pytest tests -x -q -m gpu --timeout 600 --durations=8 > ${OUT:-gpurun_out/suite}/pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> ${OUT:-gpurun_out/suite}/pytest_gpu.txt
 tail -25 ${OUT:-gpurun_out/suite}/pytest_gpu.txt
-timeout 900 python bench.py > ${OUT:-gpurun_out/suite}/bench.json 2> ${OUT:-gpurun_out/suite}/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 tail -3 ${OUT:-gpurun_out/suite}/bench.err
 python - <<'PY'
 import json

@@ -5,8 +5,8 @@ OUT=${1:-gpurun_out/other_configs.txt}
 mkdir -p $(dirname $OUT)
 : > $OUT
 one() {
-  echo "## python3 bench.py $* --no-cpu-baseline" >> $OUT
-  python3 bench.py "$@" --no-cpu-baseline 2>/dev/null | python3 -c '
+  echo "## python3 bench.py $* --full --no-cpu-baseline" >> $OUT
+  python3 bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python3 -c '
 import json, sys
 d = json.loads(sys.stdin.readline()); r = d["roofline"]; p = d.get("parity", {}).get(d["dtype"], {})
 print("%s | %.0f frames/s, %.3f ms/step, forward %.3f ms | %s %.0f TFLOP/s = %.3f in the step, %.0f = %.3f alone | box Linf %.2e score Linf %.2e" % (

@@ -4,7 +4,7 @@
 export OUT=${OUT:-gpurun_out/pmc_mix}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-PM="--steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-modes --stream 0 --graph 0 --no-detect --reps 1"
+PM="--full --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-modes --stream 0 --graph 0 --no-detect --reps 1"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM_RD --kernel-trace --output-format csv -d $OUT/a -- python3 bench.py $PM > /dev/null 2> $OUT/a.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_BRANCH SQ_INSTS_MFMA SQ_LDS_IDX_ACTIVE SQ_VMEM_TA_ADDR_FIFO_FULL --kernel-trace --output-format csv -d $OUT/b -- python3 bench.py $PM > /dev/null 2> $OUT/b.err
 python3 - <<'PY'

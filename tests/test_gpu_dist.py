@@ -58,7 +58,7 @@ def test_broadcast_weights_two_ranks_one_gpu(tmp_path):
 
 def test_bench_py_two_ranks_one_gpu():
     outs = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "4",
-                    "--no-cpu-baseline"])
+                    "--no-cpu-baseline", "--full"])
     lines = [l for l in outs[0][1].splitlines() if l.startswith("{")]
     assert len(lines) == 1 and not [l for l in outs[1][1].splitlines() if l.startswith("{")]    # rank 0 prints the one line
     d = json.loads(lines[0])
@@ -97,7 +97,7 @@ def test_bench_py_other_configs_launch_their_own_ranks(config, batch):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TDRN_DIST_BACKEND="gloo", TDRN_DIST_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--gpus", "2", "--batch", str(batch), "--steps", "2",
-                        "--warmup", "1", "--reps", "2", "--no-cpu-baseline", "--no-parity"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                        "--warmup", "1", "--reps", "2", "--no-cpu-baseline", "--no-parity", "--full"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-4000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -119,7 +119,7 @@ def test_bench_py_other_baseline_configs(config, batch):
     clips, HBM for the MobileNet model) -- run here at a small batch so that it takes seconds."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--batch", str(batch), "--steps", "2",
-                        "--warmup", "1", "--reps", "2", "--cpu-frames", "2", "--no-modes", "--stream", "0"], env=env, cwd=ROOT,
+                        "--warmup", "1", "--reps", "2", "--cpu-frames", "2", "--no-modes", "--stream", "0", "--full"], env=env, cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-4000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -133,6 +133,49 @@ def test_bench_py_other_baseline_configs(config, batch):
     if config == 5:
         assert abs(d["clips_per_s"] * 4 - d["value"]) / d["value"] < 1e-3
         assert d["config"]["global_batch"] == batch * 4 and d["trn_mode"] == "batched" and d["trn_static_net_overlapped"] is True
+
+
+def test_bench_py_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps once and prints the headline line only (the measurements of
+    --full are absent); --dump-outputs writes what the last timed step returned -- the detections of resident batch (K - 1) % 4 --
+    which equal, bit for bit, the same batch run alone through an engine built here from the same seeds."""
+    import torch
+    from tdrn_amd.data import mb_cfg
+    from tdrn_amd.layers import Detect, PriorBox
+    from tdrn_amd.model.dualrefinedet_vggbn import build_net
+    from tdrn_amd.utils import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    B, K = 4, 3
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", str(B), "--steps", str(K), "--warmup", "2",
+                        "--dump-outputs", str(out)], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, p.stderr.decode()[-4000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == 2 and d["dtype"] == "bf16" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["metric"].startswith("frames/sec/GPU @320x320 dualrefinedet_vggbn")
+    assert d["repetitions"]["n"] == 1 and d["repetitions"]["timed_steps_total"] == K
+    assert abs(d["value"] - B * K / (d["ms_per_step"] * K * 1e-3)) / d["value"] < 1e-3
+    for k in ("roofline", "kernels", "modes", "stream", "parity", "detections", "cpu_baseline", "one_step_at_a_time"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["detections.npy"]
+    got = np.load(out / "detections.npy")
+    assert got.dtype == np.float32 and got.shape == (B, 21, 200, 5) and (got[..., 0] > 0).any()
+
+    dev = torch.device("cuda:0")
+    net = build_net("test", 320, 21, 1024, 1, True, True)
+    net.set_compute_dtype("bf16")
+    sd = synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    net.eval()
+    eng = net.engine(dev)
+    pri = PriorBox(mb_cfg["VOC_320"]).forward().to(dev)
+    x = torch.from_numpy(synth.synth_frames(B, 320, seed=100 + 1000 * ((K - 1) % 4))).to(dev)
+    r = eng.forward(x)
+    want = Detect(21, 0, 200, 0.01, 0.45).forward(r["odm_loc"], r["conf"], pri, arm_loc_data=r["arm_loc"], scale=[500.0, 375.0, 500.0, 375.0])
+    torch.cuda.synchronize()
+    assert np.array_equal(got, want.cpu().numpy())
 
 
 def _one_rank_env(**extra):
