@@ -77,6 +77,41 @@ TDRN_API int tdrn_deform_conv_forward(const float *input, const float *weight,
                                       size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-b) Deformable convolution v1 backward, fp32 -- replaces
+ *     int deform_conv_backward_input_cuda(THCudaTensor *input, *offset, *gradOutput, *gradInput,
+ *         *gradOffset, *weight, *columns, int kW, int kH, int dW, int dH, int padW, int padH,
+ *         int dilationH, int dilationW, int deformable_group)      utils/deformconv/deform_conv_cuda.h:9-13
+ *     int deform_conv_backward_parameters_cuda(THCudaTensor *input, *offset, *gradOutput,
+ *         *gradWeight, *columns, *ones, int kW, ..., int deformable_group, float scale)  :15-19
+ *     called from ConvOffset2dFunction.backward         model/networks.py:648-681
+ *     kernel semantics                                  utils/deformconv/deform_conv_cuda_kernel.cu:53-154,247-298,337-400
+ *   Tensors as in (i); grad_output (N, Cout, Ho, Wo) fp32 NCHW contiguous.  `columns` / `ones` are dropped.
+ *   backward_input:       grad_input (N, Cin, H, W) += the input gradient (float atomics: the low bits depend on
+ *                         arrival order); grad_offset (N, G*2*kH*kW, Ho, Wo) is OVERWRITTEN (bitwise reproducible).
+ *   backward_parameters:  grad_weight (Cout, Cin, kH, kW) += scale * grad_output . columns^T, summed in a fixed order
+ *                         (bitwise reproducible).
+ *   The sampling rule is the forward's: a coordinate < 0 or >= H (W) contributes nothing; in [H-1, H) all of the weight
+ *   goes to row H-1 and the offset gradient along that axis is 0; at an exact integer the offset gradient is the one-sided
+ *   v_high - v_low.  One workspace query serves both entries; it returns 0 where the forward's query does (shape_check),
+ *   and the entries then return TDRN_E_SHAPE (TDRN_E_UNSUPPORTED beyond the kernels' LDS budget: Cout above ~2000).
+ *   No allocation and no host synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_deform_conv_backward_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW,
+                                                          int dH, int dW, int padH, int padW, int dilationH,
+                                                          int dilationW, int deformable_group);
+TDRN_API int tdrn_deform_conv_backward_input(const float *input, const float *offset, const float *grad_output,
+                                             float *grad_input, float *grad_offset, const float *weight, int N,
+                                             int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH,
+                                             int padW, int padH, int dilationH, int dilationW,
+                                             int deformable_group, void *workspace, size_t workspace_bytes,
+                                             void *stream);
+TDRN_API int tdrn_deform_conv_backward_parameters(const float *input, const float *offset, const float *grad_output,
+                                                  float *grad_weight, int N, int Cin, int H, int W, int Cout, int kW,
+                                                  int kH, int dW, int dH, int padW, int padH, int dilationH,
+                                                  int dilationW, int deformable_group, float scale,
+                                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -69,6 +69,10 @@ _SIGS = {
     "tdrn_error_string": (C.c_char_p, [C.c_int]),
     "tdrn_deform_conv_workspace_bytes": (C.c_size_t, [C.c_int] * 15),
     "tdrn_deform_conv_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 15 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_deform_conv_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 14),
+    "tdrn_deform_conv_backward_input": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_deform_conv_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_float, C.c_void_p, C.c_size_t,
+                                                                                            C.c_void_p]),
     "tdrn_nms_workspace_bytes": (C.c_size_t, [C.c_int]),
     "tdrn_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_size_t, C.c_void_p]),

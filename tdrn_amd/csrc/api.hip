@@ -46,6 +46,34 @@ int deform_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, 
     return TDRN_OK;
 }
 
+// backward workspace: the input as group-padded NHWC fp32 (both entries); backward_input: the NHWC grad_input accumulator and the
+// repacked weight; backward_parameters: the split-K slabs.  One size serves both entries.
+struct DeformBwdPlan {
+    DeformBwdGeom g;
+    size_t o_in, o_gin, o_w, o_slab, total;
+};
+
+int deform_bwd_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW,
+                    int G, DeformBwdPlan &b)
+{
+    DeformPlan p;
+    TDRN_TRY(deform_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW, G, TDRN_F32, p));
+    b.g = DeformBwdGeom{N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW, G, p.Ho, p.Wo};
+    const size_t cpad = (size_t)deform_bwd_cpg64(b.g) * G;
+    int splits, per_split;
+    deform_bwd_weight_splits(b.g, splits, per_split);
+    const size_t nhwc = align_up((size_t)N * H * W * cpad * 4, 256);
+    size_t o = 0;
+    b.o_in = o;   o += nhwc;
+    const size_t rest = o;
+    b.o_gin = o;  o += nhwc;
+    b.o_w = o;    o += align_up((size_t)Cout * p.taps * cpad * 4, 256);
+    b.o_slab = rest;
+    const size_t slab_end = rest + align_up((size_t)splits * p.taps * Cout * cpad * 4, 256);
+    b.total = o > slab_end ? o : slab_end;
+    return TDRN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -107,6 +135,52 @@ int tdrn_deform_conv_forward(const float *input, const float *weight, const floa
         TDRN_TRY(launch_deform(a, s));
     }
     return launch_nhwc_to_nchw_f32(out_nhwc, (long long)p.Ho * p.Wo * Cout, Cout, output, N, Cout, p.Ho * p.Wo, s);
+}
+
+size_t tdrn_deform_conv_backward_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH,
+                                                 int padW, int dilationH, int dilationW, int deformable_group)
+{
+    DeformBwdPlan b;
+    if (deform_bwd_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, b) != TDRN_OK) return 0;
+    return b.total;
+}
+
+int tdrn_deform_conv_backward_input(const float *input, const float *offset, const float *grad_output, float *grad_input,
+                                    float *grad_offset, const float *weight, int N, int Cin, int H, int W, int Cout, int kW, int kH,
+                                    int dW, int dH, int padW, int padH, int dilationH, int dilationW, int deformable_group,
+                                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !offset || !grad_output || !grad_input || !grad_offset || !weight) return TDRN_E_ARG;
+    DeformBwdPlan b;
+    TDRN_TRY(deform_bwd_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, b));
+    if (!workspace || workspace_bytes < b.total) return TDRN_E_WORKSPACE;
+    if (deform_bwd_data_px(b.g) == 0) return TDRN_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    const int G = deformable_group, cpg64 = deform_bwd_cpg64(b.g), taps = kH * kW;
+    float *in_nhwc = (float *)(ws + b.o_in), *gin = (float *)(ws + b.o_gin), *wr = (float *)(ws + b.o_w);
+    TDRN_TRY(launch_nchw_to_nhwc_grouped(input, in_nhwc, N, Cin, H * W, G, cpg64, TDRN_F32, s));
+    TDRN_TRY(launch_repack_oihw(weight, wr, Cout, Cout, Cin, taps, G, cpg64, TDRN_F32, s));
+    TDRN_HIP_TRY(hipMemsetAsync(gin, 0, (size_t)N * H * W * cpg64 * G * 4, s));
+    TDRN_TRY(launch_deform_bwd_data(b.g, in_nhwc, offset, grad_output, wr, gin, grad_offset, s));
+    return launch_deform_bwd_input_add(b.g, gin, grad_input, s);
+}
+
+int tdrn_deform_conv_backward_parameters(const float *input, const float *offset, const float *grad_output, float *grad_weight, int N,
+                                         int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH,
+                                         int dilationH, int dilationW, int deformable_group, float scale, void *workspace,
+                                         size_t workspace_bytes, void *stream)
+{
+    if (!input || !offset || !grad_output || !grad_weight) return TDRN_E_ARG;
+    DeformBwdPlan b;
+    TDRN_TRY(deform_bwd_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, b));
+    if (!workspace || workspace_bytes < b.total) return TDRN_E_WORKSPACE;
+    if ((long long)N * H * W * deform_bwd_cpg64(b.g) * deformable_group >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *in_nhwc = (float *)(ws + b.o_in);
+    TDRN_TRY(launch_nchw_to_nhwc_grouped(input, in_nhwc, N, Cin, H * W, deformable_group, deform_bwd_cpg64(b.g), TDRN_F32, s));
+    return launch_deform_bwd_weight(b.g, in_nhwc, offset, grad_output, (float *)(ws + b.o_slab), grad_weight, scale, s);
 }
 
 size_t tdrn_nms_workspace_bytes(int n) { return nms_workspace_bytes(n); }

@@ -13,6 +13,7 @@
 // l(ob,f) + l2(ob,f2) is just a longer K loop, and loc/conf are column segments of the same GEMM.
 #include <algorithm>
 
+#include "deform_sampler.h"
 #include "kernels.h"
 
 namespace tdrn {
@@ -160,24 +161,12 @@ __global__ __launch_bounds__(256) void deform_gemm_kernel(const DeformMulti mp)
             float w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f;
             int o1 = ibase[i], o2 = ibase[i], o3 = ibase[i], o4 = ibase[i];
             if (mrow[i] >= 0) {
-                const float offset_h = offh[i], offset_w = offw[i];
                 const int h_in = ho_[i] * B.stride_h - B.pad_h, w_in = wo_[i] * B.stride_w - B.pad_w;
-                const float h_im = (float)(h_in + ti * B.dil_h) + offset_h;
-                const float w_im = (float)(w_in + tj * B.dil_w) + offset_w;
-                if (h_im >= 0.f && w_im >= 0.f && h_im < (float)p.H && w_im < (float)p.W) {
-                    float h = (float)(ti * B.dil_h) + offset_h;     // map_h, relative to h_in
-                    float w = (float)(tj * B.dil_w) + offset_w;
-                    const int height = p.H - h_in, width = p.W - w_in;
-                    int h_low = (int)floorf(h), w_low = (int)floorf(w), h_high, w_high;
-                    if (h_low >= height - 1) { h_high = h_low = height - 1; h = (float)h_low; } else { h_high = h_low + 1; }
-                    if (w_low >= width - 1) { w_high = w_low = width - 1; w = (float)w_low; } else { w_high = w_low + 1; }
-                    const float lh = h - (float)h_low, lw = w - (float)w_low;
+                int r0, r1, q0, q1;
+                float lh, lw;
+                if (deform_sample(p.H, p.W, h_in, w_in, ti * B.dil_h, tj * B.dil_w, offh[i], offw[i], r0, r1, q0, q1, lh, lw)) {
                     const float hh = 1.f - lh, hw = 1.f - lw;
                     w1 = hh * hw; w2 = hh * lw; w3 = lh * hw; w4 = lh * lw;
-                    // absolute coordinates (clamped only for memory safety; a no-op whenever the
-                    // reference itself stays in bounds)
-                    const int r0 = min(max(h_in + h_low, 0), p.H - 1), r1 = min(max(h_in + h_high, 0), p.H - 1);
-                    const int q0 = min(max(w_in + w_low, 0), p.W - 1), q1 = min(max(w_in + w_high, 0), p.W - 1);
                     const int gb = ibase[i] + g * cpg;
                     o1 = gb + (r0 * p.W + q0) * p.Cin;
                     o2 = gb + (r0 * p.W + q1) * p.Cin;

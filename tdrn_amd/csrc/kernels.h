@@ -187,6 +187,20 @@ int launch_deform(const DeformArgs &a, hipStream_t s);
 // split_branches = 1: two-branch problems run as two work items that atomicAdd into PRE-ZEROED outputs
 int launch_deform_multi(const DeformArgs *args, int n, hipStream_t s, int split_branches);
 int deform_n_pad(int cout);
+// Deformable-conv backward, fp32 (deform_bwd.hip).  The input and the grad_input accumulator are NHWC fp32 with every deformable
+// group's channels padded to deform_bwd_cpg64() (a multiple of 64); grad_out and offsets are the caller's NCHW tensors.
+struct DeformBwdGeom { int N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G, Ho, Wo; };
+int deform_bwd_cpg64(const DeformBwdGeom &g);
+int deform_bwd_data_px(const DeformBwdGeom &g);       // output pixels per workgroup of the data kernel; 0 = unsupported shape
+// gin_nhwc (zeroed by the caller) += col2im(W^T grad_out); goff (NCHW) = the offset gradient (stored once).  wr: launch_repack_oihw
+// of the weight with Npad = Cout and cpg_pad = deform_bwd_cpg64 ([Cout][tap][Cpad] fp32)
+int launch_deform_bwd_data(const DeformBwdGeom &g, const float *in_nhwc, const float *off, const float *gout, const float *wr,
+                           float *gin_nhwc, float *goff, hipStream_t s);
+int launch_deform_bwd_input_add(const DeformBwdGeom &g, const float *gin_nhwc, float *grad_input, hipStream_t s);   // NCHW +=
+// split-K partial slabs of [splits][taps][Cout][Cpad] fp32, then grad_weight (OIHW) += scale * their fixed-order sum
+void deform_bwd_weight_splits(const DeformBwdGeom &g, int &splits, int &per_split);
+int launch_deform_bwd_weight(const DeformBwdGeom &g, const float *in_nhwc, const float *off, const float *gout, float *slab, float *grad_weight,
+                             float scale, hipStream_t s);
 // transform-then-sample path of the 16-bit one-group heads (deform.hip): the caller computes Y = 1x1 GEMM of the input with the
 // per-tap weight slabs ([taps][80 columns] per pixel, deform_sample_cols(taps) channels), this launch blends the corners
 int deform_sample_supported(const DeformArgs &a);      // 0 = no, else the number of taps of all branches

@@ -1,12 +1,13 @@
 """Parameter-holder builders mirroring model/networks.py of the reference (vgg :136-163,
 conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615,
-ConvOffset2d :699-733).  The modules only own parameters with the reference's names and
+ConvOffset2dFunction :617-697, ConvOffset2d :699-733).  The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import ctypes as C
 import math
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
 from .. import _lib
@@ -48,17 +49,8 @@ def mobilenet_backbone(c_last=1024):
     return nn.ModuleList([first] + [conv_dw(a, b, s) for a, b, s in plan])
 
 
-def conv_offset2d(input, offset, weight, stride=1, padding=0, dilation=1, deform_groups=1, compute="fp32"):
-    """Deformable conv v1 forward through tdrn_deform_conv_forward (replaces the FFI call at
-    model/networks.py:641-645).  NCHW fp32 CUDA tensors in, NCHW fp32 out, no bias."""
-    if input is not None and input.dim() != 4:
-        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-    _lib.require_cuda(input, "input")
-    lib = _lib.lib()
+def _deform_geometry(x, off, w, stride, padding, dilation, deform_groups):
     (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    x = input.contiguous().float()
-    off = offset.contiguous().float()
-    w = weight.detach().contiguous().float()
     N, Cin, H, W = x.shape
     Cout, Cw, kh, kw = w.shape
     if Cw != Cin:
@@ -70,16 +62,100 @@ def conv_offset2d(input, offset, weight, stride=1, padding=0, dilation=1, deform
     if tuple(off.shape) != (N, deform_groups * 2 * kh * kw, Ho, Wo):
         raise RuntimeError("invalid shape of offset: expected %r, got %r"
                            % ((N, deform_groups * 2 * kh * kw, Ho, Wo), tuple(off.shape)))
+    # the C ABI's argument order: N, Cin, H, W, Cout, kW, kH, dW, dH, padW, padH, dilationH, dilationW, G
+    return (N, Cin, H, W, Cout, kw, kh, sw, sh, pw, ph, dh, dw, deform_groups), (N, Cout, Ho, Wo)
+
+
+def _deform_forward(x, off, w, stride, padding, dilation, deform_groups, compute):
+    lib = _lib.lib()
+    dims, out_shape = _deform_geometry(x, off, w, stride, padding, dilation, deform_groups)
+    N, Cin, H, W, Cout, kw, kh, sw, sh, pw, ph, dh, dw, G = dims
     dt = _lib.DTYPES[compute]
-    nb = lib.tdrn_deform_conv_workspace_bytes(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, deform_groups, dt)
+    nb = lib.tdrn_deform_conv_workspace_bytes(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G, dt)
     if nb == 0:
         raise RuntimeError("deform_conv: shape check failed")
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    out = torch.empty((N, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    _lib.check(lib.tdrn_deform_conv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(out), N, Cin, H, W, Cout,
-                                            kw, kh, sw, sh, pw, ph, dh, dw, deform_groups, dt, _lib.ptr(ws), nb,
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    _lib.check(lib.tdrn_deform_conv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
                                             _lib.current_stream(x.device)), "tdrn_deform_conv_forward")
     return out
+
+
+class ConvOffset2dFunction(torch.autograd.Function):
+    """Deformable conv v1 with gradients (model/networks.py:617-681 of the reference, as a torch.autograd.Function):
+    forward through tdrn_deform_conv_forward, backward through tdrn_deform_conv_backward_input (input and offset
+    gradients, one call when either is needed) and tdrn_deform_conv_backward_parameters (weight gradient, scale 1 into a
+    zeroed buffer).  The backward is fp32 whatever `compute` the forward used (the reference has no 16-bit backward).
+
+        y = ConvOffset2dFunction.apply(input, offset, weight, stride, padding, dilation, deform_groups[, compute])
+    """
+
+    @staticmethod
+    def forward(ctx, input, offset, weight, stride=1, padding=0, dilation=1, deform_groups=1, compute="fp32"):
+        if input.dim() != 4:
+            raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+        _lib.require_cuda(input, "input")
+        x, off, w = input.contiguous().float(), offset.contiguous().float(), weight.contiguous().float()
+        out = _deform_forward(x, off, w, stride, padding, dilation, deform_groups, compute)
+        ctx.conf = (stride, padding, dilation, deform_groups)
+        ctx.save_for_backward(x, off, w)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, off, w = ctx.saved_tensors
+        if not grad_output.is_cuda:
+            raise NotImplementedError("conv_offset2d backward: grad_output must be a CUDA tensor")
+        lib = _lib.lib()
+        dims, out_shape = _deform_geometry(x, off, w, *ctx.conf)
+        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
+        if tuple(go.shape) != out_shape:
+            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
+        need_in, need_off, need_w = ctx.needs_input_grad[:3]
+        grad_input = grad_offset = grad_weight = None
+        if need_in or need_off or need_w:
+            N, Cin, H, W, Cout, kw, kh, sw, sh, pw, ph, dh, dw, G = dims
+            nb = lib.tdrn_deform_conv_backward_workspace_bytes(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G)
+            if nb == 0:
+                raise RuntimeError("deform_conv backward: shape check failed")
+            ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+            stream = _lib.current_stream(x.device)
+        if need_in or need_off:
+            gi = torch.zeros_like(x)
+            goff = torch.empty_like(off)
+            _lib.check(lib.tdrn_deform_conv_backward_input(_lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(gi), _lib.ptr(goff),
+                                                           _lib.ptr(w), *dims, _lib.ptr(ws), nb, stream),
+                       "tdrn_deform_conv_backward_input")
+            grad_input = gi if need_in else None
+            grad_offset = goff if need_off else None
+        if need_w:
+            gw = torch.zeros_like(w)
+            _lib.check(lib.tdrn_deform_conv_backward_parameters(_lib.ptr(x), _lib.ptr(off), _lib.ptr(go), _lib.ptr(gw), *dims, 1.0,
+                                                                _lib.ptr(ws), nb, stream),
+                       "tdrn_deform_conv_backward_parameters")
+            grad_weight = gw
+        return grad_input, grad_offset, grad_weight, None, None, None, None, None
+
+
+def conv_offset2d(input, offset, weight, stride=1, padding=0, dilation=1, deform_groups=1, compute="fp32"):
+    """Deformable conv v1 (replaces the FFI call at model/networks.py:641-645).  NCHW fp32 CUDA tensors in, NCHW fp32
+    out, no bias.
+
+    Differentiable exactly when torch.is_grad_enabled() and the input or the offset requires grad (every training use in
+    TDRN: the offsets come from a conv): the call then goes through ConvOffset2dFunction and the weight gets its gradient
+    as well.  Otherwise the output has no grad_fn -- one difference from the reference, whose Function always records:
+    with a constant input and constant offsets and a trainable weight, call ConvOffset2dFunction.apply(...) directly.
+    A forward with compute="bf16"/"fp16" gets the fp32 backward of the op."""
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _lib.require_cuda(input, "input")
+    if torch.is_grad_enabled() and (input.requires_grad or offset.requires_grad):
+        return ConvOffset2dFunction.apply(input, offset, weight, stride, padding, dilation, deform_groups, compute)
+    x = input.contiguous().float()
+    off = offset.contiguous().float()
+    w = weight.detach().contiguous().float()
+    return _deform_forward(x, off, w, stride, padding, dilation, deform_groups, compute)
 
 
 class ConvOffset2d(nn.Module):
