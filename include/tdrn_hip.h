@@ -258,8 +258,7 @@ typedef struct {
 /* Plan-shaping switches (tdrn_net_config.plan_flags).  Every one of them changes the launch plan only: outputs are
  * bit-identical with the bit set or clear, except TDRN_PLAN_NO_DEFORM_TS in the 16-bit modes (where the rounding of the
  * deformable heads sits differently; both stay inside the 16-bit drift bounds of tests/test_gpu_net.py).
- * The environment variables of the same names (TDRN_FUSE_FIRST=0, TDRN_LATE_SIDE=0|1|2, TDRN_STREAMS=1, TDRN_DEFORM_TS=0, TDRN_CHAIN=1)
- * are diagnostics overrides read when a plan is built; a set variable wins over the flag. */
+ * No environment variable overrides them. */
 #define TDRN_PLAN_NO_FUSE_FIRST 1   /* keep the first conv a launch of its own (its output tensor is then materialised) */
 #define TDRN_PLAN_NO_LATE_SIDE  2   /* release the side-lane convs on their true inputs instead of behind conv5_3      */
 #define TDRN_PLAN_ONE_STREAM    4   /* no side lanes: every launch on the caller's stream                              */
@@ -275,7 +274,7 @@ typedef struct {
 #define TDRN_PLAN_NO_PW1X1      1024 /* the wide 1x1 convs stay on conv_igemm.hip instead of dwpw.hip's persistent GEMM (pw1x1_kernel)     */
 #define TDRN_PLAN_NO_DW_SLIDE   2048 /* depthwise 3x3 layers on the one-row strip kernel instead of the sliding-window one (same bits)       */
 #define TDRN_PLAN_DW_SLIDE_ALL  4096 /* ... the sliding-window kernel (8-row segments) at every batch, also where it leaves CUs idle       */
-#define TDRN_PLAN_NO_CONV_WS    8192 /* the pooled Cin = 64 layer (conv1_2, with the first conv fused) stays on conv3x3_patch.hip instead of the weight-stationary conv3x3_ws.hip (conv2_1, full-resolution output, is on conv3x3_patch.hip either way unless TDRN_CONV_WS=2) */
+#define TDRN_PLAN_NO_CONV_WS    8192 /* the pooled Cin = 64 layer (conv1_2, with the first conv fused) stays on conv3x3_patch.hip instead of the weight-stationary conv3x3_ws.hip (conv2_1, full-resolution output, is on conv3x3_patch.hip either way) */
 #define TDRN_PLAN_NO_YGEMM_V2  16384 /* transform-then-sample heads: the transform on the round-3 schedule of ygemm_k256 (two barriers per tile, stores behind the
                                        multiply phase) instead of the round-5 one (deform.hip ygemm_k256_v2_kernel); same bits                    */
 #define TDRN_PLAN_NO_HEAD3X3   32768 /* the narrow fp32 3x3 heads (ARM loc) stay on conv_igemm.hip instead of head3x3.hip (different K order: the fp32 sums
@@ -394,7 +393,7 @@ TDRN_API int tdrn_net_op_timeline(tdrn_net *net, float *start_ms, float *end_ms,
  * converts it to fp32 NCHW (B,C,H,W) into out_dev.  Used by tests/ to compare every stage with
  * the oracle; not part of the hot path.  Tensors that a fused launch never materialises are not written: full-resolution
  * maps whose only reader is a fused max-pool, and -- in the 16-bit plans of the VGG trunks -- the first conv's output, which is
- * computed inside the next conv's loader (environment TDRN_FUSE_FIRST=0 keeps it as its own launch). */
+ * computed inside the next conv's loader (TDRN_PLAN_NO_FUSE_FIRST keeps it as its own launch). */
 /* The plan's ops (test / debug access, like the tensors): what each launch computes and on which tensors, so that a test can
  * recompute ANY stage from the stage's own materialised input (tests/test_gpu_pin16.py: every conv of the 16-bit plans against an
  * fp64 convolution of its device input with the 16-bit-rounded folded weights).  Tensor fields are indices for

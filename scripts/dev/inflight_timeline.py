@@ -71,7 +71,7 @@ for k in range(100):
     fl.launch(k)
 fl.sync()
 dt = (time.perf_counter() - t0) / 100
-print("shift %s/%s NP %d NB %d %s queues %s flags %s grid %s: %.3f ms per step = %.0f frames/s" % (os.environ.get("SHIFT_A", "0"), os.environ.get("SHIFT_B", "0"), NP, NB, os.environ.get("MODE", "graph"), os.environ.get("GPU_MAX_HW_QUEUES", "4"), os.environ.get("FLAGS", "0"), os.environ.get("TDRN_MAIN_GRID", "-"), dt * 1e3, B / dt))
+print("shift %s/%s NP %d NB %d %s queues %s flags %s: %.3f ms per step = %.0f frames/s" % (os.environ.get("SHIFT_A", "0"), os.environ.get("SHIFT_B", "0"), NP, NB, os.environ.get("MODE", "graph"), os.environ.get("GPU_MAX_HW_QUEUES", "4"), os.environ.get("FLAGS", "0"), dt * 1e3, B / dt))
 if os.environ.get("OPS", "0") != "0" and not fl.graph:
     # per-launch hipEvents on the production lanes of BOTH pipelines while they overlap: where does a step wait?
     eng.set_profile(1)

@@ -17,6 +17,7 @@ net.set_compute_dtype("bf16")
 sd = synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
 net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
 net.eval()
+net.set_plan_flags(int(os.environ.get("FLAGS", "0")))
 eng0 = net.engine(dev)
 pri = PriorBox(mb_cfg["VOC_320"]).forward().to(dev)
 NP = int(sys.argv[1]) if len(sys.argv) > 1 else 3

@@ -11,8 +11,6 @@ Writes
 The numbers justify the headline dtype choice and set tests/test_gpu_net.py:DRIFT_BOUNDS (<= 1.5x measured).
 """
 import argparse
-import os
-os.environ.setdefault("TDRN_FUSE_FIRST", "0")     # keep the first conv's output tensor (16-bit modes fuse it away) for the stage table
 import csv
 import importlib
 import os
@@ -24,6 +22,7 @@ import torch
 
 from oracle import net_ref
 from oracle import oracle as orc
+from tdrn_amd import _lib
 from tdrn_amd.data import mb_cfg
 from tdrn_amd.utils import synth
 
@@ -34,6 +33,7 @@ def build(mod, args, seed=0):
     net = importlib.import_module("tdrn_amd.model." + mod).build_net("test", *args)
     sd = synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, seed)
     net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    net.set_plan_flags(_lib.PLAN_NO_FUSE_FIRST)   # keep the first conv's output tensor (16-bit modes fuse it away) for the stage table
     return net.eval().to(DEV), sd
 
 

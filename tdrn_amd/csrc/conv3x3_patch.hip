@@ -55,7 +55,6 @@ struct PatchParams {
     int tiles_x, tiles_per_img;    // 2-D mode
     int m_tiles, n_tiles, items;   // items = m_tiles * n_tiles
     int M;                         // B*H*W
-    int max_wgs;                   // > 0: cap on the persistent grid
     int tail_split;                // 16-bit 128-cout kernels: an XCD's last, at most half-filled round of items runs as 64-cout half items
     // FUSE instantiation only: the layer's input is the first conv's output (3 -> 64 channels, 3x3, pad 1, stride 1, BN folded,
     // ReLU), computed here from the raw frames instead of being read back from HBM
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
     // along the couts -- 2 * rem HALF ITEMS of 256 pixels x 64 couts, one per workgroup -- and a half item runs on the same eight
     // consumer waves with one 32-cout accumulator tile each (the BN = 64 kernel's wave tile).  Every output element still sees the
     // same MFMA instruction with the same operand rows in the same K order: bit-identical whatever the batch (= the item count) does
-    // to the cut (tests/test_gpu_pin16.py, TDRN_PATCH_TAIL=0 keeps whole items).  A half item costs ~0.6 of a whole one (half the MFMAs,
+    // to the cut (tests/test_gpu_pin16.py, TDRN_PLAN_NO_PATCH_TAIL keeps whole items).  A half item costs ~0.6 of a whole one (half the MFMAs,
     // the same patch loads and barriers), so the last round shrinks from 1 to ~0.6 item times.
     [[maybe_unused]] int n_tail = 0, tail_enc = 0;       // tail_enc = 2 * item + cout half (one scalar: the kernel is at its SGPR budget)
     constexpr bool TAILOK = BN == 128 && sizeof(DT) == 2 && !FUSE;
@@ -974,8 +973,7 @@ template <typename DT, int BN> static int launch_patch_cfg(const PatchParams &p_
 {
     PatchParams p = p_in;
     // a multiple of 8 workgroups (the item split is per XCD); surplus workgroups find no item and exit
-    int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
-    if (p.max_wgs > 0 && grid > p.max_wgs) grid = p.max_wgs;
+    const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
 #ifdef TDRN_PATCH_WGTIME
     // diagnostics build: when did every workgroup of launch number TDRN_WGTIME_CALL (and the 17 after it) start and end?  (s_memrealtime,
     // 100 MHz; never inside a stream capture: the report synchronises)
@@ -1027,16 +1025,14 @@ int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s)
     const int mode = patch_conv_supported(a);
     if (!mode) return TDRN_E_UNSUPPORTED;
     if (out_pool && (mode < 0 || (a.H & 1) || (a.W & 1))) return TDRN_E_UNSUPPORTED;
-    if (ws_conv_supported(a)) {                           // conv3x3_ws.hip (Cin == 64): same arithmetic, same bits
+    if (out_pool && ws_conv_supported(a)) {              // conv3x3_ws.hip (Cin == 64, pooled output): same arithmetic, same bits
         const int rc = launch_conv3x3_ws(a, out_pool, s);
         if (rc != TDRN_E_UNSUPPORTED) return rc;         // (it declines launches too small to fill the chip and fused launches it has no LDS for)
     }
-    // (pooled layers stay here: conv3x3_pp.hip's POOL instantiation no longer spills with the register-only epilogue and is bit-identical --
-    // tests/test_gpu_pin16.py ran green on it -- but conv3_3 measured 210 us there against 204-210 us here: no gain; TDRN_PP_POOL=1 selects it)
-    static int pp_pool = -1;
-    if (pp_pool < 0) { const char *e = getenv("TDRN_PP_POOL"); pp_pool = e ? atoi(e) : 0; }
-    if ((!out_pool || pp_pool) && pp_conv_supported(a)) {    // conv3x3_pp.hip: same arithmetic, same bits
-        const int rc = launch_conv3x3_pp(a, out_pool, s);
+    // (pooled layers stay here: a pooled variant of conv3x3_pp.hip was bit-identical, but conv3_3 measured 210 us there against
+    // 204-210 us here: no gain)
+    if (!out_pool && pp_conv_supported(a)) {             // conv3x3_pp.hip: same arithmetic, same bits
+        const int rc = launch_conv3x3_pp(a, s);
         if (rc != TDRN_E_UNSUPPORTED) return rc;         // (it declines launches too small to fill the chip)
     }
     PatchParams p;
@@ -1057,20 +1053,15 @@ int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s)
     }
     // 128-cout items unless they would leave most CUs idle (20x20 maps at small batch): 64-cout items double
     // the item count for the same per-output arithmetic (K order unchanged, results identical)
-    static int small_bn = -1;
-    if (small_bn < 0) { const char *e = getenv("TDRN_PATCH_SMALL_BN"); small_bn = e ? atoi(e) : 1; }
     int BN = a.Npad % 128 == 0 ? 128 : 64;
-    if (small_bn && BN == 128 && p.m_tiles * (a.Npad / 128) < 160) BN = 64;
+    if (BN == 128 && p.m_tiles * (a.Npad / 128) < 160) BN = 64;
     p.n_tiles = a.Npad / BN;
     p.items = p.m_tiles * p.n_tiles;
     static int ablate = -1;
     if (ablate < 0) ablate = dev_ablate_env("TDRN_CONV_ABLATE");     // (developer builds only: common.h)
     p.ablate = ablate;
     p.fx = a.fuse_x; p.fw = a.fuse_w; p.fb = a.fuse_b; p.fS = a.H; p.fCout = a.fuse_cout;
-    p.max_wgs = a.max_wgs > 0 ? (a.max_wgs / 8) * 8 : 0;
-    static int tail = -1;
-    if (tail < 0) { const char *e = getenv("TDRN_PATCH_TAIL"); tail = e ? atoi(e) : 1; }
-    p.tail_split = tail && !(a.kdisable & 1024);     // (TDRN_PLAN_NO_PATCH_TAIL)
+    p.tail_split = !(a.kdisable & 1024);             // (TDRN_PLAN_NO_PATCH_TAIL)
     if (p.items <= 0) return TDRN_OK;
 #ifdef TDRN_PATCH_STAMP
     // diagnostics build: synchronise after every launch and print the mean cycles per wave in each state

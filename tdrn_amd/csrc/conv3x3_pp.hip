@@ -39,7 +39,6 @@
 // read only behind the issuing wave's counted vmcnt AND a later barrier; a buffer is re-filled only behind a barrier
 // that every reader passed after an lgkmcnt(0).
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
@@ -53,7 +52,7 @@ namespace tdrn {
 struct PPParams {
     const char *in, *w, *zero;
     const float *bias;
-    char *out, *out_pool;          // NHWC [B][H][W][Cs] and optional pooled [B][H/2][W/2][Cs]
+    char *out;                     // NHWC [B][H][W][Cs]
     int B, H, W, Cin, Cout, Cs, Ktot;
     int relu;
     int tiles_x, tiles_per_img;    // 2-D tiles
@@ -117,9 +116,7 @@ constexpr int kPPPieces = (kPPSlots + 7) / 8;     // patch pieces per wave and c
 }  // namespace
 
 // TW = 32 / 16: 2-D tiles of (256/TW) x TW pixels of one image; TW = 0: flat tiles of 256 consecutive NHW pixels.
-// POOL: the instantiation that also (or only) writes the fused MaxPool2d(2,2) output (two layers of a VGG trunk); kept apart so
-// that the other layers' register allocation does not carry the pooled epilogue.
-template <typename DT, int TW, bool POOL>
+template <typename DT, int TW>
 __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
 {
     static_assert(sizeof(DT) == 2, "16-bit element types only");
@@ -305,7 +302,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
 
     int cur_mt = -1, n0 = 0;
     long long tile_pix0 = 0;                            // 2-D: global pixel of the tile's (0,0); flat: mt*256
-    int tile_row0 = 0, tile_x0 = 0;                     // 2-D: b*H + y and x of the tile's (0,0)
     auto setup_item = [&](int item) {
         const int mt = mt_of(item);
         n0 = nt_of(item) * BN;
@@ -314,9 +310,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
         if (TW) {
             const int b = mt / p.tiles_per_img, tt = mt - b * p.tiles_per_img;
             const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
-            tile_row0 = b * p.H + ty * TH;
-            tile_x0 = tx * TW;
-            tile_pix0 = (long long)tile_row0 * p.W + tile_x0;
+            tile_pix0 = (long long)(b * p.H + ty * TH) * p.W + tx * TW;
             return;
         }
         tile_pix0 = (long long)mt * 256;
@@ -349,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             const long long m = tile_pix0 + i;
             return m < p.M ? m : -1;
         };
-        if (p.out && !(TDRN_PP_ABLATE & 4)) {
+        if (p.out && !(TDRN_PP_ABLATE & 4)) {          // (p.out is never null; without the test hipcc schedules the step loop differently)
             // Round 5: straight from the registers.  Group c = 4 ci + g is the 16-byte chunk c of my pixel's span of 128 couts; lane r32 has its
             // first 8 bytes, lane r32 + 32 the second: v_permlane32_swap on a chunk PAIR gives each of the two lanes one whole chunk
             // (cdna_hip_programming.md T21) -> eight dwordx4 stores per pixel fragment, no staging strip, no LDS round trips, no wave barriers.
@@ -374,60 +368,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
                     auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
                     if (gp >= 0 && cbase + (2 * pr + hh) * 8 < p.Cout)
                         *(u32x4 *)(row + (2 * pr + hh) * 16) = u32x4{rx[0], ry[0], rx[1], ry[1]};
-                }
-            }
-        }
-        if constexpr (POOL && TW != 0) if (p.out_pool) {
-            // fused MaxPool2d(2,2) on the RAW accumulators (max commutes with the monotonic bias + ReLU + rounding applied afterwards), straight
-            // from the registers as in conv3x3_patch.hip (round 5): the partner row is my other pixel fragment (TW = 32) or lane ^ 16
-            // (v_permlane16_swap), the partner column lane ^ 1 (DPP); the window's 2 / 4 lanes then hold the same maxima and store different
-            // chunk pairs of the same pooled pixel (v_permlane32_swap pairs -> dwordx4).
-            typedef short pk_s2 __attribute__((ext_vector_type(2)));
-            const pk_s2 relu_lo = p.relu ? pk_s2{0, 0} : pk_s2{(short)-32768, (short)-32768};
-            auto pkr = [&](float a, float b) -> unsigned {
-                return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(pk_s2, pack2<DT>(a, b)), relu_lo));
-            };
-            const int PW = p.W >> 1;
-            const int cbase = n0 + grp * BNH;
-            constexpr int NPAIR = 2 * WC;                       // 8 chunk pairs per pixel
-            constexpr int NDUP = TW == 32 ? 2 : 4;              // lanes holding the same window
-            const int sel = TW == 32 ? (r32 & 1) : ((r32 & 1) | ((r32 >> 3) & 2));
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt) {
-                if (TW == 32 && pt == 1) break;
-                const int i = cw * 64 + pt * 32 + r32;
-                const long long gpool = (long long)((tile_row0 + (i >> LGTW)) >> 1) * PW + ((tile_x0 + (i & (TW - 1))) >> 1);
-                char *row = p.out_pool + ((size_t)gpool * p.Cs + cbase) * ES;
-                // round rd: chunk pairs rd * NDUP .. rd * NDUP + NDUP - 1, one per lane of the window (only their maxima are computed now:
-                // 16 packed registers live at a time instead of 64)
-#pragma unroll
-                for (int rd = 0; rd < NPAIR / NDUP; ++rd) {
-                    uint2 a = make_uint2(0u, 0u), b = make_uint2(0u, 0u);
-#pragma unroll
-                    for (int d = 0; d < NDUP; ++d) {
-                        const int pr = rd * NDUP + d, ci = pr >> 1, g0 = 2 * (pr & 1);
-                        float m[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            float v = acc[ci][pt][4 * g0 + j];
-                            if (TW == 32) {
-                                v = fmaxf(v, acc[ci][1][4 * g0 + j]);
-                            } else {
-                                float va = v, vb = v;
-                                asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(va), "+v"(vb));
-                                v = fmaxf(va, vb);
-                            }
-                            m[j] = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));
-                        }
-                        const bool mine = sel == d;
-                        const unsigned ax = pkr(m[0], m[1]), ay = pkr(m[2], m[3]), bx = pkr(m[4], m[5]), by = pkr(m[6], m[7]);
-                        a.x = mine ? ax : a.x; a.y = mine ? ay : a.y; b.x = mine ? bx : b.x; b.y = mine ? by : b.y;
-                    }
-                    const int mypr = rd * NDUP + sel;
-                    auto rx = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-                    auto ry = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-                    if (cbase + (2 * mypr + hh) * 8 < p.Cout)
-                        *(u32x4 *)(row + (2 * mypr + hh) * 16) = u32x4{rx[0], ry[0], rx[1], ry[1]};
                 }
             }
         }
@@ -720,32 +660,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
 }
 
 // ---------------------------------------------------------------------------------------------
-static int g_pp_override = -1;                          // dev harness / tests: -1 = environment, 0 / 1 = forced
-void conv_pp_force(int v) { g_pp_override = v; }
-int conv_pp_enabled()
-{
-    if (g_pp_override >= 0) return g_pp_override;
-    static int e = -1;
-    if (e < 0) { const char *s = getenv("TDRN_CONV_PP"); e = s ? atoi(s) : 1; }
-    return e;
-}
-
-static int g_pp_sk_override = -1;
-void conv_pp_sk_force(int v) { g_pp_sk_override = v; }
-int conv_pp_sk_enabled()
-{
-    if (g_pp_sk_override >= 0) return g_pp_sk_override;
-    static int e = -1;
-    if (e < 0) { const char *s = getenv("TDRN_CONV_PP_SK"); e = s ? atoi(s) : 1; }
-    return e;
-}
 // scratch of the chained split: 256 flag words + one 256-KiB accumulator slab per workgroup
 size_t conv_pp_sk_bytes() { return 1024 + (size_t)256 * 8 * 32 * 64 * 16; }
 
 // the layers this kernel takes over from conv3x3_patch.hip: 16-bit, >= 2 channel chunks, couts in whole 256-groups
 int pp_conv_supported(const ConvArgs &a)
 {
-    if (!conv_pp_enabled() || (a.kdisable & 1)) return 0;
+    if (a.kdisable & 1) return 0;
     if (a.dtype == TDRN_F32 || a.fuse_x) return 0;
     // (Cin = 128 -- two chunks, 18 steps per item -- stays with conv3x3_patch.hip: the per-item cost of this kernel, drain +
     // epilogue + re-stagger, weighs 10 % there: 125 vs 116 us on conv3_1 in the net)
@@ -753,16 +674,13 @@ int pp_conv_supported(const ConvArgs &a)
     return patch_conv_supported(a);
 }
 
-int launch_conv3x3_pp(const ConvArgs &a, void *out_pool, hipStream_t s)
+int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s)
 {
     const int mode = pp_conv_supported(a);
     if (!mode) return TDRN_E_UNSUPPORTED;
-    // pooled layers (conv3_3: the pooled output only): the POOL instantiation with the register-only pooled epilogue (round 5; with the staged
-    // epilogue its 256-register budget spilled inside the step loop).  Flat tiles have no pooled variant.
-    if (out_pool && (mode < 0 || (a.H & 1) || (a.W & 1))) return TDRN_E_UNSUPPORTED;
     PPParams p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.zero = (const char *)a.zero_page; p.bias = a.bias;
-    p.out = (char *)a.out; p.out_pool = (char *)out_pool;
+    p.out = (char *)a.out;
     p.B = a.B; p.H = a.H; p.W = a.W; p.Cin = a.Cin; p.Cout = a.Cout; p.Cs = (int)a.o_cs; p.Ktot = 9 * a.Cin;
     p.relu = a.relu;
     p.M = a.B * a.H * a.W;
@@ -777,39 +695,30 @@ int launch_conv3x3_pp(const ConvArgs &a, void *out_pool, hipStream_t s)
     }
     p.n_tiles = a.Npad / 256;
     p.items = p.m_tiles * p.n_tiles;
-    {
-        // With two or more cout tiles an XCD whose items are (pixel tile, cout tile) pairs keeps the WHOLE weight matrix live (4.7 MB at
-        // 512 x 512, more than its 4-MB L2, and under the chained split its workgroups are at different channel chunks at the same
-        // time): cout-tile-major numbering gives an XCD one cout tile's weights (2.4 MB) at the price of reading every patch on two XCDs.
-        static int nm = -1;
-        if (nm < 0) { const char *e = getenv("TDRN_PP_NMAJOR"); nm = e ? atoi(e) : 1; }
-        p.n_major = (nm && p.n_tiles > 1) ? 1 : 0;
-    }
+    // With two or more cout tiles an XCD whose items are (pixel tile, cout tile) pairs keeps the WHOLE weight matrix live (4.7 MB at
+    // 512 x 512, more than its 4-MB L2, and under the chained split its workgroups are at different channel chunks at the same
+    // time): cout-tile-major numbering gives an XCD one cout tile's weights (2.4 MB) at the price of reading every patch on two XCDs.
+    p.n_major = p.n_tiles > 1 ? 1 : 0;
     if (p.items <= 0) return TDRN_OK;
     // below ~3/4 of a full grid the loader/consumer kernel's smaller (128- / 64-cout) items fill more CUs: measured 2x faster
     // at 50-100 items, equal at 200 (the two kernels produce the same bits, so the choice may depend on the batch)
     if (p.items < 192) return TDRN_E_UNSUPPORTED;
-    int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
-    const int cap = a.max_wgs > 0 ? (a.max_wgs / 8) * 8 : 0;
-    if (cap > 0 && grid > cap) grid = cap;
+    const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
     // chained split when it shortens the launch: a full grid, more than one item per workgroup, and an item count that does
     // not divide evenly (otherwise whole items are already balanced); the choice changes no output bit
     p.sk_slab = nullptr; p.sk_flag = nullptr;
     p.status = a.status; p.fault = a.fault_handoff; p.poll_max = a.fault_handoff ? (1u << 10) : (1u << 20);
     // (grid == 256: every workgroup of the launch is resident at once, see the poll in begin_acc)
-    if (a.sk_ws && conv_pp_sk_enabled() && !(a.kdisable & 2) && (grid == 256 || (cap > 0 && grid == cap && cap >= 192)) && p.items > grid && p.items % grid != 0) {
+    if (a.sk_ws && !(a.kdisable & 2) && grid == 256 && p.items > grid && p.items % grid != 0) {
         p.sk_flag = (unsigned *)a.sk_ws;
         p.sk_slab = (float *)((char *)a.sk_ws + 1024);
         if (!a.sk_flags_zero) TDRN_HIP_TRY(hipMemsetAsync(p.sk_flag, 0, 1024, s));
     }
 #define PP_LAUNCH(DT)                                                                                                  \
     do {                                                                                                               \
-        if (out_pool) {                                                                                                \
-            if (tw == 32) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 32, true>), dim3(grid), dim3(512), 0, s, p);     \
-            else hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 16, true>), dim3(grid), dim3(512), 0, s, p);               \
-        } else if (tw == 0) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 0, false>), dim3(grid), dim3(512), 0, s, p);    \
-        else if (tw == 32) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 32, false>), dim3(grid), dim3(512), 0, s, p);   \
-        else hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 16, false>), dim3(grid), dim3(512), 0, s, p);                  \
+        if (tw == 0) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 0>), dim3(grid), dim3(512), 0, s, p);                  \
+        else if (tw == 32) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 32>), dim3(grid), dim3(512), 0, s, p);           \
+        else hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 16>), dim3(grid), dim3(512), 0, s, p);                          \
     } while (0)
     if (a.dtype == TDRN_BF16) PP_LAUNCH(bf16_t);
     else PP_LAUNCH(f16_t);

@@ -27,7 +27,6 @@
 // 2 rows, then 8 rows per further tile -- and the consumers multiply tile k while batch k + 2 is produced; the ring's slot
 // counter runs on across units.
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
@@ -37,9 +36,10 @@ namespace tdrn {
 struct WsParams {
     const char *in, *w, *zero;
     const float *bias;
-    char *out, *out_pool;          // NHWC [B][H][W][Cs] and / or pooled [B][H/2][W/2][Cs]
+    const void *reserved;          // never read: with the arguments behind it moved up, hipcc schedules the fused variants differently
+    char *out_pool;                // pooled NHWC [B][H/2][W/2][Cs]
     int B, H, W, Cout, Cs, Ktot;   // Cin == 64 (one 128-byte chunk); Ktot = 9 * 64
-    int relu;
+    int relu;                      // always 1 (the launcher declines others); never read either, kept for the same reason
     int SX, TY, TSEG, NSEG, NT;    // strips per row (W / 32), tiles per column (H / 8), tiles per segment, segments, cout tiles
     int units;                     // NT * B * SX * NSEG; unit = ((nt * B + b) * SX + sx) * NSEG + seg
     // FUSE: the layer's input is the first conv's output, computed here from the raw frames
@@ -118,9 +118,9 @@ constexpr int kRawBytes = kRawPieces * 256;             // 4352 per buffer
 
 }  // namespace
 
-// MODE: 1 = full-resolution output, 2 = fused MaxPool2d(2,2) output (compile-time: the epilogue's ops sit inside the MFMA loop)
+// The output is the fused MaxPool2d(2,2) of the conv (the full-resolution map never leaves the chip).
 // U8 (FUSE only): the raw frames are uint8 planes
-template <typename DT, bool FUSE, int MODE, bool U8 = false>
+template <typename DT, bool FUSE, bool U8 = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
 {
     static_assert(sizeof(DT) == 2, "16-bit element types only");
@@ -264,7 +264,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
         // writes): a producer wave is alone on its SIMD beside a consumer that multiplies, so nothing else hides its LDS and
         // matrix-pipe latencies (one slice at a time: ~2950 cycles per slice, the producers were the critical path of the launch).
         // The accumulators start at the bias, held in registers for the whole launch.
-        // (ReLU on the packed pair as a signed 16-bit maximum with 0, see the consumers' pack_relu: exact for finite values)
+        // (ReLU on the PACKED 16-bit pair as a signed 16-bit maximum with 0 -- v_pk_max_i16: a negative value, and -0, has its sign bit
+        // set, i.e. is a negative integer; finite values come out exactly as max(v, 0) before the conversion does)
         typedef short ws_s2p __attribute__((ext_vector_type(2)));
         auto fc_relu = [&](float a, float b) -> unsigned {
             return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(ws_s2p, pack2<DT>(a, b)), ws_s2p{0, 0}));
@@ -437,81 +438,55 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
     unsigned wa[2];
 #pragma unroll
     for (int ci = 0; ci < 2; ++ci) wa[ci] = (unsigned)(OFF_W + (ci * 32 + r32) * 128 + ((hh ^ ((r32 >> 1) & 7)) << 4));
-    // ReLU on the PACKED 16-bit pair as a signed 16-bit maximum with 0 (v_pk_max_i16: a negative value -- and -0 -- has its sign bit set,
-    // i.e. is a negative integer; finite values come out exactly as max(v, 0) before the conversion does); no ReLU: maximum with -32768
     typedef short ws_s2 __attribute__((ext_vector_type(2)));
-    const ws_s2 relu_lo = p.relu ? ws_s2{0, 0} : ws_s2{(short)-32768, (short)-32768};
-    auto pack_relu = [&](float a, float b) -> unsigned {
-        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(ws_s2, pack2<DT>(a, b)), relu_lo));
-    };
 
     // ---- epilogue in two halves ------------------------------------------------------------------------------------------------
     // A lane holds, per pixel fragment, 8 groups (ci, g) of 4 couts: group c = 4 ci + g is the 16-byte chunk c of the pixel's 128-byte
     // row, of which lane r32 (hh = 0) has the first 8 bytes and lane r32 + 32 the second.  (1) Right behind a tile's last MFMAs the
-    // accumulators are CONVERTED into packed 16-bit registers (full-resolution rows: 2 x 8 groups; pooled: the fused MaxPool2d(2,2) on
-    // the raw accumulators first -- max commutes with the monotonic bias + ReLU; the partner row is my other pixel fragment, the partner
-    // column lane ^ 1, a DPP quad permute -- then 8 groups), and the accumulators are free for the next tile.  (2) The STORES run as
-    // independent ops between the MFMA groups of the next tile's first steps: v_permlane32_swap on a PAIR of chunks (c, c + 1) gives the
-    // lower lane all 16 bytes of chunk c and the upper lane all of chunk c + 1 (cdna_hip_programming.md T21), one dwordx4 store per pair,
-    // 32 contiguous bytes per pixel and instruction, no LDS round trip.  Pooled rows: both lanes of a column pair hold the same maxima and
-    // store the same bytes to the same pooled pixel.  (A consumer wave is alone on its SIMD beside a producer: the first version's epilogue
-    // -- LDS staging rounds, ds_bpermute -- ran on its own for 4150 of a tile's 9700 cycles.)
-    uint2 pk_out[MODE & 1 ? 2 : 1][8], pk_pool[8];     // packed groups of the finished tile: [pixel fragment][chunk c]
-    char *pd_out[2] = {nullptr, nullptr}, *pd_pool = nullptr;      // ... and where its rows go (null: nothing pending)
+    // accumulators are CONVERTED into 8 groups of packed 16-bit registers by the fused MaxPool2d(2,2) on the raw accumulators -- max
+    // commutes with the monotonic bias + ReLU; the partner row is my other pixel fragment, the partner column lane ^ 1, a DPP quad permute
+    // -- and the accumulators are free for the next tile.  (2) The STORES run as independent ops between the MFMA groups of the next
+    // tile's first steps: v_permlane32_swap on a PAIR of chunks (c, c + 1) gives the lower lane all 16 bytes of chunk c and the upper lane
+    // all of chunk c + 1 (cdna_hip_programming.md T21), one dwordx4 store per pair, 32 contiguous bytes per pixel and instruction, no LDS
+    // round trip.  Both lanes of a column pair hold the same maxima.  (A consumer wave is alone on its SIMD beside a producer: the first
+    // version's epilogue -- LDS staging rounds, ds_bpermute -- ran on its own for 4150 of a tile's 9700 cycles.)
+    uint2 pk_pool[8];                                   // packed groups of the finished tile: [chunk c]
+    char *pd_pool = nullptr;                            // ... and where its row goes (null: nothing pending)
     auto convert = [&]() {
         if constexpr (TDRN_WS_ABLATE & 4) return;
-        if constexpr (MODE & 1) {
+        // MaxPool2d(2,2) + ReLU on the PACKED values, as signed 16-bit maxima: rounding to 16 bits is monotonic, so it commutes with the
+        // maximum; after max(., 0) every candidate is a non-negative 16-bit float, whose bit patterns order like integers -- and
+        // max(max(a, b), 0) = max(max(a, 0), max(b, 0)).  (Pooled layers always carry a ReLU: the launcher declines otherwise.)
+        // Only compiler-visible instructions here: the accumulators come straight out of the MFMAs, and hipcc pads the MFMA -> VALU
+        // and VALU -> DPP wait states for its own instructions only, not around inline asm.
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
+        for (int ci = 0; ci < 2; ++ci)
 #pragma unroll
-                for (int ci = 0; ci < 2; ++ci)
+            for (int g = 0; g < 4; ++g) {
+                unsigned w2[2];
 #pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        pk_out[pt][4 * ci + g] = make_uint2(pack_relu(acc[ci][pt][4 * g], acc[ci][pt][4 * g + 1]), pack_relu(acc[ci][pt][4 * g + 2], acc[ci][pt][4 * g + 3]));
-        }
-        if constexpr (MODE & 2) {
-            // MaxPool2d(2,2) + ReLU on the PACKED values, as signed 16-bit maxima: rounding to 16 bits is monotonic, so it commutes with the
-            // maximum; after max(., 0) every candidate is a non-negative 16-bit float, whose bit patterns order like integers -- and
-            // max(max(a, b), 0) = max(max(a, 0), max(b, 0)).  (Pooled layers always carry a ReLU: the launcher declines otherwise.)
-            // Only compiler-visible instructions here: the accumulators come straight out of the MFMAs, and hipcc pads the MFMA -> VALU
-            // and VALU -> DPP wait states for its own instructions only, not around inline asm.
-#pragma unroll
-            for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    unsigned w2[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const ws_s2 zero = {0, 0};
-                        const ws_s2 u0 = __builtin_bit_cast(ws_s2, pack2<DT>(acc[ci][0][4 * g + 2 * h], acc[ci][0][4 * g + 2 * h + 1]));
-                        const ws_s2 u1 = __builtin_bit_cast(ws_s2, pack2<DT>(acc[ci][1][4 * g + 2 * h], acc[ci][1][4 * g + 2 * h + 1]));
-                        const ws_s2 m = __builtin_elementwise_max(__builtin_elementwise_max(u0, u1), zero);
-                        const ws_s2 nb = __builtin_bit_cast(ws_s2, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0xB1, 0xF, 0xF, true));
-                        w2[h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(m, nb));
-                    }
-                    pk_pool[4 * ci + g] = make_uint2(w2[0], w2[1]);
+                for (int h = 0; h < 2; ++h) {
+                    const ws_s2 zero = {0, 0};
+                    const ws_s2 u0 = __builtin_bit_cast(ws_s2, pack2<DT>(acc[ci][0][4 * g + 2 * h], acc[ci][0][4 * g + 2 * h + 1]));
+                    const ws_s2 u1 = __builtin_bit_cast(ws_s2, pack2<DT>(acc[ci][1][4 * g + 2 * h], acc[ci][1][4 * g + 2 * h + 1]));
+                    const ws_s2 m = __builtin_elementwise_max(__builtin_elementwise_max(u0, u1), zero);
+                    const ws_s2 nb = __builtin_bit_cast(ws_s2, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0xB1, 0xF, 0xF, true));
+                    w2[h] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(m, nb));
                 }
-        }
+                pk_pool[4 * ci + g] = make_uint2(w2[0], w2[1]);
+            }
     };
-    // op 0-7: full-resolution rows (pixel fragment op / 4, chunk pair op % 4); ops 8-9: pooled rows -- both lanes of a column pair hold the
-    // same maxima, so the even lane stores pair 2 (op - 8) and the odd lane pair 2 (op - 8) + 1 of the same pooled pixel: TWO stores per
-    // tile and wave instead of four with the odd lanes idle (a store costs the issuing wave ~150 cycles: 8 % of the launch with four)
+    // op j = 0, 1: both lanes of a column pair hold the same maxima, so the even lane stores pair 2 j and the odd lane pair 2 j + 1 of the
+    // same pooled pixel: TWO stores per tile and wave instead of four with the odd lanes idle (a store costs the issuing wave ~150 cycles:
+    // 8 % of the launch with four)
     auto store_op = [&](auto opc) {
-        constexpr int OP = decltype(opc)::value;
+        constexpr int j = decltype(opc)::value;
         if constexpr (TDRN_WS_ABLATE & 4) return;
         uint2 a, b;
-        char *dst;
-        if constexpr (OP < 8) {
-            constexpr int pr = OP & 3, pt = (MODE & 1) ? (OP >> 2) : 0;
-            a = pk_out[pt][2 * pr]; b = pk_out[pt][2 * pr + 1];
-            dst = pd_out[pt] + pr * 32 + hh * 16;
-        } else {
-            constexpr int j = OP - 8;
-            const bool odd = r32 & 1;
-            a.x = odd ? pk_pool[4 * j + 2].x : pk_pool[4 * j].x;     a.y = odd ? pk_pool[4 * j + 2].y : pk_pool[4 * j].y;
-            b.x = odd ? pk_pool[4 * j + 3].x : pk_pool[4 * j + 1].x; b.y = odd ? pk_pool[4 * j + 3].y : pk_pool[4 * j + 1].y;
-            dst = pd_pool + (2 * j + (odd ? 1 : 0)) * 32 + hh * 16;
-        }
+        const bool odd = r32 & 1;
+        a.x = odd ? pk_pool[4 * j + 2].x : pk_pool[4 * j].x;     a.y = odd ? pk_pool[4 * j + 2].y : pk_pool[4 * j].y;
+        b.x = odd ? pk_pool[4 * j + 3].x : pk_pool[4 * j + 1].x; b.y = odd ? pk_pool[4 * j + 3].y : pk_pool[4 * j + 1].y;
+        char *dst = pd_pool + (2 * j + (odd ? 1 : 0)) * 32 + hh * 16;
         auto rx = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
         auto ry = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
         if constexpr (TDRN_WS_ABLATE & 8) {             // (diagnostics: everything but the store instruction itself; p.B < 0 never holds)
@@ -520,16 +495,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
             *(u32x4 *)dst = u32x4{rx[0], ry[0], rx[1], ry[1]};
         }
     };
-    constexpr int NOPS = (MODE & 1 ? 8 : 0) + (MODE & 2 ? 2 : 0);
-    auto op_of = [](int i) constexpr -> int { return (MODE & 1) ? i : 8 + i; };      // i-th op of this MODE
     auto flush = [&]() {
-        if (!pd_pool && !pd_out[0]) return;
-        store_op(std::integral_constant<int, op_of(0)>{}); store_op(std::integral_constant<int, op_of(1)>{});
-        if constexpr (NOPS > 2) {
-            store_op(std::integral_constant<int, op_of(2)>{}); store_op(std::integral_constant<int, op_of(3)>{});
-            store_op(std::integral_constant<int, op_of(4)>{}); store_op(std::integral_constant<int, op_of(5)>{});
-            store_op(std::integral_constant<int, op_of(6)>{}); store_op(std::integral_constant<int, op_of(7)>{});
-        }
+        if (!pd_pool) return;
+        store_op(std::integral_constant<int, 0>{}); store_op(std::integral_constant<int, 1>{});
     };
 
     WS_STAMP_DECL
@@ -625,8 +593,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
             }
             __builtin_amdgcn_sched_barrier(0);
             // the previous tile's store op (s - 1) / 2 in the shadow of this step's MFMAs
-            if constexpr (HAVE_OLD && (s & 1) && (s >> 1) < NOPS) {
-                store_op(std::integral_constant<int, op_of(s >> 1)>{});
+            if constexpr (HAVE_OLD && (s & 1) && (s >> 1) < 2) {
+                store_op(std::integral_constant<int, (s >> 1)>{});
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -638,13 +606,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
         convert();
         const int n0 = un.nt * 64;
         const int ty = un.y0 + 8 * k + 2 * cw;          // image row of my first pixel fragment
-        if constexpr (MODE & 1) {
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-                pd_out[pt] = p.out + ((((size_t)un.b * p.H + ty + pt) * p.W + un.x0 + r32) * p.Cs + n0) * 2;
-        }
-        if constexpr (MODE & 2)
-            pd_pool = p.out_pool + (((size_t)(((size_t)un.b * p.H + ty) >> 1) * (p.W >> 1) + ((un.x0 + r32) >> 1)) * p.Cs + n0) * 2;
+        pd_pool = p.out_pool + (((size_t)(((size_t)un.b * p.H + ty) >> 1) * (p.W >> 1) + ((un.x0 + r32) >> 1)) * p.Cs + n0) * 2;
         WS_STAMP(2);                                    // step 35 + conversion
     };
     int ntile = 0;
@@ -697,20 +659,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
 }
 
 // ---------------------------------------------------------------------------------------------
-static int g_ws_override = -1;                          // dev harness: -1 = environment, 0 / 1 = forced, 2 = forced also below the size where it pays
-void conv_ws_force(int v) { g_ws_override = v; }
-int conv_ws_enabled()
-{
-    if (g_ws_override >= 0) return g_ws_override != 0;
-    static int e = -1;
-    if (e < 0) { const char *s = getenv("TDRN_CONV_WS"); e = s ? atoi(s) : 1; }
-    return e;
-}
-
 // the layers this kernel takes over from conv3x3_patch.hip: 16-bit, ONE 64-channel chunk, 2-D geometry in whole 8 x 32 tiles
 int ws_conv_supported(const ConvArgs &a)
 {
-    if (!conv_ws_enabled() || (a.kdisable & 64)) return 0;
+    if (a.kdisable & 64) return 0;
     if (a.dtype == TDRN_F32 || a.Cin != 64 || a.Npad % 64 || a.Cout % 64) return 0;       // (Cout = the output tensor's padded channel count)
     if (a.W % 32 || a.H % 8) return 0;
     return patch_conv_supported(a) != 0;
@@ -719,11 +671,14 @@ int ws_conv_supported(const ConvArgs &a)
 int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
 {
     if (!ws_conv_supported(a)) return TDRN_E_UNSUPPORTED;
-    if (out_pool && ((a.H & 1) || (a.W & 1) || !a.relu)) return TDRN_E_UNSUPPORTED;      // (the pooled epilogue's integer maxima assume the ReLU)
-    if (!a.out && !out_pool) return TDRN_E_ARG;
+    // Pooled output only.  A full-resolution output (conv2_1) would be eight 1-KiB stores per tile and consumer wave, ~150 cycles of the
+    // wave's time each, against two for a pooled tile: it measured 127-128 us in the net against 123-126 us on conv3x3_patch.hip (whose
+    // two consumer waves per SIMD hide each other's stores), so conv3x3_patch.hip keeps such layers.
+    if (!out_pool || a.out) return TDRN_E_UNSUPPORTED;
+    if ((a.H & 1) || (a.W & 1) || !a.relu) return TDRN_E_UNSUPPORTED;      // (the pooled epilogue's integer maxima assume the ReLU)
     WsParams p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.zero = (const char *)a.zero_page; p.bias = a.bias;
-    p.out = (char *)a.out; p.out_pool = (char *)out_pool;
+    p.reserved = nullptr; p.out_pool = (char *)out_pool;
     p.B = a.B; p.H = a.H; p.W = a.W; p.Cout = a.Cout; p.Cs = (int)a.o_cs; p.Ktot = 9 * a.Cin;
     p.relu = a.relu;
     p.SX = a.W / 32; p.TY = a.H / 8; p.NT = a.Cout / 64;      // (cout tiles of all-padding rows beyond Cout are not computed)
@@ -731,12 +686,10 @@ int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
     p.fx8 = a.fuse_x8; p.fmean[0] = a.fuse_mean[0]; p.fmean[1] = a.fuse_mean[1]; p.fmean[2] = a.fuse_mean[2];
     if (a.fuse_x && a.fuse_x8) return TDRN_E_ARG;
     if (a.fuse_x || a.fuse_x8) {
-        // the fused variant keeps LDS for the raw tiles instead of a full staging strip: pooled output only, one cout tile
-        if (a.out || !out_pool || p.NT != 1 || a.H != a.W || a.fuse_cout > 64) return TDRN_E_UNSUPPORTED;
+        // the fused variant keeps LDS for the raw tiles instead of a full staging strip: one cout tile
+        if (p.NT != 1 || a.H != a.W || a.fuse_cout > 64) return TDRN_E_UNSUPPORTED;
     }
     int grid = 256;
-    if (a.max_wgs > 0 && grid > (a.max_wgs / 8) * 8) grid = (a.max_wgs / 8) * 8;
-    if (grid < 8) return TDRN_E_UNSUPPORTED;
     // Rows per unit: a unit of T tiles costs ~T + 0.6 tile times (its first 10 rows are produced before its first tile can start, 8 of
     // them under the previous unit's last tile); the launch takes ceil(units / grid) units per workgroup.  Depends on the geometry
     // and the batch only through the unit count -- and the choice changes no output bit.
@@ -759,7 +712,7 @@ int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
     p.units = (int)units;
     if (p.units < grid) grid = ((p.units + 7) / 8) * 8;
     // below ~3/4 of the chip conv3x3_patch.hip's independent 256-pixel items spread better (small batches)
-    if (p.units < 192 && g_ws_override != 2) return TDRN_E_UNSUPPORTED;     // (2: the dev harness runs small cases through it)
+    if (p.units < 192) return TDRN_E_UNSUPPORTED;
 #ifdef TDRN_WS_STAMP
     static unsigned *stamps = nullptr;
     if (!stamps) TDRN_HIP_TRY(hipMalloc((void **)&stamps, 256 * 8 * 4 * sizeof(unsigned)));
@@ -791,21 +744,10 @@ int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
 #endif
 #define WS_LAUNCH(DT)                                                                                              \
     do {                                                                                                           \
-        if (a.fuse_x8) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, true, 2, true>), dim3(grid), dim3(512), 0, s, p); \
-        else if (a.fuse_x) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, true, 2>), dim3(grid), dim3(512), 0, s, p);  \
-        else if (mode == 1) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, false, 1>), dim3(grid), dim3(512), 0, s, p); \
-        else hipLaunchKernelGGL((conv3x3_ws_kernel<DT, false, 2>), dim3(grid), dim3(512), 0, s, p);               \
+        if (a.fuse_x8) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, true, true>), dim3(grid), dim3(512), 0, s, p);    \
+        else if (a.fuse_x) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, true>), dim3(grid), dim3(512), 0, s, p);      \
+        else hipLaunchKernelGGL((conv3x3_ws_kernel<DT, false>), dim3(grid), dim3(512), 0, s, p);                   \
     } while (0)
-    const int mode = (a.out ? 1 : 0) | (out_pool ? 2 : 0);
-    if (mode == 3) return TDRN_E_UNSUPPORTED;            // (both outputs at once: no plan asks for it; conv3x3_patch.hip takes such a launch)
-    // Full-resolution outputs (conv2_1) are eight 1-KiB stores per tile and consumer wave, ~150 cycles of the wave's time each, against two
-    // for a pooled tile: measured in the net 127-128 us against 123-126 us on conv3x3_patch.hip (whose two consumer waves per SIMD hide each
-    // other's stores) -- so this kernel takes such a layer only when asked to (TDRN_CONV_WS=2, the dev harness).  Same bits either way.
-    {
-        static int e = -1;
-        if (e < 0) { const char *v = getenv("TDRN_CONV_WS"); e = v ? atoi(v) : 1; }
-        if (mode == 1 && g_ws_override != 2 && e < 2) return TDRN_E_UNSUPPORTED;
-    }
     if (a.dtype == TDRN_BF16) WS_LAUNCH(bf16_t);
     else WS_LAUNCH(f16_t);
 #undef WS_LAUNCH

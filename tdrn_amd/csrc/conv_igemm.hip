@@ -441,12 +441,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_kernel(const ConvPa
     igemm_tile<DT, BM, BN, WGM, WGN, STAGES>(p, wg, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.z, smem);
 }
 
-int conv_patch_enabled()
-{
-    static int use_patch = -1;
-    if (use_patch < 0) { const char *e = getenv("TDRN_CONV_PATCH"); use_patch = e ? atoi(e) : 1; }
-    return use_patch;
-}
+// (chosen by layer geometry only, never by batch size: a frame's result must not depend on what else is in the batch)
+constexpr int kPatchMinPixels = 400;            // smaller maps (the 10x10 / 5x5 pyramid levels) stay on the implicit GEMM
+int patch_conv_takes(const ConvArgs &a) { return patch_conv_supported(a) && a.H * a.W >= kPatchMinPixels; }
 
 int conv_n_pad(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)align_up((size_t)cout, 128)); }
 
@@ -461,18 +458,12 @@ static int launch_cfg(const ConvParams &p, int phases, hipStream_t s)
     return hip_status(hipGetLastError());
 }
 
-static int g_conv_variant = -1;   // TDRN_CONV_VARIANT: 0 = always the 2-stage kernels (A/B switch)
-
 template <typename DT> static int launch_dt(const ConvParams &p, int phases, hipStream_t s)
 {
-    if (g_conv_variant < 0) {
-        const char *e = getenv("TDRN_CONV_VARIANT");
-        g_conv_variant = e ? atoi(e) : 1;
-    }
     // the deep-pipelined 256x128 kernel runs one workgroup per CU: use it when the grid still has
     // at least ~2 waves of workgroups over the 256 CUs
     const long long big_tiles = (long long)cdiv(p.M, 256) * (p.Npad / 128) * phases;
-    if (g_conv_variant >= 1 && p.Npad % 128 == 0 && big_tiles >= 512) return launch_cfg<DT, 256, 128, 4, 2, 3>(p, phases, s);
+    if (p.Npad % 128 == 0 && big_tiles >= 512) return launch_cfg<DT, 256, 128, 4, 2, 3>(p, phases, s);
     if (p.Npad % 128 == 0) return launch_cfg<DT, 128, 128, 2, 2, 2>(p, phases, s);
     if (p.Npad % 64 == 0) return launch_cfg<DT, 128, 64, 2, 2, 2>(p, phases, s);
     return launch_cfg<DT, 128, 32, 4, 1, 2>(p, phases, s);
@@ -553,14 +544,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p, 
 // number of K slices for a small-M problem: fill the chip (~2 workgroups per CU) but keep >= 4 K-steps each
 int conv_splitk_choice(const ConvArgs &a)
 {
-    static int enabled = -1;
-    if (enabled < 0) { const char *e = getenv("TDRN_SPLITK"); enabled = e ? atoi(e) : 1; }
-    if (!enabled) return 1;
     const int es = dtype_bytes(a.dtype);
     const int nk = a.kh * a.kw * (a.Cin / (128 / es));
     const int bn = a.Npad % 128 == 0 ? 128 : (a.Npad % 64 == 0 ? 64 : 32);
     const long long blocks = (long long)cdiv(a.B * a.Ho * a.Wo, 128) * (a.Npad / bn) * a.phases;
-    if (conv_patch_enabled() && patch_conv_supported(a) && a.H * a.W >= conv_patch_enabled() * 400) return 1;
+    if (patch_conv_takes(a)) return 1;
     if (head3x3_supported(a)) return 1;                  // (head3x3.hip takes the launch whole)
     if (blocks >= 160 || nk < 8) return 1;
     int s = (int)((384 + blocks - 1) / blocks);
@@ -601,11 +589,7 @@ static int make_params(const ConvArgs &a, ConvParams &p)
                     a.o_bs == (long long)a.Ho * a.Wo * a.o_cs) ? 1 : 0;
     p.n_tiles = 0;
     p.B = a.B;
-    {
-        static int bm = -1;                  // TDRN_IGEMM_BATCH_MINOR=0: keep the image-major row order (A/B switch)
-        if (bm < 0) { const char *e = getenv("TDRN_IGEMM_BATCH_MINOR"); bm = e ? atoi(e) : 1; }
-        p.batch_minor = (bm && a.pad > 0 && a.phases == 1 && a.B > 1 && a.Ho * a.Wo <= 1600 && a.kh * a.kw <= 32) ? 1 : 0;
-    }
+    p.batch_minor = (a.pad > 0 && a.phases == 1 && a.B > 1 && a.Ho * a.Wo <= 1600 && a.kh * a.kw <= 32) ? 1 : 0;
     p.splits = (a.splitk > 1 && a.partial) ? a.splitk : 1;
     p.partial = (float *)a.partial;
     static int ablate = -1;
@@ -619,12 +603,8 @@ int launch_conv(const ConvArgs &a, hipStream_t s)
     ConvParams p;
     TDRN_TRY(make_params(a, p));
     if (p.M <= 0) return TDRN_OK;
-    // 3x3/s1/p1 layers with enough tiles go to the warp-specialised patch kernel (TDRN_CONV_PATCH=0: off)
-    static int use_patch = -1;
-    if (use_patch < 0) { const char *e = getenv("TDRN_CONV_PATCH"); use_patch = e ? atoi(e) : 1; }
-    // (chosen by layer geometry only, never by batch size: a frame's result must not depend on
-    // what else is in the batch)
-    if (p.splits == 1 && use_patch && patch_conv_supported(a) && a.H * a.W >= use_patch * 400)
+    // 3x3/s1/p1 layers with enough tiles go to the warp-specialised patch kernel (TDRN_PLAN_NO_CONV_PATCH: off)
+    if (p.splits == 1 && patch_conv_takes(a))
         return launch_conv3x3_patch(a, nullptr, s);
     if (a.fuse_x) return TDRN_E_UNSUPPORTED;             // only the patch kernel computes the first conv itself
     if (p.splits == 1 && head3x3_supported(a)) return launch_head3x3(a, s);      // the narrow fp32 heads (ARM loc)
@@ -663,7 +643,7 @@ int launch_conv(const ConvArgs &a, hipStream_t s)
 // (persistent convs of other stream lanes may hold most CUs).  Independent stages (the lateral of the 10x10 level beside the
 // 5x5 chain) overlap by themselves.
 //
-// MEASURED, AND NOT THE DEFAULT PLAN (opt-in: TDRN_PLAN_CHAIN / TDRN_CHAIN=1).  Nine layers, ~3200 tasks at batch 32, bit-identical
+// MEASURED, AND NOT THE DEFAULT PLAN (opt-in: TDRN_PLAN_CHAIN).  Nine layers, ~3200 tasks at batch 32, bit-identical
 // to the nine launches (tested): 664 us alone / 717 us in the step with coherent (`sc1`) accesses for everything a task hands
 // to another, 806 us with plain accesses + one agent-scope release and acquire per task (which also slowed every concurrent
 // kernel 3-5x: each release writes an XCD's L2 back) -- against 170 us alone / 270 us in the step for the launches it
@@ -778,7 +758,7 @@ int conv_chain_max_layers() { return kChainMax; }
 int conv_chain_supported(const ConvArgs &a)
 {
     if (a.out_f32 || a.fuse_x || a.Npad % 128 != 0) return 0;
-    if (a.splitk == 1 && conv_patch_enabled() && patch_conv_supported(a) && a.H * a.W >= conv_patch_enabled() * 400) return 0;   // the patch kernels' layer
+    if (a.splitk == 1 && patch_conv_takes(a)) return 0;   // the patch kernels' layer
     return 1;
 }
 

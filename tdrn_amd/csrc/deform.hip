@@ -42,7 +42,6 @@ struct DeformMulti {
     DeformParams p[kMaxDeformProblems];
     int block_start[kMaxDeformProblems + 1];
     int n;
-    int xcd_order;    // 1: the grid is 8 * ceil(tiles / 8) workgroups and workgroup b works on tile (b % 8) * ceil(tiles / 8) + b / 8 (see the kernel)
 };
 
 template <typename DT> struct MmaD;
@@ -67,14 +66,12 @@ template <> struct MmaD<float> {
 template <typename DT, int NTL>
 __global__ __launch_bounds__(256) void deform_gemm_kernel(const DeformMulti mp)
 {
-    // XCD-aware tile order: workgroup b runs on XCD b % 8; with `xcd_order` every XCD works on a CONTIGUOUS run of pixel tiles, so the
-    // rows that neighbouring tiles gather (the taps reach +-1..2 rows plus the offsets) come through one L2 instead of eight
-    int bid = (int)blockIdx.x;
-    if (mp.xcd_order) {
-        const int total = mp.block_start[mp.n], per = (total + 7) >> 3;
-        bid = (bid & 7) * per + (bid >> 3);
-        if (bid >= total) return;                       // (whole workgroup; the grid is rounded up to 8 * per)
-    }
+    // XCD-aware tile order: workgroup b runs on XCD b % 8; the grid is 8 * ceil(tiles / 8) workgroups and workgroup b works on tile
+    // (b % 8) * ceil(tiles / 8) + b / 8, so every XCD works on a CONTIGUOUS run of pixel tiles and the rows that neighbouring tiles
+    // gather (the taps reach +-1..2 rows plus the offsets) come through one L2 instead of eight
+    const int total = mp.block_start[mp.n], per = (total + 7) >> 3;
+    const int bid = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
+    if (bid >= total) return;                           // (whole workgroup; the grid is rounded up to 8 * per)
     int prob = 0;
 #pragma unroll
     for (int i = 1; i < kMaxDeformProblems; ++i)
@@ -308,7 +305,7 @@ int deform_n_pad(int cout) { return (int)align_up((size_t)cout, 32); }
 
 template <typename DT> static int launch_deform_dt(const DeformMulti &mp, int ntl, hipStream_t s)
 {
-    dim3 grid((unsigned)(mp.xcd_order ? 8 * ((mp.block_start[mp.n] + 7) / 8) : mp.block_start[mp.n]));
+    dim3 grid((unsigned)(8 * ((mp.block_start[mp.n] + 7) / 8)));
     switch (ntl) {
         case 1: hipLaunchKernelGGL((deform_gemm_kernel<DT, 1>), grid, dim3(256), 0, s, mp); break;
         case 2: hipLaunchKernelGGL((deform_gemm_kernel<DT, 2>), grid, dim3(256), 0, s, mp); break;
@@ -393,9 +390,6 @@ int launch_deform_multi(const DeformArgs *args, int n, hipStream_t s, int split_
     }
     if (mp.n == 0) return TDRN_OK;
     for (int i = mp.n; i < kMaxDeformProblems; ++i) { mp.p[i] = mp.p[0]; mp.block_start[i + 1] = mp.block_start[mp.n]; }
-    static int xo = -1;
-    if (xo < 0) { const char *e = getenv("TDRN_DEFORM_XCD"); xo = e ? atoi(e) : 1; }
-    mp.xcd_order = xo;
     switch (args[0].dtype) {
         case TDRN_F32: return launch_deform_dt<float>(mp, args[0].Npad / 32, s);
         case TDRN_BF16: return launch_deform_dt<bf16_t>(mp, args[0].Npad / 32, s);
@@ -439,7 +433,6 @@ struct SampleMulti {
     SampleParams p[4];
     int block_start[5];
     int n;
-    int xcd_remap;
 };
 constexpr int kSampleCols = 80;    // Y columns per tap (75 used)
 
@@ -450,7 +443,7 @@ __global__ __launch_bounds__(256) void deform_sample_kernel(const SampleMulti mp
     // 4 per block), so that the Y rows shared by neighbouring pixels -- the x+1 / y+1 corners, the overlapping taps -- are fetched
     // into ONE L2 instead of up to eight.
     const int nblk = (int)gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = (int)blockIdx.x & 7;
-    const int blk = mp.xcd_remap ? (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+    const int blk = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + ((int)blockIdx.x >> 3);
     int prob = 0;
 #pragma unroll
     for (int i = 1; i < 4; ++i)
@@ -563,11 +556,9 @@ struct YGemmParams {
     int M, N, ycs, parts, tiles_per_part, taps;
 };
 
-// CT = column tiles (of 32) per wave.  CT = 1: eight waves x 32 columns (round 3, the default).  CT = 2 (round 4, TDRN_YGEMM_CT=2): FOUR waves x 64
-// columns -- 128 weight registers per wave, two workgroups of four waves per CU: every wave still reads the whole 16-KiB pixel tile
-// from LDS per tile, but there are half as many waves doing it for the same 256 columns, so the LDS reads per output halve (CT = 1:
-// 128 KiB of LDS reads per tile = 1024 cycles beside 1024 cycles of MFMA per SIMD: the two pipes were co-critical).  Same K order
-// per output element: bit-identical.
+// Eight waves x 32 columns.  (Four waves x 64 columns -- half the LDS reads per output: 128 KiB of LDS reads per tile = 1024 cycles
+// beside 1024 cycles of MFMA per SIMD, the two pipes co-critical -- measured 337-344 us against 332-334 us for the pair of deform
+// launches (round 4, interleaved): the transform is not bound by its LDS reads.)
 // up to four independent problems (the pyramid levels) in ONE launch: the transforms of the small levels fill the tail of the
 // large one, and three kernel boundaries (~7 us each in the step, round 4 trace) disappear from the critical path
 struct YGemmMulti {
@@ -588,8 +579,8 @@ struct YGemmMulti {
 #define YG_STAMP_FLUSH do { } while (0)
 #endif
 
-template <typename DT, int CT>
-__global__ __launch_bounds__(CT == 1 ? 512 : 256, CT == 1 ? 4 : 2) void ygemm_k256_kernel(const YGemmMulti mp)
+template <typename DT>
+__global__ __launch_bounds__(512, 4) void ygemm_k256_kernel(const YGemmMulti mp)
 {
     int prob = 0;
 #pragma unroll
@@ -598,7 +589,7 @@ __global__ __launch_bounds__(CT == 1 ? 512 : 256, CT == 1 ? 4 : 2) void ygemm_k2
     const YGemmParams &p = mp.p[prob];
     const int local_blk = (int)blockIdx.x - mp.block_start[prob];
     const int ncg = p.N / 256;
-    constexpr int NW = 8 / CT;                           // waves per workgroup
+    constexpr int NW = 8;                                // waves per workgroup
     constexpr int NT = NW * 64;
     constexpr int TP = 32;                               // pixels per tile
     constexpr int TBYTES = TP * 512;                     // 16 KiB
@@ -609,14 +600,13 @@ __global__ __launch_bounds__(CT == 1 ? 512 : 256, CT == 1 ? 4 : 2) void ygemm_k2
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
     const int part = local_blk / ncg, cg = local_blk - part * ncg;
-    const int col0 = cg * 256 + wave * (32 * CT);
-    // my 32 CT columns x 256 channels: fragment [ct][kk] = channels [16kk + 8hh, +8) of column col0 + 32 ct + r32
-    u32x4 wf[CT][16];
+    const int col0 = cg * 256 + wave * 32;
+    // my 32 columns x 256 channels: fragment kk = channels [16kk + 8hh, +8) of column col0 + r32
+    u32x4 wf[16];
+    {
+        const char *wr = p.w + ((size_t)(col0 + r32) * 256 + 8 * hh) * 2;
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const char *wr = p.w + ((size_t)(col0 + 32 * ct + r32) * 256 + 8 * hh) * 2;
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) wf[ct][kk] = *(const u32x4 *)(wr + kk * 32);
+        for (int kk = 0; kk < 16; ++kk) wf[kk] = *(const u32x4 *)(wr + kk * 32);
     }
     const int t0 = part * p.tiles_per_part;
     int nt = (p.M + TP - 1) / TP - t0;
@@ -681,29 +671,25 @@ __global__ __launch_bounds__(CT == 1 ? 512 : 256, CT == 1 ? 4 : 2) void ygemm_k2
         __builtin_amdgcn_s_barrier();                    // (raw: __syncthreads() would drain the piece just issued)
         asm volatile("" ::: "memory");
         YG_STAMP(2);                                     // barrier
-        f32x16 acc[CT];
+        f32x16 acc;
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[ct][e] = 0.f;
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
         const char *ab = smem + buf * TBYTES + r32 * 512;
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             const u32x4 a = *(const u32x4 *)(ab + (((2 * kk + hh) ^ r32) << 4));
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) MmaD<DT>::run(wf[ct][kk], a, acc[ct]);
+            MmaD<DT>::run(wf[kk], a, acc);
         }
         // lane = pixel r32; register e = column (e & 3) + 8 (e >> 2) + 4 hh of a 32-column tile.  The tile goes through an LDS image
         // [pixel][256 columns] so that the stores are whole 128-byte lines (512 B per pixel row, 16 B per lane): written as
         // 8-byte pieces straight from the registers, a line of Y was assembled from eight partial writes (222 -> 167 us for
         // the four levels).  The staging stores are inline asm: in front of an LDS store it can see, hipcc drains every LDS-DMA
         // piece in flight with a vmcnt(0).
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const unsigned sa = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)sst + (unsigned)(r32 * SROW + (wave * 32 * CT + 32 * ct + 4 * hh) * 2);
+        {
+            const unsigned sa = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)sst + (unsigned)(r32 * SROW + (wave * 32 + 4 * hh) * 2);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const uint2 v = make_uint2(pack2<DT>(acc[ct][4 * g], acc[ct][4 * g + 1]), pack2<DT>(acc[ct][4 * g + 2], acc[ct][4 * g + 3]));
+                const uint2 v = make_uint2(pack2<DT>(acc[4 * g], acc[4 * g + 1]), pack2<DT>(acc[4 * g + 2], acc[4 * g + 3]));
                 asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(sa), "v"(v), "n"(16 * g) : "memory");
             }
         }
@@ -988,23 +974,14 @@ int launch_ygemm_multi(const YGemmProblem *pr, int n, int dtype, hipStream_t s, 
         }
     } report{s, nst, stamps, mp, &calls};
 #endif
-    static int ct = -1;
-    // CT = 2 (four waves x 64 columns: half the LDS reads per output) measured 337-344 us against 332-334 us for the pair of deform
-    // launches (round 4, interleaved): the transform is not bound by its LDS reads; the round-3 shape stays the default
-    if (ct < 0) { const char *e = getenv("TDRN_YGEMM_CT"); ct = e ? atoi(e) : 1; }
-    static int v2 = -1;
-    if (v2 < 0) { const char *e = getenv("TDRN_YGEMM_V2"); v2 = e ? atoi(e) : 1; }
     bool tapmajor = true;
     for (int i = 0; i < mp.n; ++i) tapmajor = tapmajor && mp.p[i].taps > 0;
-    if (v2 && !(kdisable & 128) && tapmajor && ct == 1) {
+    if (!(kdisable & 128) && tapmajor) {
         if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_v2_kernel<bf16_t>), grid, dim3(512), 0, s, mp);
         else hipLaunchKernelGGL((ygemm_k256_v2_kernel<f16_t>), grid, dim3(512), 0, s, mp);
-    } else if (ct == 1) {
-        if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_kernel<bf16_t, 1>), grid, dim3(512), 0, s, mp);
-        else hipLaunchKernelGGL((ygemm_k256_kernel<f16_t, 1>), grid, dim3(512), 0, s, mp);
     } else {
-        if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_kernel<bf16_t, 2>), grid, dim3(256), 0, s, mp);
-        else hipLaunchKernelGGL((ygemm_k256_kernel<f16_t, 2>), grid, dim3(256), 0, s, mp);
+        if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_kernel<bf16_t>), grid, dim3(512), 0, s, mp);
+        else hipLaunchKernelGGL((ygemm_k256_kernel<f16_t>), grid, dim3(512), 0, s, mp);
     }
     return hip_status(hipGetLastError());
 }
@@ -1072,11 +1049,6 @@ int launch_deform_sample_multi(const DeformArgs *args, const void *const *y, con
     }
     if (mp.n == 0) return TDRN_OK;
     for (int i = mp.n; i < 4; ++i) { mp.p[i] = mp.p[0]; mp.block_start[i + 1] = mp.block_start[mp.n]; }
-    {
-        static int remap = -1;
-        if (remap < 0) { const char *e = getenv("TDRN_SAMPLE_XCD"); remap = e ? atoi(e) : 1; }
-        mp.xcd_remap = remap;
-    }
     dim3 grid((unsigned)mp.block_start[mp.n]);
     if (args[0].dtype == TDRN_BF16) hipLaunchKernelGGL((deform_sample_kernel<bf16_t>), grid, dim3(256), 0, s, mp);
     else hipLaunchKernelGGL((deform_sample_kernel<f16_t>), grid, dim3(256), 0, s, mp);

@@ -477,8 +477,6 @@ struct Pw1x1Params {
     int M, Cin, Cout, Cs, relu;
     int m_tiles, n_tiles, items;
     int ablate;                    // diagnostics (TDRN_PW_ABLATE): 1 no pixel DMA, 2 no weight DMA, 4 no LDS reads / MFMA, 8 no stores
-    int n_major;                   // item = nt * m_tiles + mt instead of mt * n_tiles + nt (see the kernel)
-    int stagger;                   // group 1 issues a unit's LDS-DMA pieces BETWEEN its two MFMA halves, group 0 in front of them (TDRN_PW_STAGGER=0: both in front)
     int tail_split;                // an XCD's last, sparsely filled round of items runs as 64- or 128-cout sub-items (see the kernel)
 };
 
@@ -529,7 +527,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
     // config 4, 256 -> 512, ...).  When the XCD's last round is at most a quarter (half) filled, its items are cut ALONG THE COUTS into
     // four 64-cout (two 128-cout) sub-items, one per workgroup: the same eight waves with one (two) 32-cout accumulator tiles each, a
     // quarter (half) of the weight rows, bias and stores, the same pixel rows.  Every output element sees the same MFMA rows in the same
-    // K order: bit-identical whatever the batch does to the cut (TDRN_PLAN_NO_PATCH_TAIL / TDRN_PATCH_TAIL=0 keep whole items).
+    // K order: bit-identical whatever the batch does to the cut (TDRN_PLAN_NO_PATCH_TAIL keeps whole items).
     int n_tail = 0, tail_item = 0, tail_c0 = 0, tail_wcn = WC;
     if (p.tail_split && avail > 0) {
         const int full = avail / istride, rem = avail - full * istride;
@@ -551,12 +549,12 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
     auto seq_c0 = [&](int i) -> int { return i < n_full ? 0 : tail_c0; };
     auto seq_wcn = [&](int i) -> int { return i < n_full ? WC : tail_wcn; };
     const unsigned smem_lds = __builtin_amdgcn_readfirstlane(dp_lds_addr(smem));
-    // item numbering: pixel-tile major by default -- the cout tiles of one pixel tile are neighbouring items of ONE XCD, dealt to
+    // item numbering: pixel-tile major -- the cout tiles of one pixel tile are neighbouring items of ONE XCD, dealt to
     // neighbouring workgroups at the same time, so the pixel rows (the operand that streams from HBM) cross the fabric once; the
     // whole weight matrix (<= 2 MB) stays in every XCD's L2.  (cout-tile major, conv3x3_pp.hip's choice for its 9x bigger weight
     // matrices, fetched the activations once per cout tile: 185 MB for a 105-MB tensor, profiles/r04_cfg4.)
-    auto mt_of = [&](int item) -> int { return p.n_major ? item % p.m_tiles : item / p.n_tiles; };
-    auto nt_of = [&](int item) -> int { return p.n_major ? item / p.m_tiles : item % p.n_tiles; };
+    auto mt_of = [&](int item) -> int { return item / p.n_tiles; };
+    auto nt_of = [&](int item) -> int { return item % p.n_tiles; };
 
     // one chunk of an operand: wave w stages pixel rows [8(w + 8k), +8) / its group's weight rows, k = 0..3 (4 pieces each);
     // rows past M re-read the last row (their outputs are never stored)
@@ -732,7 +730,10 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
         if (u + 1 < n_units) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         DP_BAR();                                       // ... everybody's; and every wave has left the MFMAs of unit u-1
-        const bool late = p.stagger && grp == 1;        // (wave-uniform: group 1 issues its pieces between its two MFMA halves)
+        // (round 6: wave group 1 issues a unit's eight LDS-DMA pieces between its two MFMA halves, group 0 in front of them, so the two
+        // waves of a SIMD no longer issue and multiply in lockstep: -2 % on the 8-chunk layers, -9...-10 % on the 16-chunk ones (512 ->
+        // 1024, 1024 -> 1024 at 20 x 20); same arithmetic, same bits.  Round 4 had moved only the pixel pieces behind ALL the MFMAs: nothing.)
+        const bool late = grp == 1;                     // (wave-uniform)
         if (!late) {
             if (u + 1 < n_units) stage_w(q1.item, q1.c, wbuf ^ 1);
             if (u + 2 < n_units) stage_a(q2.item, q2.c, abuf == 0 ? 2 : abuf - 1);     // (= the buffer of unit u-1)
@@ -774,17 +775,10 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
 }
 
 // ---------------------------------------------------------------------------------------------
-int dwpw_enabled()
-{
-    static int e = -1;
-    if (e < 0) { const char *s = getenv("TDRN_DWPW"); e = s ? atoi(s) : 1; }      // 0: never; 1: where the plan asks (TDRN_PLAN_DWPW); 2: every plan
-    return e;
-}
-
 // 0 = no; else the tile mode (32 / 16 = 2-D tiles, -1 = flat tiles)
 int dwpw_supported(const DwPwArgs &a)
 {
-    if (!dwpw_enabled() || a.dtype == TDRN_F32) return 0;
+    if (a.dtype == TDRN_F32) return 0;
     if (a.stride != 1 || a.Cin % 64 || a.Cin < 64 || a.Npad % 256 || a.Cout > a.Npad || a.Cs < a.Cout) return 0;
     if ((long long)a.B * a.H * a.W * a.Cin * 2 >= (1ll << 32)) return 0;       // 32-bit byte offsets into the input
     if ((long long)a.Npad * a.Cin * 2 >= (1ll << 31)) return 0;
@@ -833,18 +827,11 @@ int launch_dwpw(const DwPwArgs &a, hipStream_t s)
 }
 
 
-int pw1x1_enabled()
-{
-    static int e = -1;
-    if (e < 0) { const char *s = getenv("TDRN_PW1X1"); e = s ? atoi(s) : 1; }
-    return e;
-}
-
 // the 1x1 / stride 1 / unpadded convs this kernel takes over from conv_igemm.hip: 16-bit, whole 64-channel chunks, couts in whole
 // 256-groups, a plain NHWC output tensor, no residual, no split-K, and enough items to fill the chip
 int pw1x1_supported(const ConvArgs &a)
 {
-    if (!pw1x1_enabled() || (a.kdisable & 8) || a.dtype == TDRN_F32) return 0;
+    if ((a.kdisable & 8) || a.dtype == TDRN_F32) return 0;
     if (a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0 || a.phases != 1 || a.res || a.out_f32 || a.splitk > 1 || a.fuse_x) return 0;
     if (a.Ho != a.H || a.Wo != a.W || a.Cin % 64 || a.Npad % 256 || a.Cout > a.Npad) return 0;
     if (a.o_rs != (long long)a.Wo * a.o_cs || a.o_bs != (long long)a.Ho * a.Wo * a.o_cs || a.o_base) return 0;
@@ -867,18 +854,7 @@ int launch_pw1x1(const ConvArgs &a, hipStream_t s)
     static int ablate = -1;
     if (ablate < 0) ablate = dev_ablate_env("TDRN_PW_ABLATE");     // (developer builds only: common.h)
     p.ablate = ablate;
-    static int nmajor = -1;
-    if (nmajor < 0) { const char *e = getenv("TDRN_PW_NMAJOR"); nmajor = e ? atoi(e) : 0; }
-    p.n_major = nmajor;
-    static int stag = -1;
-    // (round 6, default on: wave group 1 issues a unit's eight LDS-DMA pieces between its two MFMA halves, group 0 in front of them, so
-    // the two waves of a SIMD no longer issue and multiply in lockstep: -2 % on the 8-chunk layers, -9...-10 % on the 16-chunk ones
-    // (512 -> 1024, 1024 -> 1024 at 20 x 20); same arithmetic, same bits.  Round 4 had moved only the pixel pieces behind ALL the MFMAs: nothing.)
-    if (stag < 0) { const char *e = getenv("TDRN_PW_STAGGER"); stag = e ? atoi(e) : 1; }
-    p.stagger = stag;
-    static int tail = -1;
-    if (tail < 0) { const char *e = getenv("TDRN_PATCH_TAIL"); tail = e ? atoi(e) : 1; }
-    p.tail_split = tail && !(a.kdisable & 1024);     // (TDRN_PLAN_NO_PATCH_TAIL; pixel-tile-major items only: the sub-items of a tile are neighbours)
+    p.tail_split = !(a.kdisable & 1024);             // (TDRN_PLAN_NO_PATCH_TAIL)
     const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
     if (a.dtype == TDRN_BF16) hipLaunchKernelGGL((pw1x1_kernel<bf16_t>), dim3(grid), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((pw1x1_kernel<f16_t>), dim3(grid), dim3(512), 0, s, p);

@@ -42,7 +42,6 @@ struct ConvArgs {
     // ... or the frames as uint8 planes (B, 3, S, S) with the per-plane mean still to be subtracted (conv3x3_ws.hip only: tdrn_net_io.reserved[3])
     const unsigned char *fuse_x8 = nullptr;
     float fuse_mean[3] = {0.f, 0.f, 0.f};
-    int max_wgs = 0;                // patch kernel: > 0 caps the persistent grid (a multiple of 8), leaving CUs to concurrent lanes
     void *sk_ws = nullptr;          // conv3x3_pp.hip: scratch of conv_pp_sk_bytes() for the chained split (one launch at a time), or null
     bool sk_flags_zero = false;     // the first 1024 bytes of sk_ws are zero on entry (every launch leaves them zero): no memset node
     // kernel-choice switches of this launch (tdrn_net_config.plan_flags TDRN_PLAN_NO_CONV_PP / _NO_PP_SK / _NO_CONV_PATCH):
@@ -69,24 +68,20 @@ size_t conv_splitk_bytes(const ConvArgs &a, int splits);
 int head3x3_supported(const ConvArgs &a);
 int launch_head3x3(const ConvArgs &a, hipStream_t s);
 // warp-specialised 3x3/s1/p1 kernel (conv3x3_patch.hip); out_pool = optional fused MaxPool2d(2,2) output
-int conv_patch_enabled();                       // TDRN_CONV_PATCH (default 1)
 int patch_conv_supported(const ConvArgs &a);   // 0 = no, 32/16 = 2-D tiles, -1 = flat tiles
+int patch_conv_takes(const ConvArgs &a);       // launch_conv hands this (unsplit) layer to launch_conv3x3_patch (conv_igemm.hip)
 int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s);
 // all-waves-compute ("ping-pong") 3x3/s1/p1 kernel for the 16-bit Cin >= 128, Cout % 256 == 0 layers (conv3x3_pp.hip);
-// launch_conv3x3_patch hands those layers over to it (TDRN_CONV_PP=0 keeps the loader/consumer kernel)
+// launch_conv3x3_patch hands those layers over to it when their output is not pooled (kdisable bit 0 keeps the loader/consumer kernel)
 int pp_conv_supported(const ConvArgs &a);      // 0 = no, else the tile mode of patch_conv_supported
-int launch_conv3x3_pp(const ConvArgs &a, void *out_pool, hipStream_t s);
-void conv_pp_force(int v);                      // dev harness: -1 = environment, 0 / 1 = forced
-void conv_pp_sk_force(int v);                   // dev harness: the chained split ("stream-K") of conv3x3_pp.hip on / off
-int conv_pp_sk_enabled();                       // TDRN_CONV_PP_SK (default 1)
+int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s);
 size_t conv_pp_sk_bytes();
 // weight-stationary 3x3/s1/p1 kernel for the 16-bit Cin == 64 layers (conv3x3_ws.hip: the whole weight tile resident in LDS, the
 // activations in a ring of image rows, the first conv optionally computed by its producer waves); launch_conv3x3_patch hands those
-// layers over to it when their output is POOLED -- by default that is conv1_2 alone; a full-resolution output (conv2_1) is declined
-// unless TDRN_CONV_WS=2 (it measured slower there) -- and TDRN_CONV_WS=0 / kdisable bit 6 keep the loader/consumer kernel.  Same output bits.
+// layers over to it when their output is POOLED (conv1_2; a full-resolution output stays on the loader/consumer kernel, as does
+// everything under kdisable bit 6).  Same output bits.
 int ws_conv_supported(const ConvArgs &a);
-int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s);
-void conv_ws_force(int v);                      // dev harness: -1 = environment, 0 / 1 = forced
+int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s);   // out_pool only (a.out null)
 // rows of the packed weight matrix must be padded to a multiple of this
 int conv_n_pad(int cout);
 // channels of every NHWC activation tensor are padded to a multiple of this
@@ -118,10 +113,9 @@ struct DwPwArgs {
     int B = 0, H = 0, W = 0, Cin = 0, Cout = 0, Npad = 0, Cs = 0;  // Cs: channel stride of the output tensor
     int stride = 1, relu_dw = 1, relu = 1, dtype = TDRN_BF16;
 };
-int dwpw_enabled();                              // TDRN_DWPW (default 1)
 int dwpw_supported(const DwPwArgs &a);           // 0 = no, else the tile mode
 int launch_dwpw(const DwPwArgs &a, hipStream_t s);
-// wide 1x1 convs as a persistent 256 x 256-item GEMM (dwpw.hip pw1x1_kernel); launch_conv hands them over (TDRN_PW1X1=0 / kdisable bit 3: off)
+// wide 1x1 convs as a persistent 256 x 256-item GEMM (dwpw.hip pw1x1_kernel); launch_conv hands them over (kdisable bit 3: off)
 int pw1x1_supported(const ConvArgs &a);
 int launch_pw1x1(const ConvArgs &a, hipStream_t s);
 // softmax over rows of (R, C) fp32, in place allowed

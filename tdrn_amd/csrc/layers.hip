@@ -258,9 +258,7 @@ int launch_first_conv(const float *x, const float *w, const float *bias, void *o
                       int Cout, int Cpad, int relu, int dtype, hipStream_t s)
 {
     const int So = (S + 2 - 3) / stride + 1;
-    static int use_mfma = -1;
-    if (use_mfma < 0) { const char *e = getenv("TDRN_FIRST_MFMA"); use_mfma = e ? atoi(e) : 1; }
-    if (use_mfma && Cpad == 64 && (stride == 1 || stride == 2)) {
+    if (Cpad == 64 && (stride == 1 || stride == 2)) {
         const int tiles_x = (So + 31) / 32, tiles_y = (So + 7) / 8;
         const long long n_tiles = (long long)B * tiles_x * tiles_y;
 #define LM(DT)                                                                                                              \
@@ -633,10 +631,7 @@ int launch_dwconv3(const void *in, const float *w, const float *bias, void *out,
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const int per16 = 16 / dtype_bytes(dtype);
     if (C % per16) return TDRN_E_UNSUPPORTED;
-    static int strip = -1, slide = -1;
-    if (strip < 0) { const char *e = getenv("TDRN_DW_STRIP"); strip = e ? atoi(e) : 1; }
-    if (slide < 0) { const char *e = getenv("TDRN_DW_SLIDE"); slide = e ? atoi(e) : 1; }
-    if (slide && !(kdisable & 16) && strip && (stride == 1 || stride == 2) && Wo >= 4) {
+    if (!(kdisable & 16) && (stride == 1 || stride == 2) && Wo >= 4) {
         // strips of 4 outputs at stride 1, of 2 at stride 2 (9 input columns per row do not fit the registers of two waves per
         // SIMD there).  Segment height: the tallest of 8 / 4 / 2 rows that still leaves >= 768 workgroups (3 per CU); below
         // that the strip kernel (one row per thread).  Measured on dualrefinedet_mobilenet 320 x 64 (profiles/r04_experiments.md):
@@ -646,7 +641,6 @@ int launch_dwconv3(const void *in, const float *w, const float *bias, void *out,
         int th = 0;
         for (int t = 8; t >= 2 && !th; t >>= 1)
             if (per_row * ((Ho + t - 1) / t) >= 768ll * 256) th = t;
-        if (slide > 1) th = slide;                          // (experiments: a forced segment height)
         if (kdisable & 32) th = 8;                          // (TDRN_PLAN_DW_SLIDE_ALL)
         if (th) {
             const int nseg = (Ho + th - 1) / th;
@@ -661,7 +655,7 @@ int launch_dwconv3(const void *in, const float *w, const float *bias, void *out,
             return hip_status(hipGetLastError());
         }
     }
-    if (strip && (stride == 1 || stride == 2) && Wo >= 4) {
+    if ((stride == 1 || stride == 2) && Wo >= 4) {
         const long long total = (long long)B * Ho * ((Wo + 3) / 4) * (C / per16);
         dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
 #define LS(DT)                                                                                                                         \

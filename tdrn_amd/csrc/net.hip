@@ -167,17 +167,17 @@ struct tdrn_net {
     // Side-lane convs (TCB laterals, ARM heads, offset convs) are held back until conv5_3 has been computed: released on their
     // true inputs (L2Norm of conv4_3) they share the CUs with conv5_1..5_3 and stretch the trunk, the critical path, by
     // 0.24 ms; held back, they run beside conv6/conv7 and the small top-down layers instead (+1.4 % frames/s; held until fc7
-    // or capped to 128..224 workgroups: no further gain).  TDRN_LATE_SIDE 0: off, 2: until fc7; TDRN_SIDE_GRID: the cap.
-    int t_late = -1, t_late2 = -1;
+    // or capped to 128..224 workgroups: no further gain).  TDRN_PLAN_NO_LATE_SIDE: off.
+    int t_late = -1;
     std::vector<int> chain_ops;          // the chain launch's member ops in stage order (empty: no chain)
     size_t chain_partial_off = 0;        // the chain's split-K slab region (bytes per sample from workspace start)
     bool pp_sk_planned = false;          // some main-lane conv may use conv3x3_pp.hip's chained split
     int fuse_first = -1;                 // index of the conv whose patch loader computes the first conv itself (16-bit modes), or -1
     int x_t = -1;                        // fp32 (3, S, S) workspace tensor: the net input when the caller hands uint8 planes to a plan whose first conv reads fp32
-    int late_side = 1, side_grid = 0, main_grid = 0;
-    bool use_lanes = true, lanes_ready = false, deform_split = true;
+    bool late_side = true;
+    bool use_lanes = true, lanes_ready = false;
+    bool y_tap_major = true;            // Y of the transform-then-sample heads is tap-major (every level's transform runs on ygemm_k256)
     int plan_error = TDRN_OK;
-    int splitk_ref_batch = 32;          // split-K factors are planned for this batch (the benchmark's) and used for every batch (TDRN_SPLITK_REF)
     const void *offs_ws = nullptr;      // ssd4scale deform: the workspace / batch whose offset tensors the last forward filled
     int offs_batch = 0, offs_key_batch = 0;
     int dev = -1;                       // the device the pooled handles below belong to (the one current at the first forward)
@@ -415,17 +415,13 @@ struct tdrn_net {
         o.flops = 2.0 * ti.H * ti.W * o.Cout * taps * ti.C;
         o.bytes = (double)ti.H * ti.W * (ti.Cpad * es + (o.Cout + 2 * taps * G) * 4);
         // 16-bit plans, one deformable group: transform (1x1 GEMM into per-tap partial outputs), then sample (deform.hip);
-        // TDRN_DEFORM_TS=0 keeps the fused gather kernel
-        {
-            const char *e = getenv("TDRN_DEFORM_TS");
-            const bool ts_on = e ? atoi(e) != 0 : !(cfg.plan_flags & TDRN_PLAN_NO_DEFORM_TS);
-            if (ts_on && cfg.dtype != TDRN_F32 && G == 1 && (int)taps <= 34) {
-                o.y_groups = (o.Cout + 79) / 80;
-                o.y_cols = deform_sample_cols((int)taps);
-                o.y_t = T(o.y_cols * o.y_groups, ti.H, ti.W);
-                o.wt_off = blob((size_t)o.y_groups * o.y_cols * o.Cin * es);
-                o.bt_off = blob((size_t)o.y_groups * o.y_cols * 4);
-            }
+        // TDRN_PLAN_NO_DEFORM_TS keeps the fused gather kernel
+        if (!(cfg.plan_flags & TDRN_PLAN_NO_DEFORM_TS) && cfg.dtype != TDRN_F32 && G == 1 && (int)taps <= 34) {
+            o.y_groups = (o.Cout + 79) / 80;
+            o.y_cols = deform_sample_cols((int)taps);
+            o.y_t = T(o.y_cols * o.y_groups, ti.H, ti.W);
+            o.wt_off = blob((size_t)o.y_groups * o.y_cols * o.Cin * es);
+            o.bt_off = blob((size_t)o.y_groups * o.y_cols * 4);
         }
         push(o);
     }
@@ -480,7 +476,6 @@ struct tdrn_net {
         x = conv(x, "backbone." + std::to_string(idx), true, bn ? "backbone." + std::to_string(idx + 1) : "", 1024, 3, 1, 6, 6, 1);
         idx += bn ? 3 : 2;
         fc7 = conv(x, "backbone." + std::to_string(idx), true, bn ? "backbone." + std::to_string(idx + 1) : "", c7, 1, 1, 0, 1, 1);
-        t_late2 = fc7;
     }
 
     // TCB / FPN (dualrefinedet_vggbn.py:30-34,97-114,166-178).  Returns the 4 ODM sources.
@@ -737,9 +732,8 @@ struct tdrn_net {
         // that read it can start while conv5 / fc6 / fc7 -- which leave CUs idle -- are still running, instead of
         // queueing behind fc7 on the main lane.
         {
-            const char *le = getenv("TDRN_L2_EARLY");
             int side = 1;
-            for (size_t i = 0; i < ops.size() && !(le && atoi(le) == 0); ++i) {
+            for (size_t i = 0; i < ops.size(); ++i) {
                 if (ops[i].kind != OP_L2NORM) continue;
                 size_t prod = i;
                 for (size_t j = 0; j < i; ++j)
@@ -753,12 +747,10 @@ struct tdrn_net {
             }
         }
         // first conv fused into the loader of the conv behind it (conv3x3_patch.hip FUSE): 16-bit modes, stride 1, 64 channels,
-        // 8x32 tiles, and nobody else reads the first conv's output (TDRN_FUSE_FIRST=0 keeps the two launches)
+        // 8x32 tiles, and nobody else reads the first conv's output (TDRN_PLAN_NO_FUSE_FIRST keeps the two launches)
         {
-            const char *fe = getenv("TDRN_FUSE_FIRST");
-            const bool fuse_on = fe ? atoi(fe) != 0 : !(cfg.plan_flags & TDRN_PLAN_NO_FUSE_FIRST);
             fuse_first = -1;
-            if (fuse_on && cfg.dtype != TDRN_F32 && conv_patch_enabled() && !(kdisable & 4) && ops.size() > 1 && ops[0].kind == OP_FIRST &&
+            if (!(cfg.plan_flags & TDRN_PLAN_NO_FUSE_FIRST) && cfg.dtype != TDRN_F32 && !(kdisable & 4) && ops.size() > 1 && ops[0].kind == OP_FIRST &&
                 ops[1].kind == OP_CONV && ops[0].stride == 1 && tensors[ops[0].out].Cpad == 64) {
                 const Op &c = ops[1];
                 const Tensor &ti = tensors[ops[0].out];
@@ -774,21 +766,18 @@ struct tdrn_net {
                 }
             }
         }
-        if (cfg.plan_flags & TDRN_PLAN_NO_LATE_SIDE) late_side = 0;
-        if (const char *e = getenv("TDRN_LATE_SIDE")) late_side = atoi(e);
-        if (const char *e = getenv("TDRN_SIDE_GRID")) side_grid = atoi(e);
-        if (const char *e = getenv("TDRN_MAIN_GRID")) main_grid = atoi(e);      // experiment: cap the persistent grids of the main lane (CUs left to the other step in flight)
-        if (const char *rb = getenv("TDRN_SPLITK_REF")) splitk_ref_batch = atoi(rb) > 0 ? atoi(rb) : 32;
-        // split-K per layer from its geometry only (at the reference batch, 32 unless TDRN_SPLITK_REF says otherwise), so that a frame's arithmetic never
+        late_side = !(cfg.plan_flags & TDRN_PLAN_NO_LATE_SIDE);
+        // split-K per layer from its geometry only (at a fixed reference batch: the benchmark's), so that a frame's arithmetic never
         // depends on the batch it travels in; the partial slabs live in a per-lane region of the workspace
         {
+            constexpr int kSplitkRefBatch = 32;
             size_t lane_bytes[kLanes] = {0, 0, 0, 0};
             for (Op &o : ops) {
-                if (o.kind == OP_CONV && o.pool_t >= 0 && conv_patch_enabled()) o.stat = ST_CONV3;
+                if (o.kind == OP_CONV && o.pool_t >= 0) o.stat = ST_CONV3;
                 if (o.kind != OP_CONV || o.pool_t >= 0) continue;
                 const Tensor &ti = tensors[o.in];
                 ConvArgs a;
-                a.B = splitk_ref_batch; a.H = ti.H; a.W = ti.W; a.Cin = o.Cin; a.Ho = o.hw >> 16; a.Wo = o.hw & 0xffff;
+                a.B = kSplitkRefBatch; a.H = ti.H; a.W = ti.W; a.Cin = o.Cin; a.Ho = o.hw >> 16; a.Wo = o.hw & 0xffff;
                 a.Cout = o.Cout; a.Npad = o.Npad; a.kh = a.kw = o.k; a.stride = o.stride; a.pad = o.pad; a.dil = o.dil;
                 a.phases = o.phases; a.dtype = cfg.dtype; a.out_f32 = o.out_kind != OUT_TENSOR;
                 a.kdisable = kdisable;
@@ -796,8 +785,7 @@ struct tdrn_net {
                 a.o_cs = o.out_kind == OUT_TENSOR ? tensors[o.out].Cpad : 0;
                 a.o_rs = (long long)a.Wo * a.o_cs; a.o_bs = (long long)a.Ho * a.Wo * a.o_cs;
                 a.res = o.res >= 0 ? (const void *)1 : nullptr;
-                if (o.splitk == 1 && conv_patch_enabled() && patch_conv_supported(a) && a.H * a.W >= conv_patch_enabled() * 400)
-                    o.stat = ST_CONV3;
+                if (o.splitk == 1 && patch_conv_takes(a)) o.stat = ST_CONV3;
                 if (o.chain_tag && !(o.out_kind == OUT_TENSOR && conv_chain_supported(a))) o.chain_tag = false;
             }
             // The chain launch: tagged layers whose inputs are chain members or exist before the first member starts (a layer
@@ -805,8 +793,7 @@ struct tdrn_net {
             // the main lane and get their own split-K slabs (stages overlap inside the launch).
             chain_ops.clear();
             {
-                const char *ce = getenv("TDRN_CHAIN");
-                const bool chain_on = ce ? atoi(ce) != 0 : (cfg.plan_flags & TDRN_PLAN_CHAIN) != 0;   // opt-in: it lost (conv_igemm.hip)
+                const bool chain_on = (cfg.plan_flags & TDRN_PLAN_CHAIN) != 0;   // opt-in: it lost (conv_igemm.hip)
                 int first = -1;
                 for (size_t i = 0; i < ops.size() && chain_on; ++i) {
                     Op &o = ops[i];
@@ -875,7 +862,7 @@ struct tdrn_net {
         // a depthwise op directly followed by its pointwise conv, which is the only
         // reader of the depthwise output; decided from the geometry (the batch-dependent 4-GiB limit is re-checked per forward,
         // which then falls back to the two launches: the depthwise tensor keeps its place in the workspace)
-        if (cfg.dtype != TDRN_F32 && ((cfg.plan_flags & TDRN_PLAN_DWPW) || dwpw_enabled() > 1))
+        if (cfg.dtype != TDRN_F32 && (cfg.plan_flags & TDRN_PLAN_DWPW))
             for (size_t i = 0; i + 1 < ops.size(); ++i) {
                 Op &d = ops[i];
                 Op &c = ops[i + 1];
@@ -904,11 +891,12 @@ struct tdrn_net {
             for (const Op &o : ops)
                 if (o.kind == OP_CONV && o.stat == ST_CONV3 && o.lane == 0 && o.Cin >= 256 && o.Npad % 256 == 0) pp_sk_planned = true;
         if (pp_sk_planned || !chain_ops.empty()) ws_fixed = kTailCtl + (pp_sk_planned ? align_up(conv_pp_sk_bytes(), 256) : 1024);
-        const char *e = getenv("TDRN_STREAMS");
-        if (cfg.plan_flags & TDRN_PLAN_ONE_STREAM) use_lanes = false;
-        if (e) use_lanes = atoi(e) > 1;
-        const char *ds = getenv("TDRN_DEFORM_SPLIT");
-        if (ds && atoi(ds) == 0) deform_split = false;
+        use_lanes = !(cfg.plan_flags & TDRN_PLAN_ONE_STREAM);
+        // Y layout of the transform-then-sample heads: tap-major [tap][pixel][80] when every level's transform runs on ygemm_k256
+        // (which writes it), else the plain [pixel][columns] matrix of the generic GEMM
+        y_tap_major = true;
+        for (const Op &d : ops)
+            if (d.kind == OP_DEFORM && d.y_t >= 0 && !ygemm_supported(d.Cin, d.y_cols, cfg.dtype)) y_tap_major = false;
         tensor_lane.assign(tensors.size(), 0);
         tensor_shared.assign(tensors.size(), 0);
         for (const Op &o : ops) {
@@ -1201,7 +1189,7 @@ struct tdrn_net {
         // split two-branch deformable heads accumulate into zeroed outputs: zero them on a side stream at the very
         // start (under the first conv) instead of in front of the deform launch on the critical path
         bool zeroed_early = false;
-        if (lanes && deform_split) {
+        if (lanes) {
             const Op *dsplit = nullptr;
             int n_deform_groups = 0;
             for (size_t k = 0; k < ops.size(); ++k)
@@ -1272,13 +1260,6 @@ struct tdrn_net {
         };
         DeformArgs dargs[4];
         const void *ts_y[4] = {nullptr, nullptr, nullptr, nullptr};
-        // Y layout of the transform-then-sample heads: tap-major [tap][pixel][80] when every level's transform runs on ygemm_k256
-        // (which writes it), else the plain [pixel][columns] matrix of the generic GEMM
-        static int ts_tap_env = -1;
-        if (ts_tap_env < 0) { const char *e = getenv("TDRN_Y_TAP_MAJOR"); ts_tap_env = e ? atoi(e) : 1; }
-        int ts_tap_major = ts_tap_env ? 1 : 0;
-        for (const Op &d : ops)
-            if (d.kind == OP_DEFORM && d.y_t >= 0 && !ygemm_supported(d.Cin, d.y_cols, cfg.dtype)) ts_tap_major = 0;
         int ts_cs[4] = {0, 0, 0, 0}, ts_op[4] = {-1, -1, -1, -1};
         int n_dargs = 0;
         OffsetProblem oq[4];                                // consecutive offset convs of one lane: one launch (layers.hip)
@@ -1320,10 +1301,8 @@ struct tdrn_net {
                 }
                 for (int t : {o.in, o.res, o.off_t})
                     if (t >= 0 && tensor_lane[t] != lane) TDRN_HIP_TRY(hipStreamWaitEvent(s, tensor_ev[t], 0));
-                if (late_side && lane != 0 && (o.kind == OP_CONV || o.kind == OP_OFFSET)) {
-                    const int tl = late_side == 2 ? t_late2 : t_late;
-                    if (tl >= 0 && tensor_shared[tl]) TDRN_HIP_TRY(hipStreamWaitEvent(s, tensor_ev[tl], 0));
-                }
+                if (late_side && lane != 0 && (o.kind == OP_CONV || o.kind == OP_OFFSET) && t_late >= 0 && tensor_shared[t_late])
+                    TDRN_HIP_TRY(hipStreamWaitEvent(s, tensor_ev[t_late], 0));
             }
             const bool deform_batched = o.kind == OP_DEFORM && oi + 1 < ops.size() && ops[oi + 1].kind == OP_DEFORM && n_dargs < 3;
             const bool offset_batched = o.kind == OP_OFFSET && oi + 1 < ops.size() && ops[oi + 1].kind == OP_OFFSET && n_oq < 3 &&
@@ -1372,8 +1351,6 @@ struct tdrn_net {
                     }
                     ConvArgs a;
                     conv_args(o, a);
-                    if (lane != 0) a.max_wgs = side_grid;
-                    else if (main_grid > 0) a.max_wgs = main_grid;
                     if (o.lane == 0 && pp_sk_planned) {
                         a.sk_ws = tail + kTailCtl;
                         a.sk_flags_zero = true;
@@ -1401,7 +1378,7 @@ struct tdrn_net {
                         }
                         a.fuse_x = xin;
                     }
-                    if (a.fuse_x && !(conv_patch_enabled() && patch_conv_supported(a) > 0)) {
+                    if (a.fuse_x && patch_conv_supported(a) <= 0) {
                         // the fusion was planned from the layer geometry; should the patch kernel decline THIS launch (a limit
                         // that depends on the batch), run the two layers as two launches: the first conv's tensor keeps its place
                         // in the workspace
@@ -1412,7 +1389,7 @@ struct tdrn_net {
                     }
                     if (o.pool_t >= 0) {
                         const Tensor &tp = tensors[o.pool_t];
-                        if (conv_patch_enabled() && patch_conv_supported(a) > 0) {
+                        if (patch_conv_supported(a) > 0) {
                             a.out = nullptr;                 // only the pooled map leaves the chip
                             rc = launch_conv3x3_patch(a, tptr(ws, o.pool_t, B), s);
                         } else {
@@ -1519,14 +1496,13 @@ struct tdrn_net {
                         {   // ... and (round 5) a range's Y is kept below 192 MiB, so that it is still in the 256-MiB memory-side cache when
                             // the sampling launch gathers it: the pair of launches 277-285 -> 254-255 us alone at batch 32 (two ranges of
                             // 16 frames; ranges of 8 / 4 frames lose it again to the extra launches), 520 -> 488 us at MobileNet's batch 64.
-                            // Per-frame arithmetic untouched.  TDRN_TS_RANGE_MB=0 switches it off, another value is another bound.
-                            static long long cap_mb = -1;
-                            if (cap_mb < 0) { const char *e = getenv("TDRN_TS_RANGE_MB"); cap_mb = e ? atoll(e) : 192; }
+                            // Per-frame arithmetic untouched.  TDRN_PLAN_TS_ONE_RANGE switches it off.
+                            constexpr size_t kRangeBytes = (size_t)192 << 20;
                             size_t per_frame = 0;
                             for (int i = 0; i < n_dargs; ++i)
                                 per_frame += (size_t)dargs[i].H * dargs[i].W * ops[ts_op[i]].y_cols * es;       // (one column group's Y: a group's two launches are adjacent)
-                            if (cap_mb > 0 && per_frame > 0 && !(kdisable & 512)) {
-                                long long fit = (long long)((size_t)cap_mb << 20) / (long long)per_frame;
+                            if (per_frame > 0 && !(kdisable & 512)) {
+                                long long fit = (long long)kRangeBytes / (long long)per_frame;
                                 fit = fit < 1 ? 1 : fit;
                                 if (fit < Bc) Bc = (int)fit;
                             }
@@ -1542,8 +1518,6 @@ struct tdrn_net {
                             int n_yq = 0;
                             bool all_ygemm = true;
                             for (int i = 0; i < n_dargs; ++i) all_ygemm = all_ygemm && ygemm_supported(ops[ts_op[i]].Cin, ops[ts_op[i]].y_cols, cfg.dtype);
-                            static int ymulti = -1;
-                            if (ymulti < 0) { const char *e = getenv("TDRN_YGEMM_MULTI"); ymulti = e ? atoi(e) : 1; }
                             for (int i = 0; i < n_dargs && rc == TDRN_OK; ++i) {
                                 const Op &d = ops[ts_op[i]];
                                 DeformArgs &c = ca[i];
@@ -1564,10 +1538,10 @@ struct tdrn_net {
                                 const char *wty = wb + d.wt_off + (size_t)yg * d.y_cols * d.Cin * es;
                                 c.Cout = d.Cout - 80 * yg < 80 ? d.Cout - 80 * yg : 80;
                                 if (yg > 0) { c.split = 0; c.out1 += 80 * yg - 12; }     // (columns 12.. are conf columns: group g starts at conf column 80 g - 12)
-                                if (all_ygemm && ymulti) {       // all levels' transforms in ONE launch (below)
-                                    yq[n_yq++] = YGemmProblem{c.in, wty, ybuf, (long long)nb * c.H * c.W, d.y_cols, d.y_cols, ts_tap_major ? taps : 0};
+                                if (all_ygemm) {                 // all levels' transforms in ONE launch (below)
+                                    yq[n_yq++] = YGemmProblem{c.in, wty, ybuf, (long long)nb * c.H * c.W, d.y_cols, d.y_cols, y_tap_major ? taps : 0};
                                 } else if (ygemm_supported(d.Cin, d.y_cols, cfg.dtype)) {
-                                    rc = launch_ygemm(c.in, wty, ybuf, (long long)nb * c.H * c.W, d.y_cols, d.y_cols, cfg.dtype, s, ts_tap_major ? taps : 0);
+                                    rc = launch_ygemm(c.in, wty, ybuf, (long long)nb * c.H * c.W, d.y_cols, d.y_cols, cfg.dtype, s, y_tap_major ? taps : 0);
                                 } else {
                                     ConvArgs g;
                                     g.in = c.in; g.w = wty; g.bias = (const float *)(wb + d.bt_off); g.zero_page = wb;
@@ -1580,13 +1554,13 @@ struct tdrn_net {
                                 ts_y[i] = ybuf; ts_cs[i] = d.y_cols;
                             }
                             if (rc == TDRN_OK && n_yq > 0) rc = launch_ygemm_multi(yq, n_yq, cfg.dtype, s, kdisable);
-                            if (rc == TDRN_OK) rc = launch_deform_sample_multi(ca, ts_y, ts_cs, n_dargs, s, ts_tap_major);
+                            if (rc == TDRN_OK) rc = launch_deform_sample_multi(ca, ts_y, ts_cs, n_dargs, s, y_tap_major ? 1 : 0);
                           }
                         n_dargs = 0;
                         break;
                     }
                     if (!deform_batched) {      // all pyramid levels in one launch
-                        const int split = !deform_split ? 0 : (o.n_branches == 2 ? 1 : ((o.G >= 2 && o.G % 2 == 0) ? 2 : 0));
+                        const int split = o.n_branches == 2 ? 1 : ((o.G >= 2 && o.G % 2 == 0) ? 2 : 0);
                         if (split) {             // the two branches / the two halves of the groups accumulate into zeroed outputs
                             if (zeroed_early) {
                                 TDRN_HIP_TRY(hipStreamWaitEvent(s, ev_zero, 0));
@@ -1812,12 +1786,7 @@ int tdrn_net_op_info(const tdrn_net *net, int index, tdrn_op_info *out)
     out->splitk = o.splitk; out->groups = o.G; out->out_kind = o.out_kind; out->level = o.scale;
     out->n_branches = o.n_branches; out->k2 = o.k2; out->pad2 = o.pad2; out->off_c0[0] = o.off_c0[0]; out->off_c0[1] = o.off_c0[1];
     if (o.kind == OP_DEFORM && o.y_t >= 0) {
-        static int tm = -1;
-        if (tm < 0) { const char *e = getenv("TDRN_Y_TAP_MAJOR"); tm = e ? atoi(e) : 1; }
-        bool all = tm != 0;
-        for (const Op &d : net->ops)
-            if (d.kind == OP_DEFORM && d.y_t >= 0 && !ygemm_supported(d.Cin, d.y_cols, net->cfg.dtype)) all = false;
-        out->y_tap_major = all ? 1 : 0;
+        out->y_tap_major = net->y_tap_major ? 1 : 0;
         out->y_groups = o.y_groups;
     }
     out->fused_first = (index == net->fuse_first) ? 1 : 0;

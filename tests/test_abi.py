@@ -39,6 +39,16 @@ def test_no_product_import_of_the_oracle():
     assert not bad, "product code must never touch oracle/: %r" % bad
 
 
+def test_library_reads_no_kernel_choice_from_the_environment():
+    # kernel choice goes through tdrn_net_config.plan_flags only; TDRN_WGTIME_CALL is read by a diagnostics build (#ifdef)
+    csrc = os.path.join(ROOT, "tdrn_amd", "csrc")
+    names = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            names.update(re.findall(r'getenv\(\s*"([^"]*)"', open(os.path.join(csrc, f)).read()))
+    assert names <= {"TDRN_PLAN_DUMP", "TDRN_WGTIME_CALL"}, sorted(names)
+
+
 def test_priorbox_host_bit_exact(golden_dir):
     for name in ("VOC_320", "VOC_512_RefineDet"):
         ref = np.load(os.path.join(golden_dir, "priorbox_%s.npz" % name))["priors"]

@@ -692,13 +692,12 @@ def test_fused_first_conv_at_a_batch_past_4gib_of_input():
 
 
 @pytest.mark.parametrize("model,args", [("dualrefinedet_vggbn", (320, 21, 1024, 1, True, True)), ("ssd4scale_vgg", (320, 21, 1024, False, False))])
-def test_fused_first_conv_equals_two_launches(model, args, monkeypatch):
+def test_fused_first_conv_equals_two_launches(model, args):
     """16-bit plans compute the first conv inside conv1_2's patch loader (conv3x3_patch.hip FUSE): same operand layout and
     instruction as the stand-alone kernel, so every output is BIT-identical to the two-launch plan (plan_flags TDRN_PLAN_NO_FUSE_FIRST) --
     at the build size, at other frame sizes (tiles at every border, fewer items than CUs) and at batch 1 / 3 / 8."""
     # (the multihead DRN needs a >= 5x5 coarsest map for its 5x5 deformable heads: sizes from 320 up)
     cases = [(320, 3), (320, 8), (384, 3), (448, 1), (704, 1)] + ([(192, 3), (256, 1)] if model == "ssd4scale_vgg" else [])
-    monkeypatch.delenv("TDRN_FUSE_FIRST", raising=False)
     for dtype in ("bf16", "fp16"):
         fused, _ = _build(model, args)                       # two handles in one process, differing only in plan_flags
         fused.set_compute_dtype(dtype)
