@@ -171,7 +171,8 @@ TDRN_API int tdrn_gpu_nms_host(int *keep_out, int *num_out, const float *boxes_h
                                int boxes_num, int boxes_dim, float nms_overlap_thresh,
                                int device_id);
 
-/* decode / center_size -- layers/box_utils.py:176-195, :16-25.  Device fp32 (P,4) arrays. */
+/* decode / center_size -- layers/box_utils.py:176-195, :16-25.  Device fp32 (P,4) arrays, each 16-byte aligned (the rows are
+ * read and written as 16-byte vectors): any other address -> TDRN_E_ARG, checked on the host before anything is enqueued. */
 TDRN_API int tdrn_decode(const float *loc, const float *priors, int P, float var0, float var1,
                          float *boxes_out, void *stream);
 TDRN_API int tdrn_center_size(const float *boxes, int P, float *out, void *stream);
@@ -187,7 +188,8 @@ TDRN_API int tdrn_prior_box(int n_maps, const int *feature_maps, double image_si
 /* Detect.forward -- layers/functions/detection.py:25-70, fully on device, batched over
  * (image, class):  two-stage decode (:43-48), score > conf_thresh (:53), boxes*scale (:59),
  * cpu_nms semantics (:60), first top_k survivors packed as [score,x1,y1,x2,y2] (:61-63).
- *   loc (B,P,4)  conf (B*P,C)  priors (P,4)  arm_loc (B,P,4) or NULL  -- device fp32
+ *   loc (B,P,4)  conf (B*P,C)  priors (P,4)  arm_loc (B,P,4) or NULL  -- device fp32; loc, priors, arm_loc and the workspace
+ *   must be 16-byte aligned (read / written as 16-byte vectors; TDRN_E_ARG otherwise, before anything is enqueued)
  *   scale: 4 HOST floats (the caller's [w,h,w,h]; evaluate.py:461)
  *   out (B,C,top_k,5) device fp32, fully overwritten (class 0 and unused slots = 0)
  *   counts_out (B*C) device int32 or NULL: survivors per (image,class), capped at top_k. */
@@ -320,6 +322,9 @@ TDRN_API int tdrn_net_pack_weights(tdrn_net *net, void *weights_dev, size_t weig
                                    void *stream);
 TDRN_API int tdrn_net_adopt_weights(tdrn_net *net);
 
+/* The outputs (arm_loc, odm_loc, conf, offsets[], loc_maps[]) may start at ANY 4-byte-aligned address: the same bits as at a
+ * 16-byte-aligned one (the geometry alone chooses the kernels and their arithmetic; a 16-byte store becomes four 4-byte ones).
+ * Each is written exactly over its own extent: (B,P,4) / (B*P,C) / (B,G*18,H,W) / (B,12,H,W) floats, nothing before or behind. */
 typedef struct {
     const float *x;        /* (B,3,S,S) fp32 NCHW, mean-subtracted 0..255 range, device      */
     int batch;
@@ -328,7 +333,7 @@ typedef struct {
     float *conf;           /* (B*P,C) fp32 softmax (test phase) or logits                    */
     float *offsets[4];     /* optional (B,G*18,H,W) fp32 NCHW out (arm_offset_list); or NULL */
     const float *ref_loc[4]; /* ssd4scale deform=1: (B,12,H,W) fp32 NCHW loc maps IN        */
-    float *loc_maps[4];    /* ssd4scale ret_loc: (B,12,H,W) fp32 NCHW raw loc maps OUT       */
+    float *loc_maps[4];    /* ssd4scale deform=0 ret_loc: (B,12,H,W) fp32 NCHW raw loc maps OUT */
     /* reserved[0] != NULL, ssd4scale deform=1 only: REUSE the deformable offsets the previous forward of this net computed in
      * this workspace at this batch size instead of recomputing them from ref_loc (the reference's cached offset_list of the frames
      * between two key frames, evaluate_trn.py:459-462: offsets are a function of the key frame's loc maps only).  ref_loc may then

@@ -171,6 +171,13 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def aligned16(t):
+    """`t`, or a copy of it when its data does not start on a 16-byte boundary: for the entries that read a (., 4) fp32 array
+    as 16-byte vectors and return TDRN_E_ARG for any other address (tdrn_decode, tdrn_center_size, tdrn_detect).  A slice
+    of a larger buffer -- e.g. an `out=` view handed to NetEngine.forward -- may start on any 4-byte boundary."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
 def current_stream(device=None):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

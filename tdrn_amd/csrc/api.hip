@@ -252,12 +252,14 @@ int tdrn_gpu_nms_host(int *keep_out, int *num_out, const float *boxes_host, int 
 int tdrn_decode(const float *loc, const float *priors, int P, float var0, float var1, float *boxes_out, void *stream)
 {
     if (!loc || !priors || !boxes_out || P < 0) return TDRN_E_ARG;
+    if (((uintptr_t)loc | (uintptr_t)priors | (uintptr_t)boxes_out) & 15) return TDRN_E_ARG;     // (P,4) rows as 16-byte vectors
     return launch_decode(loc, priors, P, var0, var1, boxes_out, (hipStream_t)stream);
 }
 
 int tdrn_center_size(const float *boxes, int P, float *out, void *stream)
 {
     if (!boxes || !out || P < 0) return TDRN_E_ARG;
+    if (((uintptr_t)boxes | (uintptr_t)out) & 15) return TDRN_E_ARG;                               // (P,4) rows as 16-byte vectors
     return launch_center_size(boxes, P, out, (hipStream_t)stream);
 }
 

@@ -667,6 +667,8 @@ int launch_detect(const float *loc, const float *conf, const float *priors, cons
 {
     if (!loc || !conf || !priors || !scale4 || !out || !ws) return TDRN_E_ARG;
     if (scale_on_device && ((uintptr_t)scale4 & 15)) return TDRN_E_ARG;
+    // loc / arm_loc / priors rows are read, and the decoded boxes stored into the workspace, as 16-byte vectors
+    if (((uintptr_t)loc | (uintptr_t)arm_loc | (uintptr_t)priors | (uintptr_t)ws) & 15) return TDRN_E_ARG;
     if (nms_thresh <= 0) return TDRN_E_VALUE;
     if (B <= 0 || P <= 0 || C < 2 || top_k <= 0) return TDRN_E_ARG;
     if (ws_bytes < detect_workspace_bytes(B, P, C, top_k)) return TDRN_E_WORKSPACE;

@@ -28,7 +28,7 @@ struct Head3Params {
     float *out;                    // element (b, y, x, co) at out + b * o_bs + y * o_rs + x * o_cs + co
     long long o_bs, o_rs, o_cs;
     int B, H, W, Cin, Cout, relu, tiles_per_img;
-    int vec16;                     // out is 16-byte aligned: a pixel's four columns go out as one dwordx4
+    int vec16;                     // out is 16-byte aligned: a pixel's four columns go out as one dwordx4 (else four dword stores)
 };
 
 constexpr int kH3MaxW = 64;
@@ -152,8 +152,13 @@ __global__ __launch_bounds__(512, 2) void head3x3_kernel(const Head3Params p)
         if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
         const int left = p.Cout - 4 * kg;
         if (left >= 4 && p.vec16) *(f32x4 *)dst = v;
-        else
-            for (int i = 0; i < left; ++i) dst[i] = v[i];
+        else {
+            // my four columns at most, one by one (columns 4 kg + 4.. belong to the next lane groups of this pixel)
+            if (left > 0) dst[0] = v[0];
+            if (left > 1) dst[1] = v[1];
+            if (left > 2) dst[2] = v[2];
+            if (left > 3) dst[3] = v[3];
+        }
     }
 }
 

@@ -126,11 +126,12 @@ class NetEngine(object):
         x = x.contiguous() if u8 is not None else x.contiguous().float()
         B, P, Cn = x.size(0), self.num_priors, self.num_classes
         dev = x.device
-        ws = self.workspace(B)
         ssd = self.cfg.model in (_lib.SSD4SCALE_MOBILE, _lib.SSD4SCALE_VGG)
-        o = out or {}
-        arm_loc = o.get("arm_loc")
         has_arm = not (self.cfg.model == _lib.REFINEDET_VGG and not self.cfg.use_refine)
+        o = out or {}
+        self._check_out(o, B, dev, has_arm, not ssd)
+        ws = self.workspace(B)
+        arm_loc = o.get("arm_loc")
         if arm_loc is None and has_arm:
             arm_loc = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
         odm_loc = None
@@ -198,6 +199,37 @@ class NetEngine(object):
         res = {"arm_loc": arm_loc, "odm_loc": odm_loc, "conf": conf, "offsets": offsets, "loc_maps": loc_maps,
                "offsets_token": getattr(self, "_offs_token", None)}
         return res
+
+    def _check_out(self, o, B, dev, has_arm, has_odm):
+        """`out=` of forward(): the library writes through the raw pointers, so every buffer must be exactly what forward()
+        would allocate -- a wrong one would be a silent out-of-bounds write on the device.  Any 4-byte-aligned address is fine
+        (tdrn_net_io: same bits)."""
+        shapes = {"conf": (B * self.num_priors, self.num_classes)}
+        if has_arm:
+            shapes["arm_loc"] = (B, self.num_priors, 4)
+        if has_odm:
+            shapes["odm_loc"] = (B, self.num_priors, 4)
+        spans = []
+        for k, t in o.items():
+            if k not in ("arm_loc", "odm_loc", "conf"):
+                raise ValueError("out: unknown output %r (expected arm_loc, odm_loc, conf)" % (k,))
+            if k not in shapes:
+                raise ValueError("out: this model has no %r output" % (k,))
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise ValueError("out[%r] must be a float32 tensor" % (k,))
+            if t.device != dev:
+                raise ValueError("out[%r] is on %s, the input on %s" % (k, t.device, dev))
+            if not t.is_contiguous():
+                raise ValueError("out[%r] must be contiguous" % (k,))
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError("out[%r] has shape %r, expected %r" % (k, tuple(t.shape), shapes[k]))
+            spans.append((t.data_ptr(), t.data_ptr() + 4 * t.numel(), k))
+        spans.sort()
+        for (_, e0, k0), (s1, _, k1) in zip(spans, spans[1:]):
+            if s1 < e0:
+                raise ValueError("out[%r] and out[%r] overlap" % (k0, k1))
 
     def check(self):
         """tdrn_net_check: raises TdrnError(TDRN_E_DEVICE) when a forward enqueued since the last check reported a device-side

@@ -31,12 +31,13 @@ class Detect(object):
         _lib.require_cuda(loc_data, "loc_data")
         dev = loc_data.device
         B, P, Cn = loc_data.size(0), prior_data.size(0), self.num_classes
-        loc = loc_data.contiguous().float()
+        # (loc / arm_loc / priors are read as 16-byte vectors: a net output handed over as a 4-byte-aligned slice is copied first)
+        loc = _lib.aligned16(loc_data.contiguous().float())
         conf = conf_data.contiguous().float().view(-1, Cn)
         if conf.size(0) != B * P:
             raise ValueError("conf_data has %d rows, expected %d" % (conf.size(0), B * P))
-        pri = prior_data.to(dev).contiguous().float()
-        arm = arm_loc_data.contiguous().float() if arm_loc_data is not None else None
+        pri = _lib.aligned16(prior_data.to(dev).contiguous().float())
+        arm = _lib.aligned16(arm_loc_data.contiguous().float()) if arm_loc_data is not None else None
         lib = _lib.lib()
         # evaluate.py:461 passes a CUDA tensor: it is read on the device (no .tolist() = no hidden device sync)
         scale_d = None
