@@ -177,6 +177,64 @@ TDRN_API int tdrn_decode(const float *loc, const float *priors, int P, float var
                          float *boxes_out, void *stream);
 TDRN_API int tdrn_center_size(const float *boxes, int P, float *out, void *stream);
 
+/* ========================================================================================
+ * (ii-b) Training losses, fp32 -- replace
+ *     match(threshold, truths, priors, variances, labels, loc_t, conf_t, idx)     layers/box_utils.py:81-121
+ *     refine_match(..., idx, arm_loc)                                              :123-149
+ *     MultiBoxLoss.forward / RefineMultiBoxLoss.forward      layers/modules/multibox_loss.py:59-110,
+ *                                                            layers/modules/refine_multibox_loss.py:28-102
+ *   and their autograd backward.  Semantics are the reference's, quirks included:
+ *   - IoU: truths against point_form(priors) (match) or against the ARM decode of the priors (refine_match; the decode is
+ *     tdrn_decode's arithmetic); op order of intersect / jaccard (:28-67): inter = clamp(min(x2)-max(x1),0) *
+ *     clamp(min(y2)-max(y1),0), union = (area_a + area_b) - inter, iou = inter / union, correctly rounded.
+ *   - argmax ties go to the lowest index (torch CPU): a prior that overlaps no truth takes truth 0, a truth that overlaps
+ *     no prior takes prior 0.  Forced matches: overlap 2 at every truth's best prior, then in ascending j
+ *     best_truth_idx[best_prior_idx[j]] = j, so when truths share a best prior the LAST j wins.
+ *   - conf_t = (int)(label + 1) (the float -> long truncation), 0 where the overlap is below `threshold`.
+ *   - encode (:151-172) op for op, against the priors (match) or center_size(decoded) (refine_match).
+ *   - an image with no truths: all background, loc_t = 0, no positives and so no mined negatives (the reference fails).
+ *   - mining score: log_sum_exp with the BATCH-global max of conf (box_utils.py:216-223) minus the target logit; rows whose
+ *     exps all underflow score -inf and rank last; positives score 0.  num_neg = min(negpos_ratio * num_pos, P - 1) per
+ *     image; a row is a negative when its rank in a STABLE descending sort of the score is below num_neg (ties: the lower
+ *     prior index first).  A positive that ranks in is counted once (pos u neg).
+ *   - loss_l = smooth-L1 (beta 1, summed) over positives; loss_c = cross entropy (summed, per-row log-softmax) over
+ *     pos u neg; both divided by N = sum of num_pos as float.  N = 0 gives 0/0 = NaN, as the reference's arithmetic.
+ *   - backward: d/d loc = g_l / N * clamp(loc - loc_t, -1, 1) on positives, d/d conf = g_c / N * (softmax(conf) -
+ *     onehot(conf_t)) on pos u neg, 0 elsewhere; targets and arm_loc get no gradient (the reference detaches them).
+ *   prior_for_matching, bkg_label, neg_mining, neg_overlap, encode_target are unused by the reference and have no argument.
+ *
+ * tdrn_match: B images in one call.  truths (T_total, 5) device fp32 rows [x1,y1,x2,y2,label], image b = rows
+ *   [truth_off[b], truth_off[b+1]) with truth_off (B+1) int32 DEVICE; every image has at most max_truths rows (<= 512,
+ *   else TDRN_E_UNSUPPORTED; offsets that break the promise are clamped, never followed out of bounds).  truths may be
+ *   NULL when T_total = 0.  priors (P,4) center-size; arm_loc (B,P,4) or NULL (NULL: match, else refine_match).
+ *   loc_t (B,P,4) fp32 and conf_t (B,P) int32, fully overwritten.
+ * tdrn_multibox_loss_forward: loc (B,P,4), conf (B,P,C) or NULL (= only_loc: no mining, loss_out[1] untouched), loc_t,
+ *   conf_t as tdrn_match writes them.  C <= 1024 (TDRN_E_UNSUPPORTED above).  Outputs, all device: loss_out (2) fp32 =
+ *   [loss_l / N, loss_c / N]; sel (B,P) uint8 = 0 unused, 1 positive, 2 mined negative; num_pos (B) int32.
+ *   The workspace query takes C = 0 for only_loc.
+ * tdrn_multibox_loss_backward: grad_loss (2) DEVICE fp32 = [d/d loss_l, d/d loss_c] (read on the device: no host round
+ *   trip); sel and num_pos of the forward; grad_loc (B,P,4) and grad_conf (B,P,C) fully overwritten (grad_conf unused
+ *   when conf is NULL).  No workspace: the softmax is recomputed from conf.
+ *   priors, arm_loc, loc, loc_t and grad_loc must be 16-byte aligned (read / written as 16-byte vectors; TDRN_E_ARG
+ *   otherwise, before anything is enqueued); every other pointer needs only its element alignment.
+ *   Errors before any launch: TDRN_E_ARG (null pointer, bad size), TDRN_E_WORKSPACE, TDRN_E_UNSUPPORTED.  No allocation, no
+ *   host synchronisation, no float atomics: every sum runs in a fixed order, so results are bitwise reproducible.
+ * ====================================================================================== */
+/* encode alone (box_utils.py:151-172, the arithmetic tdrn_match uses): matched (P,4) point form, priors (P,4) center-size,
+ * out (P,4); all three 16-byte aligned (TDRN_E_ARG otherwise). */
+TDRN_API int tdrn_encode(const float *matched, const float *priors, int P, float var0, float var1, float *out, void *stream);
+TDRN_API size_t tdrn_match_workspace_bytes(int B, int P, int max_truths);
+TDRN_API int tdrn_match(const float *truths, const int32_t *truth_off, int T_total, int max_truths, int B,
+                        const float *priors, int P, const float *arm_loc, float threshold, float var0, float var1,
+                        float *loc_t, int32_t *conf_t, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API size_t tdrn_multibox_loss_workspace_bytes(int B, int P, int C);
+TDRN_API int tdrn_multibox_loss_forward(const float *loc, const float *conf, const float *loc_t, const int32_t *conf_t,
+                                        int B, int P, int C, int negpos_ratio, float *loss_out, uint8_t *sel,
+                                        int32_t *num_pos, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_multibox_loss_backward(const float *loc, const float *conf, const float *loc_t, const int32_t *conf_t,
+                                         const uint8_t *sel, const int32_t *num_pos, const float *grad_loss, int B,
+                                         int P, int C, float *grad_loc, float *grad_conf, void *stream);
+
 /* PriorBox.forward -- layers/functions/prior_box.py:33-64 (host, double arithmetic, cast to
  * fp32, clamp).  aspect_ratios ragged: ar_count[k] values per map, concatenated in `ars`.
  * out == NULL: returns the number of priors only.  Returns P (>= 0) or a negative error. */

@@ -81,6 +81,13 @@ _SIGS = {
     "tdrn_gpu_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]),
     "tdrn_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "tdrn_center_size": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdrn_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "tdrn_match_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "tdrn_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                             C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_multibox_loss_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "tdrn_multibox_loss_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "tdrn_multibox_loss_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 3),
     "tdrn_prior_box": (C.c_int, [C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tdrn_nms_topk_classes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

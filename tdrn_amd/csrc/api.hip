@@ -263,6 +263,39 @@ int tdrn_center_size(const float *boxes, int P, float *out, void *stream)
     return launch_center_size(boxes, P, out, (hipStream_t)stream);
 }
 
+int tdrn_encode(const float *matched, const float *priors, int P, float var0, float var1, float *out, void *stream)
+{
+    return launch_encode(matched, priors, P, var0, var1, out, (hipStream_t)stream);
+}
+
+size_t tdrn_match_workspace_bytes(int B, int P, int max_truths) { return match_workspace_bytes(B, P, max_truths); }
+
+int tdrn_match(const float *truths, const int32_t *truth_off, int T_total, int max_truths, int B, const float *priors, int P,
+               const float *arm_loc, float threshold, float var0, float var1, float *loc_t, int32_t *conf_t, void *workspace,
+               size_t workspace_bytes, void *stream)
+{
+    return launch_match(truths, truth_off, T_total, max_truths, B, priors, P, arm_loc, threshold, var0, var1, loc_t, conf_t,
+                        workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t tdrn_multibox_loss_workspace_bytes(int B, int P, int C) { return multibox_loss_workspace_bytes(B, P, C); }
+
+int tdrn_multibox_loss_forward(const float *loc, const float *conf, const float *loc_t, const int32_t *conf_t, int B, int P, int C,
+                               int negpos_ratio, float *loss_out, uint8_t *sel, int32_t *num_pos, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    return launch_multibox_loss_forward(loc, conf, loc_t, conf_t, B, P, C, negpos_ratio, loss_out, sel, num_pos, workspace,
+                                        workspace_bytes, (hipStream_t)stream);
+}
+
+int tdrn_multibox_loss_backward(const float *loc, const float *conf, const float *loc_t, const int32_t *conf_t, const uint8_t *sel,
+                                const int32_t *num_pos, const float *grad_loss, int B, int P, int C, float *grad_loc,
+                                float *grad_conf, void *stream)
+{
+    return launch_multibox_loss_backward(loc, conf, loc_t, conf_t, sel, num_pos, grad_loss, B, P, C, grad_loc, grad_conf,
+                                         (hipStream_t)stream);
+}
+
 int tdrn_prior_box(int n_maps, const int *feature_maps, double image_size, const double *steps, const double *min_sizes,
                    const double *max_sizes, int n_max_sizes, const int *ar_count, const double *ars, int clip, int flip,
                    float *out)

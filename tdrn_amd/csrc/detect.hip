@@ -23,30 +23,10 @@
 #include <cmath>
 #include <cstring>
 
+#include "box_coder.h"
 #include "kernels.h"
 
 namespace tdrn {
-
-__device__ __forceinline__ void decode_one(const float *l, const float *pr, float v0, float v1, float *b)
-{
-    const float cx = __fadd_rn(pr[0], __fmul_rn(__fmul_rn(l[0], v0), pr[2]));
-    const float cy = __fadd_rn(pr[1], __fmul_rn(__fmul_rn(l[1], v0), pr[3]));
-    const float w = __fmul_rn(pr[2], expf(__fmul_rn(l[2], v1)));
-    const float h = __fmul_rn(pr[3], expf(__fmul_rn(l[3], v1)));
-    const float x1 = __fsub_rn(cx, __fdiv_rn(w, 2.f));
-    const float y1 = __fsub_rn(cy, __fdiv_rn(h, 2.f));
-    b[0] = x1;
-    b[1] = y1;
-    b[2] = __fadd_rn(w, x1);
-    b[3] = __fadd_rn(h, y1);
-}
-__device__ __forceinline__ void center_size_one(const float *b, float *o)
-{
-    o[0] = __fdiv_rn(__fadd_rn(b[2], b[0]), 2.f);
-    o[1] = __fdiv_rn(__fadd_rn(b[3], b[1]), 2.f);
-    o[2] = __fsub_rn(b[2], b[0]);
-    o[3] = __fsub_rn(b[3], b[1]);
-}
 
 __global__ __launch_bounds__(256) void decode_kernel(const float *__restrict__ loc, const float *__restrict__ priors,
                                                      int P, float v0, float v1, float *__restrict__ out)

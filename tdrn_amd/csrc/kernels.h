@@ -234,4 +234,25 @@ int launch_nms(const float *dets, int n, double thresh, int strict_gt, int preso
                int32_t *keep_out, int32_t *num_out, void *ws, size_t ws_bytes, hipStream_t s,
                int plain_rule = 0, float min_score = -INFINITY, int pre_top_k = 0);
 
+// ---------------------------------------------------------------------------------------------
+// MultiBoxLoss / RefineMultiBoxLoss, fp32 (loss.hip; semantics: tdrn_hip.h section ii-b)
+// ---------------------------------------------------------------------------------------------
+constexpr int kMaxMatchTruths = 512;     // truths per image staged in LDS by the match kernels
+constexpr int kMaxLossClasses = 1024;
+// truths [T_total][5] (x1,y1,x2,y2,label) of all images back to back, image b = rows [truth_off[b], truth_off[b+1]) (device);
+// arm_loc == NULL: match (against point_form(priors)), else refine_match (against the ARM decode).  loc_t (B,P,4), conf_t (B,P).
+size_t match_workspace_bytes(int B, int P, int max_truths);
+int launch_match(const float *truths, const int32_t *truth_off, int T_total, int max_truths, int B, const float *priors, int P,
+                 const float *arm_loc, float threshold, float var0, float var1, float *loc_t, int32_t *conf_t, void *ws,
+                 size_t ws_bytes, hipStream_t s);
+int launch_encode(const float *matched, const float *priors, int P, float v0, float v1, float *out, hipStream_t s);
+// C = 0 in the query (conf == NULL in the launch): only_loc
+size_t multibox_loss_workspace_bytes(int B, int P, int C);
+int launch_multibox_loss_forward(const float *loc, const float *conf, const float *loc_t, const int32_t *conf_t, int B, int P,
+                                 int C, int negpos_ratio, float *loss_out, uint8_t *sel, int32_t *num_pos, void *ws,
+                                 size_t ws_bytes, hipStream_t s);
+int launch_multibox_loss_backward(const float *loc, const float *conf, const float *loc_t, const int32_t *conf_t,
+                                  const uint8_t *sel, const int32_t *num_pos, const float *grad_loss, int B, int P, int C,
+                                  float *grad_loc, float *grad_conf, hipStream_t s);
+
 }  // namespace tdrn

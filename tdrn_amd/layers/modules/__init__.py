@@ -1,3 +1,4 @@
 from .l2norm import L2Norm
+from .multibox_loss import MultiBoxLoss, RefineMultiBoxLoss
 
-__all__ = ['L2Norm']
+__all__ = ['L2Norm', 'MultiBoxLoss', 'RefineMultiBoxLoss']
