@@ -235,6 +235,81 @@ TDRN_API int tdrn_multibox_loss_backward(const float *loc, const float *conf, co
                                          const uint8_t *sel, const int32_t *num_pos, const float *grad_loss, int B,
                                          int P, int C, float *grad_loc, float *grad_conf, void *stream);
 
+/* ========================================================================================
+ * (ii-c) Training augmentation, SSDAugmentation on the device -- replaces
+ *     SSDAugmentation(size, mean) = ConvertFromInts, ToAbsoluteCoords, PhotometricDistort, Expand(mean), RandomSampleCrop,
+ *     RandomMirror, ToPercentCoords, Resize(size), SubtractMeans(mean)         utils/augmentations.py:618-635
+ *   followed by VOCDetection.pull_item's BGR -> RGB and HWC -> CHW (data/voc0712.py:379-382), for a whole batch of raw
+ *   uint8 frames, in two launches and with no host synchronisation.  The draws are consumed in the reference's order
+ *   (augmentations.py:188-198, :544-551, :144-156, :418-442, :237-311, :485-491); semantics are the reference's, quirks
+ *   included:
+ *   - every image goes through the fp32 BGR -> HSV -> BGR round trip (cv2's float path: h in [0, 360], s and v unscaled),
+ *     with contrast before it or after it; brightness adds, contrast and saturation multiply, hue adds and wraps
+ *     (> 360 -> -360, < 0 -> +360), no clamp anywhere.  Off values are exact no-ops (x * 1, x + 0; hue 0 never wraps);
+ *   - lighting noise permutes the channels: canvas channel c = distorted channel perm[c];
+ *   - Expand: a draw of 1 means NO expand.  The canvas is int(h*r) x int(w*r), filled with mean[c] in canvas channel c
+ *     (the mean is not permuted with the image); the image sits at (int(left), int(top)); boxes shift by those ints;
+ *   - RandomSampleCrop: the IoU test never rejects (max_iou is inf), so the five non-None modes sample alike.  left =
+ *     uniform(W - w) and top = uniform(H - h) are one-argument calls (low = W - w, high = 1.0): the left edge lies in
+ *     [1, W - w] when W - w >= 1.  A trial is kept when some box centre lies strictly inside the int rect; kept boxes are
+ *     clamped to it and shifted.  Boxes move in fp64 and are cast to fp32 at the end;
+ *   - Resize is cv2.resize INTER_LINEAR on fp32: source coordinate (d + 0.5) * (n_src / n_dst) - 0.5 in double, cast to
+ *     float, floor, border clamp as tdrn_preprocess_u8; weights (1 - f, f) in fp32, horizontal pass then vertical, unfused.
+ *   Deviations, by design:
+ *   - the reference draws new crop modes without bound; here at most TDRN_AUGMENT_MAX_ROUNDS, then no crop and status bit
+ *     TDRN_AUGMENT_CROP_FALLBACK;
+ *   - an image with no truths gets no crop (the reference never augments one: voc0712.py:360-369);
+ *   - the random source is Philox4x32-10, keyed by the 64-bit seed, counter (draw slot, 0, sample id): a sample's result
+ *     depends on (seed, sample id) alone, not on B or its place in the batch.  The <= 50 crop trials of a mode round run on
+ *     a wave's lanes and the lowest passing trial wins, which has the sequential loop's distribution.  uniform(lo, hi) =
+ *     lo + (hi - lo) * u with a 53-bit u; randint(n) = (32-bit word * n) >> 32.
+ *   - tape mode instead replays recorded draws (randint results and uniform results, in the reference's order) one by one:
+ *     the exact decisions of the reference for its own RandomState.  A tape that runs out ends the crop (no crop), draws
+ *     0 from then on and sets TDRN_AUGMENT_TAPE_EXHAUSTED.
+ *
+ * tdrn_augment_sample: one launch.  hw (B,2) int32 DEVICE [h, w] per image; truths (T_total,5) fp64 DEVICE rows [x1,y1,x2,
+ *   y2,label] as fractions, image b = rows [truth_off[b], truth_off[b+1]) with truth_off (B+1) int32 DEVICE, at most
+ *   max_truths (<= TDRN_AUGMENT_MAX_TRUTHS, else TDRN_E_UNSUPPORTED) per image (offsets that break the promise are clamped).
+ *   Exactly one source: sample_ids (B) int64 DEVICE with `seed` (Philox), or tape (fp64 DEVICE) with tape_off (B+1) int32
+ *   DEVICE (image b replays tape[tape_off[b] .. tape_off[b+1])); both or neither -> TDRN_E_ARG.
+ *   Writes params (B) records, out_truths (T_total,5) fp32 rows [x1,y1,x2,y2,label] (fractions of the output) packed with
+ *   out_off (B+1) int32 -- the truth layout tdrn_match reads; T_total and max_truths of the input remain valid bounds for
+ *   it.  Rows behind out_off[B] are not written.
+ * tdrn_augment_apply: images (B) DEVICE table of {HWC uint8 BGR frame, h, w} (rows of 3*w bytes); params as written by
+ *   tdrn_augment_sample; mean (3) HOST floats (BGR); out (B,3,S,S) fp32 = resized - mean, channels RGB when to_rgb,
+ *   fully overwritten.  Only pixels inside a frame are read, whatever the params say.  S <= TDRN_AUGMENT_MAX_SIZE.
+ *   Errors before any launch: TDRN_E_ARG (null pointer, bad size, no or two sources), TDRN_E_UNSUPPORTED.  No allocation,
+ *   no host synchronisation, no workspace.
+ * ====================================================================================== */
+#define TDRN_AUGMENT_MAX_TRUTHS 512
+#define TDRN_AUGMENT_MAX_ROUNDS 32
+#define TDRN_AUGMENT_MAX_SIZE 2048
+#define TDRN_AUGMENT_CROP_FALLBACK 1     /* status bits */
+#define TDRN_AUGMENT_TAPE_EXHAUSTED 2
+typedef struct {
+    float brightness;        /* added (0 = off) */
+    float contrast_pre;      /* multiplied before the HSV round trip (1 = off) */
+    float contrast_post;     /* multiplied after it (1 = off) */
+    float saturation;        /* multiplies s (1 = off) */
+    float hue;               /* added to h, then wrapped (0 = off) */
+    int32_t perm[3];         /* canvas channel c = distorted channel perm[c] */
+    int32_t canvas_w, canvas_h, img_x, img_y;          /* expand canvas and the frame's place on it (no expand: w, h, 0, 0) */
+    int32_t crop_x0, crop_y0, crop_x1, crop_y1;        /* crop rect on the canvas (no crop: the canvas) */
+    int32_t cropped;         /* 1: a crop trial was kept and its centre test chose the boxes */
+    int32_t mirror;
+    int32_t kept;            /* boxes out */
+    int32_t status;          /* TDRN_AUGMENT_* bits */
+} tdrn_augment_params;
+typedef struct {
+    const uint8_t *data;     /* HWC uint8 BGR, rows of 3 * w bytes */
+    int32_t h, w;
+} tdrn_augment_image;
+TDRN_API int tdrn_augment_sample(const int32_t *hw, const double *truths, const int32_t *truth_off, int T_total, int max_truths,
+                                 int B, uint64_t seed, const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
+                                 tdrn_augment_params *params, float *out_truths, int32_t *out_off, void *stream);
+TDRN_API int tdrn_augment_apply(const tdrn_augment_image *images, const tdrn_augment_params *params, int B, const float *mean,
+                                int S, int to_rgb, float *out, void *stream);
+
 /* PriorBox.forward -- layers/functions/prior_box.py:33-64 (host, double arithmetic, cast to
  * fp32, clamp).  aspect_ratios ragged: ar_count[k] values per map, concatenated in `ars`.
  * out == NULL: returns the number of priors only.  Returns P (>= 0) or a negative error. */

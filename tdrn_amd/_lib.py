@@ -60,6 +60,23 @@ class OpInfo(C.Structure):
                 ("b2", C.c_char * 48), ("y_groups", C.c_int)]
 
 
+class AugmentParams(C.Structure):
+    """tdrn_augment_params (tdrn_hip.h section ii-c): one image's SSDAugmentation decisions."""
+    _fields_ = [("brightness", C.c_float), ("contrast_pre", C.c_float), ("contrast_post", C.c_float), ("saturation", C.c_float),
+                ("hue", C.c_float), ("perm", C.c_int32 * 3), ("canvas_w", C.c_int32), ("canvas_h", C.c_int32),
+                ("img_x", C.c_int32), ("img_y", C.c_int32), ("crop_x0", C.c_int32), ("crop_y0", C.c_int32),
+                ("crop_x1", C.c_int32), ("crop_y1", C.c_int32), ("cropped", C.c_int32), ("mirror", C.c_int32),
+                ("kept", C.c_int32), ("status", C.c_int32)]
+
+
+class AugmentImage(C.Structure):
+    """tdrn_augment_image: a HWC uint8 BGR frame on the device and its size."""
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+AUGMENT_MAX_TRUTHS, AUGMENT_MAX_SIZE = 512, 2048
+AUGMENT_CROP_FALLBACK, AUGMENT_TAPE_EXHAUSTED = 1, 2
+
 OP_KINDS = ("first_conv", "conv", "conv_transpose", "depthwise", "maxpool", "l2norm", "offset_conv", "deform_heads", "other")
 
 _lib = None
@@ -88,6 +105,8 @@ _SIGS = {
     "tdrn_multibox_loss_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "tdrn_multibox_loss_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "tdrn_multibox_loss_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    "tdrn_augment_sample": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_uint64] + [C.c_void_p] * 7),
+    "tdrn_augment_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdrn_prior_box": (C.c_int, [C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tdrn_nms_topk_classes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -296,6 +296,20 @@ int tdrn_multibox_loss_backward(const float *loc, const float *conf, const float
                                          (hipStream_t)stream);
 }
 
+int tdrn_augment_sample(const int32_t *hw, const double *truths, const int32_t *truth_off, int T_total, int max_truths, int B,
+                        uint64_t seed, const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
+                        tdrn_augment_params *params, float *out_truths, int32_t *out_off, void *stream)
+{
+    return launch_augment_sample(hw, truths, truth_off, T_total, max_truths, B, seed, sample_ids, tape, tape_off, params,
+                                 out_truths, out_off, (hipStream_t)stream);
+}
+
+int tdrn_augment_apply(const tdrn_augment_image *images, const tdrn_augment_params *params, int B, const float *mean, int S,
+                       int to_rgb, float *out, void *stream)
+{
+    return launch_augment_apply(images, params, B, mean, S, to_rgb, out, (hipStream_t)stream);
+}
+
 int tdrn_prior_box(int n_maps, const int *feature_maps, double image_size, const double *steps, const double *min_sizes,
                    const double *max_sizes, int n_max_sizes, const int *ar_count, const double *ars, int clip, int flip,
                    float *out)

@@ -255,4 +255,13 @@ int launch_multibox_loss_backward(const float *loc, const float *conf, const flo
                                   const uint8_t *sel, const int32_t *num_pos, const float *grad_loss, int B, int P, int C,
                                   float *grad_loc, float *grad_conf, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// SSDAugmentation on the device (augment.hip; semantics: tdrn_hip.h section ii-c)
+// ---------------------------------------------------------------------------------------------
+int launch_augment_sample(const int32_t *hw, const double *truths, const int32_t *truth_off, int T_total, int max_truths, int B,
+                          uint64_t seed, const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
+                          tdrn_augment_params *params, float *out_truths, int32_t *out_off, hipStream_t s);
+int launch_augment_apply(const tdrn_augment_image *images, const tdrn_augment_params *params, int B, const float *mean, int S,
+                         int to_rgb, float *out, hipStream_t s);
+
 }  // namespace tdrn

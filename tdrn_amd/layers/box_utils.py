@@ -1,4 +1,6 @@
 """decode / center_size / encode and the loss targets (match, refine_match) on the device (layers/box_utils.py of the reference)."""
+from collections import namedtuple
+
 import torch
 
 from .. import _lib
@@ -43,15 +45,28 @@ def _to_device(t, device):
     return t.to(device)
 
 
+PackedTargets = namedtuple("PackedTargets", "truths offsets T_total max_truths")
+PackedTargets.__doc__ = """A batch's truths already on the device, in tdrn_match's layout (SSDAugmentation.batch makes them): truths
+(>= T_total, 5) fp32 rows [x1, y1, x2, y2, label], offsets (B+1) int32 (image b = rows [offsets[b], offsets[b+1])), and two
+HOST bounds: T_total >= offsets[B] and max_truths >= every image's count."""
+
+
 def match_targets(targets, priors, threshold, variances, arm_loc=None):
     """Batched match / refine_match (box_utils.py:81-149) on the device: one call for the whole batch.
 
-    targets: list of B tensors [n_i, 5] (x1, y1, x2, y2, label), as detection_collate gives them, on any device.
+    targets: list of B tensors [n_i, 5] (x1, y1, x2, y2, label), as detection_collate gives them, on any device; or a
+    PackedTargets, whose truths and offsets are used as they are (no copy, nothing read back).
     priors (P, 4) on the GPU; arm_loc (B, P, 4) or None (None: match against the priors; else refine_match against the
     ARM decode).  Returns (loc_t (B, P, 4) fp32, conf_t (B, P) int32) on the priors' device.  No host synchronisation:
     the per-image counts are tensor sizes, and the packed truths and offsets go up through pinned memory."""
     _lib.require_cuda(priors, "priors")
     dev = priors.device
+    if isinstance(targets, PackedTargets):
+        B, P = targets.offsets.numel() - 1, priors.size(0)
+        truths, off = targets.truths.to(dev).float().contiguous(), targets.offsets.to(dev).int().contiguous()
+        total, max_truths = int(targets.T_total), int(targets.max_truths)
+        truths = truths if total else None
+        return _match(truths, off, total, max_truths, B, priors, threshold, variances, arm_loc)
     B, P = len(targets), priors.size(0)
     counts = [int(t.size(0)) for t in targets]
     offs = [0]
@@ -60,20 +75,25 @@ def match_targets(targets, priors, threshold, variances, arm_loc=None):
     rows = [t.reshape(-1, 5).float() for t in targets if t.numel()]
     truths = _to_device(torch.cat([r.to(rows[0].device) for r in rows]).contiguous(), dev) if rows else None
     off = _to_device(torch.tensor(offs, dtype=torch.int32), dev)
+    max_truths = max(counts) if counts else 0
+    return _match(truths, off, offs[-1], max_truths, B, priors, threshold, variances, arm_loc)
+
+
+def _match(truths, off, total, max_truths, B, priors, threshold, variances, arm_loc):
+    dev, P = priors.device, priors.size(0)
     pri = _lib.aligned16(priors.detach().contiguous().float())
     arm = None
     if arm_loc is not None:
         arm = _lib.aligned16(arm_loc.detach().to(dev).reshape(B, P, 4).contiguous().float())
     loc_t = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
     conf_t = torch.empty(B, P, dtype=torch.int32, device=dev)
-    max_truths = max(counts) if counts else 0
     L = _lib.lib()
     nb = L.tdrn_match_workspace_bytes(B, P, max_truths)
     if nb == 0:
         raise _lib.TdrnError(-4 if max_truths > 512 else -1, "match: B=%d P=%d, %d truths in one image (at most 512)"
                              % (B, P, max_truths))
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    _lib.check(L.tdrn_match(_lib.ptr(truths), _lib.ptr(off), offs[-1], max_truths, B, _lib.ptr(pri), P, _lib.ptr(arm),
+    _lib.check(L.tdrn_match(_lib.ptr(truths), _lib.ptr(off), total, max_truths, B, _lib.ptr(pri), P, _lib.ptr(arm),
                             float(threshold), float(variances[0]), float(variances[1]), _lib.ptr(loc_t), _lib.ptr(conf_t),
                             _lib.ptr(ws), nb, _lib.current_stream(dev)), "match")
     return loc_t, conf_t
