@@ -175,7 +175,8 @@ int tdrn_deform_conv_backward_parameters(const float *input, const float *offset
     DeformBwdPlan b;
     TDRN_TRY(deform_bwd_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, b));
     if (!workspace || workspace_bytes < b.total) return TDRN_E_WORKSPACE;
-    if ((long long)N * H * W * deform_bwd_cpg64(b.g) * deformable_group >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    // the same limits as backward_input (32-bit element offsets, its LDS budget): a layer is served by both entries or by neither
+    if (deform_bwd_data_px(b.g) == 0) return TDRN_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
     float *in_nhwc = (float *)(ws + b.o_in);

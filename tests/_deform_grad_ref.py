@@ -104,3 +104,48 @@ def near_decision(off, x_shape, w_shape, stride=1, padding=0, dilation=1, G=1, e
     bad = near(hs) | near(ws)                               # integers include the borders 0 and H / W
     bad = bad.unsqueeze(3).expand(-1, -1, -1, 2, -1, -1)    # both axes of the sample
     return bad.reshape(N, G * 2 * kh * kw, hs.shape[-2], hs.shape[-1])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Shapes of the backward fuzz (tests/test_gpu_train_fuzz.py); tests/test_deform_grad_ref.py asserts on the CPU that they
+# reach the branches of deform_bwd.hip they are meant to reach.
+# ------------------------------------------------------------------------------------------------------------------
+FUZZ_SEEDS = tuple(range(24))
+FUZZ_CPG = (1, 2, 3, 8, 63, 64, 65, 100, 130)        # channels per group: below a wave, a chunk, chunks with a ragged last one
+FUZZ_COUT = (1, 4, 31, 32, 33, 75, 128, 129, 140)    # around the weight kernel's switch (32) and its 128-wide blocks
+FUZZ_OFFSET_SCALE = (0.0, 0.5, 2.0, 6.0)
+
+
+def _schedule(values, n, seed):
+    import numpy as np
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = []
+    while len(out) < n:
+        out += [values[i] for i in rng.permutation(len(values))]
+    return out[:n]
+
+
+def fuzz_shape(seed):
+    """dict(N, Cin, H, W, Cout, k=(kh, kw), stride, pad, dil, G, osc, Ho, Wo, M): test_deform_conv_fuzz_matches_oracle's
+    distribution with the channels per group and Cout run through FUZZ_CPG / FUZZ_COUT.  Wide inputs get small kernels and
+    maps, so the fp64 oracle stays in seconds."""
+    import numpy as np
+    n = len(FUZZ_SEEDS)
+    rng = np.random.Generator(np.random.PCG64(5000 + seed))
+    cpg, Cout = _schedule(FUZZ_CPG, n, 11)[seed], _schedule(FUZZ_COUT, n, 12)[seed]
+    G = int(rng.choice([1, 2, 4, 8]))
+    while G * cpg > 520:
+        G = int(rng.choice([1, 2, 4, 8]))
+    Cin = G * cpg
+    kmax, span = (3, 8) if Cin >= 200 else (5, 13)
+    kh, kw = int(rng.integers(1, kmax + 1)), int(rng.integers(1, kmax + 1))
+    sh, sw = int(rng.integers(1, 3)), int(rng.integers(1, 3))
+    dh, dw = int(rng.integers(1, 3)), int(rng.integers(1, 3))
+    ph, pw = int(rng.integers(0, 3)), int(rng.integers(0, 3))
+    N = int(rng.integers(1, 4))
+    H = int(rng.integers(dh * (kh - 1) + 1, dh * (kh - 1) + 1 + span))
+    W = int(rng.integers(dw * (kw - 1) + 1, dw * (kw - 1) + 1 + span))
+    Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+    Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+    return dict(N=N, Cin=Cin, H=H, W=W, Cout=Cout, k=(kh, kw), stride=(sh, sw), pad=(ph, pw), dil=(dh, dw), G=G, cpg=cpg,
+                osc=float(_schedule(FUZZ_OFFSET_SCALE, n, 13)[seed]), Ho=Ho, Wo=Wo, M=N * Ho * Wo)

@@ -201,3 +201,260 @@ def loc_t_tolerance(refine):
     ulp); the encode's (c_match - c_anchor) / (0.1 * w_anchor) amplifies that ulp of the anchor centre by up to 1 / (0.1 w)
     for a small anchor, so a few elements move by up to ~3e-5 absolute."""
     return (3e-6, 5e-5) if refine else (3e-6, 1e-7)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Seeded case builders of the training fuzz (tests/test_gpu_train_fuzz.py; their claims are asserted on the CPU by
+# tests/test_loss_ref.py).  Ties are made exact, not near: identical rows of conf give bit-identical mining scores in any
+# deterministic implementation, and identical priors give bit-identical IoUs, so select / match_batch stay the oracle with
+# no near-tie exemption.
+# ------------------------------------------------------------------------------------------------------------------
+FAR = np.array([-5.0, -5.0, 0.1, 0.1], F32)               # a prior that overlaps no truth of the unit square
+TRUTH_COUNTS = (0, 1, 64, 65, 256, 257, 511, 512)         # around the 256-truth trips of the staging loops, up to the limit
+CONF_MODES = ("gaussian", "zeros", "random", "zero_score", "neg_inf", "cap")
+PATTERN_GAP = 1e-3                                        # least distance between the scores of two distinct patterns
+
+
+def fuzz_priors(rng, P):
+    """Synthetic center-size priors (test_gpu_fuzz._priors' distribution)."""
+    c = rng.random((P, 2)).astype(F32)
+    wh = (0.02 + 0.3 * rng.random((P, 2))).astype(F32)
+    return np.concatenate([c, wh], 1)
+
+
+def _background_scores(pats):
+    """fp64 mining score of each pattern on a background row: log-sum-exp minus the background logit (the batch max cancels)."""
+    x = pats.astype(np.float64)
+    m = x.max(1, keepdims=True)
+    return np.log(np.exp(x - m).sum(1)) + m[:, 0] - x[:, 0]
+
+
+def _random_patterns(rng, K, C):
+    """K rows whose background scores lie at least PATTERN_GAP apart and at least that far above 0 (the positives' score):
+    the background logit spread over [-2, 2], the other logits N(0, 1)."""
+    for _ in range(100):
+        pats = rng.standard_normal((K, C)).astype(F32)
+        pats[:, 0] = rng.permutation(np.linspace(-2.0, 2.0, K)).astype(F32) if K > 1 else F32(0)
+        s = np.sort(np.concatenate([[0.0], _background_scores(pats)]))
+        if np.diff(s).min() >= 10 * PATTERN_GAP:
+            return pats
+    raise AssertionError("no %d patterns of %d classes with distinct scores" % (K, C))
+
+
+def pattern_conf(rng, B, P, C, K, shares=None, mode="random", num_neg=None):
+    """(conf [B, P, C] fp32, pattern index [B, P]): every row of conf is one of K row patterns, pattern k on about
+    shares[k] of the rows (uniform when None).
+      zeros       K = 1, all logits 0: the zero-initialised head, every background row ties;
+      random      K random patterns (_random_patterns);
+      zero_score  pattern 0 is [0, -200, -200, ...] and every logit of the batch is <= 0: its exps beside the first vanish
+                  against 1 in fp32 and in fp64, so its background score is exactly 0, the positives' score.  With num_neg
+                  (the restatement's num_neg per image) image b gets num_neg[b] // 2 rows of the other patterns, which puts
+                  the boundary inside the score-0 group;
+      neg_inf     random patterns clipped to <= 2 and ONE element of the batch (row 0 of image 0, the last class) set to
+                  1000: every other row's exps underflow to 0 in fp32 and fp64 alike (exp(-998)), score -inf.
+    Returns the pattern index too, so a test can name the tie groups."""
+    assert C >= 2 and K >= 1
+    if mode == "zeros":
+        assert K == 1
+        return np.zeros((B, P, C), F32), np.zeros((B, P), np.int64)
+    pats = _random_patterns(rng, K, C)
+    p = None if shares is None else np.asarray(shares, np.float64) / np.sum(shares)
+    idx = rng.choice(K, size=(B, P), p=p)
+    if mode == "zero_score":
+        pats = pats - np.maximum(pats.max(), F32(0)) - F32(0.5)         # a common shift keeps the scores; all logits < 0
+        pats[0] = F32(-200)
+        pats[0, 0] = F32(0)
+        if num_neg is not None:
+            idx[:] = 0
+            for b in range(B):
+                n_hot = min(int(num_neg[b]) // 2, P)
+                idx[b, rng.choice(P, n_hot, replace=False)] = rng.integers(1, K, n_hot) if K > 1 else 0
+    elif mode == "neg_inf":
+        pats = np.minimum(pats, F32(2))
+    conf = pats[idx].astype(F32)
+    if mode == "neg_inf":
+        conf[0, 0, C - 1] = F32(1000)
+    return np.ascontiguousarray(conf), idx
+
+
+def tiled_priors(base, copies, stride, P=None):
+    """[P, 4]: prior i of base[:stride] at the indices i, i + stride, ..., i + (copies - 1) * stride (stride such as 300 or
+    64 k + 1: the copies fall into other waves and other 256-prior chunks), rows behind copies * stride far away.  Every
+    truth then has `copies` exactly tied best priors, of which the lowest index must win."""
+    base = np.asarray(base, F32)[:stride]
+    if len(base) < stride:
+        base = np.concatenate([base, np.repeat(FAR[None], stride - len(base), 0)])
+    P = copies * stride if P is None else P
+    assert copies >= 2 and P >= copies * stride
+    return np.ascontiguousarray(np.concatenate([np.tile(base, (copies, 1)), np.repeat(FAR[None], P - copies * stride, 0)]).astype(F32))
+
+
+def tiled_arm(rng, B, copies, stride, P):
+    """An ARM input for tiled_priors: equal rows for equal priors and the last two columns 0 (exp(0) = 1 is exact everywhere,
+    so the decoded boxes, and with them the ties, are exact)."""
+    a = np.zeros((B, stride, 4), F32)
+    a[:, :, :2] = (0.3 * rng.standard_normal((B, stride, 2))).astype(F32)
+    out = np.zeros((B, P, 4), F32)
+    out[:, :copies * stride] = np.tile(a, (1, copies, 1))
+    return out
+
+
+def threshold_case(P=520, a=5, b=300):
+    """(priors [P, 4], target [1, 5], a, b): prior A = (0.5, 0.5, 0.5, 0.5) at index a, prior B = (0.375, 0.5, 0.25, 0.5) at
+    index b (another 256-prior chunk), every other prior far away, and the truth [0.25, 0.25, 0.5, 0.75] with label 6.  B is
+    the truth's box (IoU 1, the forced match).  A: inter 0.125, union 0.25 + 0.125 - 0.125, IoU exactly 0.5 (all dyadic): a
+    positive at threshold 0.5, background at nextafter(0.5, 1)."""
+    pri = np.repeat(FAR[None], P, 0)
+    pri[a] = (0.5, 0.5, 0.5, 0.5)
+    pri[b] = (0.375, 0.5, 0.25, 0.5)
+    return pri.astype(F32), np.array([[0.25, 0.25, 0.5, 0.75, 6.0]], F32), a, b
+
+
+def truth_counts(rng, B):
+    """B truth counts: as many of TRUTH_COUNTS as fit (all eight at B >= 8), image 0 never empty, the rest 1..40."""
+    if B >= len(TRUTH_COUNTS):
+        counts = list(TRUTH_COUNTS) + [int(v) for v in rng.integers(1, 41, B - len(TRUTH_COUNTS))]
+        counts = [counts[i] for i in rng.permutation(B)]
+    else:
+        counts = [int(v) for v in rng.choice(TRUTH_COUNTS, B, replace=False)]
+    if counts[0] == 0:
+        j = int(np.argmax(counts))
+        counts[0], counts[j] = counts[j], counts[0]
+    if counts[0] == 0:
+        counts[0] = 1
+    return counts
+
+
+def edge_targets(rng, counts, C, priors):
+    """synth_targets(counts) with, where an image has the rows for it: the TINY truth last (it overlaps no prior and takes
+    prior 0), the box of prior P - 1 before it (its best prior is P - 1, in the last, ragged chunk), and at n >= 12 one box
+    at the rows 1, 3, 5, 7, 9 with labels that differ where C allows (they share a best prior; row 9 wins it)."""
+    targets = synth_targets(rng, len(counts), 1, 1, max(C, 2), counts)
+    last = point_form(priors[-1:])[0]
+    for t in targets:
+        n = len(t)
+        if n >= 12:
+            for k, r in enumerate((3, 5, 7, 9)):
+                t[r, :4] = t[1, :4]
+                t[r, 4] = (t[1, 4] + k + 1) % max(C - 1, 1)
+        if n >= 2:
+            t[n - 1] = np.append(TINY, F32(0))
+        if n >= 3:
+            t[n - 2, :4] = last
+    return targets
+
+
+def fragile_priors(threshold, target, priors, v, arm_loc):
+    """[P] bool: the priors of one image whose conf_t one ulp of the ARM decode's exp can move: the best IoU within 1e-6 of
+    another truth's (exact ties, as of identical truths, move together and do not count) or of the threshold."""
+    target = np.asarray(target, F32).reshape(-1, 5)
+    P = priors.shape[0]
+    if len(target) == 0:
+        return np.zeros(P, bool)
+    boxes = point_form(priors) if arm_loc is None else decode(np.asarray(arm_loc, F32), priors, v)
+    ov = iou(target[:, :4], boxes).astype(np.float64)
+    best = ov.max(0)
+    d = best[None, :] - ov
+    near = ((d > 0) & (d <= 1e-6)).any(0)
+    return near | (np.abs(best - float(F32(threshold))) <= 1e-6)
+
+
+def mining_scores_f32(conf, conf_t):
+    """The device's arithmetic for the mining score ([B, P] fp32): the batch max, correctly rounded fp32 exps summed one
+    after the other in fp32, log, plus the max, minus the target logit; 0 on positives."""
+    B, P = conf_t.shape
+    x = conf.reshape(B * P, -1).astype(F32)
+    g = x.max()
+    s = _exp(x - g).cumsum(1, dtype=F32)[:, -1]
+    with np.errstate(divide="ignore"):
+        sc = (_log(s) + g) - x[np.arange(B * P), conf_t.reshape(-1)]
+    sc[conf_t.reshape(-1) > 0] = 0
+    return sc.reshape(B, P)
+
+
+def select_from_scores(s, conf_t, negpos):
+    """select's rule on given scores [B, P]: sel alone."""
+    B, P = conf_t.shape
+    pos = conf_t > 0
+    sel = pos.astype(np.uint8)
+    for b in range(B):
+        k = min(negpos * int(pos[b].sum()), P - 1)
+        if k == 0:
+            continue
+        neg = np.zeros(P, bool)
+        neg[np.argsort(-s[b], kind="stable")[:k]] = True
+        sel[b][neg & ~pos[b]] = 2
+    return sel
+
+
+FUZZ_SEEDS = tuple(range(32))
+FUZZ_B = (1, 2, 3, 5, 32)
+FUZZ_P = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2049, 6375, 16320)
+FUZZ_C = (2, 3, 21, 81, 201, 1024)
+FUZZ_NEGPOS = (0, 1, 3, 7)
+FUZZ_MAX_ELEMS = 12_000_000                      # B * P * C of a case (the fp64 oracle's arrays)
+_GOLDEN_PRIORS = {6375: "VOC_320", 16320: "VOC_512_RefineDet"}
+
+
+def _schedule(values, n, seed):
+    """n draws that run through permutations of `values`: every value comes up about equally often, whatever n."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = []
+    while len(out) < n:
+        out += [values[i] for i in rng.permutation(len(values))]
+    return out[:n]
+
+
+def fuzz_case(seed, golden_dir):
+    """The drawn case of test_loss_fuzz_matches_restatement[seed]: a dict with B, P, C, negpos, refine, only_loc, mode, tiled
+    (None or (copies, stride)), priors, targets, loc, conf (None with only_loc), arm (None when plain), exact_arm, and the
+    restatement's conf_t of it.  P, B, C and the conf mode each run through every value (_schedule); the rest is drawn."""
+    n = len(FUZZ_SEEDS)
+    rng = np.random.Generator(np.random.PCG64(7000 + seed))
+    B, P, C = _schedule(FUZZ_B, n, 1)[seed], _schedule(FUZZ_P, n, 2)[seed], _schedule(FUZZ_C, n, 3)[seed]
+    mode = _schedule(CONF_MODES, n, 4)[seed]
+    while B * P * C > FUZZ_MAX_ELEMS or (C == 1024 and B * P > 20000):
+        C = FUZZ_C[FUZZ_C.index(C) - 1]
+    only_loc = seed % 8 == 5
+    if only_loc:
+        C, mode = 2, "none"
+    elif P < 63 and mode != "gaussian":           # one or two priors hold no tie group with members on both sides of a boundary
+        mode = "gaussian"
+    # the tie modes need a boundary (negpos > 0); the -inf group is reached only behind the positives' own ranks (negpos > 1)
+    negpos = int(rng.choice({"gaussian": FUZZ_NEGPOS, "none": FUZZ_NEGPOS, "neg_inf": (3, 7), "cap": (7,)}.get(mode, (1, 3, 7))))
+    refine = bool(rng.integers(0, 2))
+    priors = priors_of(_GOLDEN_PRIORS[P], golden_dir) if P in _GOLDEN_PRIORS else fuzz_priors(rng, P)
+    tiled = None
+    if P >= 255 and rng.integers(0, 2):
+        stride = int(rng.choice([s for s in (65, 129, 257, 300) if 2 * s <= P] or [P // 2]))
+        tiled = (P // stride, stride)
+        priors = tiled_priors(priors[rng.permutation(P)[:stride]], tiled[0], stride, P)
+    counts = truth_counts(rng, B)
+    if mode == "cap":
+        counts = [max(c, min(512, max(64, P // 2))) for c in counts]      # negpos * num_pos > P - 1 needs many truths
+    targets = edge_targets(rng, counts, C, priors)
+    arm, exact_arm = None, False
+    if refine:
+        exact_arm = tiled is not None
+        arm = tiled_arm(rng, B, tiled[0], tiled[1], P) if exact_arm else (0.3 * rng.standard_normal((B, P, 4))).astype(F32)
+    loc = (0.5 * rng.standard_normal((B, P, 4))).astype(F32)
+    conf_t = match_batch(0.5, targets, priors, (0.1, 0.2), arm)[1]
+    conf = None
+    if not only_loc:
+        num_neg = np.minimum(negpos * (conf_t > 0).sum(1), P - 1)
+        if mode == "gaussian":
+            conf = (1.5 * rng.standard_normal((B, P, C))).astype(F32)
+        elif mode == "zeros":
+            conf = pattern_conf(rng, B, P, C, 1, mode="zeros")[0]
+        else:
+            K = int(rng.integers(3, 9))
+            shares = rng.random(K) + 0.2
+            conf = pattern_conf(rng, B, P, C, K, shares, "random" if mode == "cap" else mode, num_neg)[0]
+    return dict(seed=seed, B=B, P=P, C=C, negpos=negpos, refine=refine, only_loc=only_loc, mode=mode, tiled=tiled, counts=counts,
+                priors=priors, targets=targets, loc=loc, conf=conf, arm=arm, exact_arm=exact_arm, conf_t=conf_t)
+
+
+def describe(k):
+    return "seed=%d B=%d P=%d C=%d negpos=%d %s%s mode=%s tiled=%r truths=%r" % (
+        k["seed"], k["B"], k["P"], k["C"], k["negpos"], "refine" if k["refine"] else "plain", " only_loc" if k["only_loc"] else "",
+        k["mode"], k["tiled"], k["counts"] if len(k["counts"]) <= 8 else "%d..%d" % (min(k["counts"]), max(k["counts"])))

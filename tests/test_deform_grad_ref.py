@@ -159,3 +159,16 @@ def test_known_answer_exact_integer_is_one_sided():
     want[2, 2] = 1.0
     np.testing.assert_allclose(gx, want, atol=1e-12)
     np.testing.assert_allclose(go, [4.0, 1.0], atol=1e-12)
+
+
+def test_backward_fuzz_shapes_reach_the_kernels_branches():
+    """The shapes of test_gpu_train_fuzz.test_deform_backward_fuzz_matches_oracle: every channels-per-group and Cout value,
+    every offset scale, pixel counts M below the 128 of one weight split and above it with a ragged last 32-pixel step."""
+    S = [gref.fuzz_shape(seed) for seed in gref.FUZZ_SEEDS]
+    assert {s["cpg"] for s in S} == set(gref.FUZZ_CPG) and {s["Cout"] for s in S} == set(gref.FUZZ_COUT)
+    assert {s["osc"] for s in S} == set(gref.FUZZ_OFFSET_SCALE) and {s["G"] for s in S} == {1, 2, 4, 8}
+    assert all(s["Cin"] == s["G"] * s["cpg"] <= 520 and s["Ho"] >= 1 and s["Wo"] >= 1 for s in S)
+    assert sum(s["M"] < 128 for s in S) >= 4 and sum(s["M"] > 128 and s["M"] % 32 != 0 for s in S) >= 4
+    assert any(s["M"] % 16 != 0 for s in S)                          # a ragged last pixel tile of the data kernel
+    assert any(s["cpg"] > 64 and s["G"] > 1 for s in S)              # several groups of more than one chunk each
+    assert max(s["N"] * s["Cin"] * s["k"][0] * s["k"][1] * s["Ho"] * s["Wo"] for s in S) <= 4_000_000    # the oracle's column tensor

@@ -122,6 +122,28 @@ def test_philox_is_deterministic_and_independent_of_the_batch():
         assert np.array_equal(x1[b], R.apply(imgs[b], p, 320, MEAN, to_rgb=True)), b
 
 
+def _check_sample_invariants(p, hw, target, r, i):
+    """The reference's invariants on one image's decisions p (a params_to_dicts record) and moved boxes r, for a frame of
+    hw = (h, w) with the truths `target`."""
+    h, w = hw
+    cw, ch = p["canvas_w"], p["canvas_h"]
+    x0, y0, x1, y1 = p["crop"]
+    assert cw >= w and ch >= h and p["img_x"] + w <= cw and p["img_y"] + h <= ch, i
+    if p["cropped"]:
+        ww, hh = x1 - x0, y1 - y0                 # int rect of a real w x h: |(x1 - x0) - w| < 1
+        assert ww + 1 > 0.3 * cw and hh + 1 > 0.3 * ch and x1 <= cw and y1 <= ch, i
+        assert (hh + 1) / max(ww - 1, 1e-9) >= 0.5 and (hh - 1) / (ww + 1) <= 2, i
+        if cw - ww >= 2:                          # then W - w >= 1 and left = uniform(W - w, 1) >= 1
+            assert x0 >= 1, i
+        if ch - hh >= 2:
+            assert y0 >= 1, i
+        assert 1 <= p["kept"] <= len(target), i
+    else:
+        assert (x0, y0, x1, y1) == (0, 0, cw, ch) and p["kept"] == len(target), i
+    assert len(r) == p["kept"] and (r[:, :4] >= 0).all() and (r[:, :4] <= 1).all(), i
+    assert (r[:, 0] <= r[:, 2]).all() and (r[:, 1] <= r[:, 3]).all(), i
+
+
 @gpu
 def test_philox_invariants_and_rates_against_the_reference():
     n = 20000
@@ -133,24 +155,7 @@ def test_philox_invariants_and_rates_against_the_reference():
     ps = params_to_dicts(params)
     rows = _rows(packed)
     for i in range(n):
-        p, (h, w) = ps[i], hw[i]
-        cw, ch = p["canvas_w"], p["canvas_h"]
-        x0, y0, x1, y1 = p["crop"]
-        assert cw >= w and ch >= h and p["img_x"] + w <= cw and p["img_y"] + h <= ch, i
-        if p["cropped"]:
-            ww, hh = x1 - x0, y1 - y0                 # int rect of a real w x h: |(x1 - x0) - w| < 1
-            assert ww + 1 > 0.3 * cw and hh + 1 > 0.3 * ch and x1 <= cw and y1 <= ch, i
-            assert (hh + 1) / max(ww - 1, 1e-9) >= 0.5 and (hh - 1) / (ww + 1) <= 2, i
-            if cw - ww >= 2:                          # then W - w >= 1 and left = uniform(W - w, 1) >= 1
-                assert x0 >= 1, i
-            if ch - hh >= 2:
-                assert y0 >= 1, i
-            assert 1 <= p["kept"] <= len(targets[i]), i
-        else:
-            assert (x0, y0, x1, y1) == (0, 0, cw, ch) and p["kept"] == len(targets[i]), i
-        r = rows[i]
-        assert len(r) == p["kept"] and (r[:, :4] >= 0).all() and (r[:, :4] <= 1).all(), i
-        assert (r[:, 0] <= r[:, 2]).all() and (r[:, 1] <= r[:, 3]).all(), i
+        _check_sample_invariants(ps[i], hw[i], targets[i], rows[i], i)
     # rates: the reference's own decision code (the restatement) on numpy's legacy RandomState, 4000 samples
     m = 4000
     ref = [R.sample(w, h, t[:, :4], t[:, 4], np.random.RandomState(90000 + i))[0]

@@ -633,3 +633,146 @@ def test_preprocess_guarded():
         out8.check("preprocess_u8 k=%d" % k, full=False)        # (uint8 values may equal a sentinel byte: compared bitwise below)
         _assert_same_bits(out.t, want, "preprocess k=%d" % k)
         _assert_same_bits(out8.t, want8, "preprocess_u8 k=%d" % k)
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. the training losses (tdrn_hip.h ii-b): tdrn_match, tdrn_multibox_loss_forward / _backward, tdrn_encode
+# ---------------------------------------------------------------------------------------------
+def _loss_inputs(B, P, Cn, refine):
+    import _loss_ref as R
+    r = np.random.Generator(np.random.PCG64(100 * B + Cn + (7 if refine else 0)))
+    counts = [9, 0, 40][:B]
+    targets = R.synth_targets(r, B, 1, 1, max(Cn, 2), counts)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return dict(truths=t(np.concatenate(targets)), off=t(off), T=int(off[-1]), Tmax=max(counts), pri=t(_priors(P, P + B)),
+                arm=t((0.3 * r.standard_normal((B, P, 4))).astype(np.float32)) if refine else None,
+                loc=t((0.5 * r.standard_normal((B, P, 4))).astype(np.float32)),
+                conf=t((1.5 * r.standard_normal((B, P, Cn))).astype(np.float32)),
+                gloss=torch.tensor([0.7, 1.3], device=DEV))
+
+
+def _loss_calls(d, B, P, Cn, o, only_loc=False):
+    """tdrn_match, the forward and the backward on the output buffers o (a dict of tensors), workspaces of exactly the queried size"""
+    lib = _lib.lib()
+    s = _lib.current_stream(DEV)
+    conf = None if only_loc else d["conf"]
+    _lib.check(lib.tdrn_match(_lib.ptr(d["truths"]), _lib.ptr(d["off"]), d["T"], d["Tmax"], B, _lib.ptr(d["pri"]), P, _lib.ptr(d["arm"]),
+                              0.5, 0.1, 0.2, _lib.ptr(o["loc_t"]), _lib.ptr(o["conf_t"]), _lib.ptr(o["ws_match"]), o["ws_match"].numel(), s),
+               "match")
+    _lib.check(lib.tdrn_multibox_loss_forward(_lib.ptr(d["loc"]), _lib.ptr(conf), _lib.ptr(o["loc_t"]), _lib.ptr(o["conf_t"]), B, P,
+                                              0 if only_loc else Cn, 3, _lib.ptr(o["loss"]), _lib.ptr(o["sel"]), _lib.ptr(o["num_pos"]),
+                                              _lib.ptr(o["ws_loss"]), o["ws_loss"].numel(), s), "loss forward")
+    _lib.check(lib.tdrn_multibox_loss_backward(_lib.ptr(d["loc"]), _lib.ptr(conf), _lib.ptr(o["loc_t"]), _lib.ptr(o["conf_t"]),
+                                               _lib.ptr(o["sel"]), _lib.ptr(o["num_pos"]), _lib.ptr(d["gloss"]), B, P, 0 if only_loc else Cn,
+                                               _lib.ptr(o["grad_loc"]), None if only_loc else _lib.ptr(o["grad_conf"]), s), "loss backward")
+
+
+@gpu
+@pytest.mark.parametrize("refine", [False, True], ids=["plain", "refine"])
+@pytest.mark.parametrize("B,P,Cn", [(1, 257, 3), (3, 1025, 21)])
+def test_loss_entries_guarded(B, P, Cn, refine):
+    lib = _lib.lib()
+    d = _loss_inputs(B, P, Cn, refine)
+    nm = lib.tdrn_match_workspace_bytes(B, P, d["Tmax"])
+    assert nm > 0
+    shapes = {"loc_t": ((B, P, 4), torch.float32), "conf_t": ((B, P), torch.int32), "sel": ((B, P), torch.uint8),
+              "num_pos": ((B,), torch.int32), "loss": ((2,), torch.float32), "grad_loc": ((B, P, 4), torch.float32),
+              "grad_conf": ((B, P, Cn), torch.float32)}
+    vec16 = ("loc_t", "grad_loc")                  # read / written as 16-byte vectors; the others need their element alignment only
+    for only_loc in (False, True):
+        nl = lib.tdrn_multibox_loss_workspace_bytes(B, P, 0 if only_loc else Cn)
+        assert nl > 0
+        want = {n: _plain(sh, dt) for n, (sh, dt) in shapes.items()}
+        want.update(ws_match=_plain((nm,), torch.uint8), ws_loss=_plain((nl,), torch.uint8))
+        _loss_calls(d, B, P, Cn, want, only_loc)
+        torch.cuda.synchronize()
+        assert int(want["num_pos"].sum()) > 0 and (only_loc or int((want["sel"] == 2).sum()) > 0)
+        for k in OFFSETS:
+            g = {n: Guarded(sh, dt, offset=(16 * k if n in vec16 else 2 * k - 1 if n == "sel" else 4 * (k - 3)))
+                 for n, (sh, dt) in shapes.items()}                                   # sel at an odd byte, the rest at 4 or 20 bytes
+            wsm, wsl = Guarded(dtype=torch.uint8, nbytes=nm), Guarded(dtype=torch.uint8, nbytes=nl)
+            o = {n: v.t for n, v in g.items()}
+            o.update(ws_match=wsm.t, ws_loss=wsl.t)
+            _loss_calls(d, B, P, Cn, o, only_loc)
+            tag = "loss B=%d P=%d C=%d %s%s k=%d" % (B, P, Cn, "refine" if refine else "plain", " only_loc" if only_loc else "", k)
+            for n, v in g.items():
+                partly = n == "sel" or (only_loc and n in ("loss", "grad_conf"))      # (sel: bytes at an odd offset, compared below)
+                v.check("%s %s" % (tag, n), full=not partly)
+            wsm.check(tag + " match workspace", full=False)
+            wsl.check(tag + " loss workspace", full=False)
+            for n in shapes:
+                if only_loc and n in ("loss", "grad_conf"):
+                    continue
+                _assert_same_bits(g[n].t, want[n], "%s %s" % (tag, n))
+            if only_loc:                           # conf NULL: loss_out[1] and grad_conf are left as they were
+                words = g["loss"].t.view(torch.int32)
+                assert int(words[1]) == SENTINEL and int(words[0]) != SENTINEL, tag
+                assert int(words[0]) == int(want["loss"].view(torch.int32)[0]), tag
+                assert bool((g["grad_conf"].t.view(torch.int32) == SENTINEL).all()), tag
+
+
+@gpu
+def test_encode_guarded():
+    import _loss_ref as R
+    P = 1025
+    r = np.random.Generator(np.random.PCG64(12))
+    pri = torch.from_numpy(_priors(P, 12)).to(DEV)
+    matched = torch.from_numpy(R.synth_targets(r, 1, 1, 1, 21, [P])[0][:, :4].copy()).to(DEV)
+    lib = _lib.lib()
+    s = _lib.current_stream(DEV)
+    want = _plain((P, 4))
+    _lib.check(lib.tdrn_encode(_lib.ptr(matched), _lib.ptr(pri), P, 0.1, 0.2, _lib.ptr(want), s))
+    for k in OFFSETS:
+        o = Guarded((P, 4), offset=4 * k)
+        _lib.check(lib.tdrn_encode(_lib.ptr(matched), _lib.ptr(pri), P, 0.1, 0.2, o.ptr(), s))
+        o.check("encode k=%d" % k)
+        _assert_same_bits(o.t, want, "encode k=%d" % k)
+    u = Guarded((P, 4), offset=4)                                  # not a 16-byte address: refused on the host, nothing written
+    assert lib.tdrn_encode(_lib.ptr(matched), _lib.ptr(pri), P, 0.1, 0.2, u.ptr(), s) == -1
+    torch.cuda.synchronize()
+    assert bool((u.raw.view(torch.int32) == SENTINEL).all())
+
+
+@gpu
+@pytest.mark.parametrize("refine", [False, True], ids=["plain", "refine"])
+def test_match_clamps_offsets_that_break_the_promise(refine):
+    """tdrn_hip.h: 'offsets that break the promise are clamped, never followed out of bounds'.  The truths are a view INSIDE a
+    larger NaN-filled allocation, so a read that did follow a bad offset lands in mapped memory and shows as NaN or as a changed
+    result, not as a fault."""
+    import _loss_ref as R
+    lib = _lib.lib()
+    s = _lib.current_stream(DEV)
+    B, P, counts, Tmax, pad = 3, 1025, [20, 30, 25], 30, 600
+    T = sum(counts)
+    r = np.random.Generator(np.random.PCG64(21))
+    rows = np.concatenate(R.synth_targets(r, B, 1, 1, 21, counts))
+    big = torch.full(((T + 2 * pad) * 5,), float("nan"), device=DEV)
+    truths = big[pad * 5:(pad + T) * 5].view(T, 5)
+    truths.copy_(torch.from_numpy(rows))
+    pri = torch.from_numpy(_priors(P, 21)).to(DEV)
+    arm = torch.from_numpy((0.3 * r.standard_normal((B, P, 4))).astype(np.float32)).to(DEV) if refine else None
+    nb = lib.tdrn_match_workspace_bytes(B, P, Tmax)
+
+    def run(off, loc_t, conf_t, ws):
+        off_d = torch.tensor(off, dtype=torch.int32, device=DEV)
+        _lib.check(lib.tdrn_match(_lib.ptr(truths), _lib.ptr(off_d), T, Tmax, B, _lib.ptr(pri), P, _lib.ptr(arm), 0.5, 0.1, 0.2,
+                                  _lib.ptr(loc_t), _lib.ptr(conf_t), _lib.ptr(ws), nb, s), "match")
+        torch.cuda.synchronize()
+    want_l, want_c = _plain((B, P, 4)), _plain((B, P), torch.int32)
+    run([0, 20, 50, 75], want_l, want_c, _plain((nb,), torch.uint8))
+    assert bool(torch.isfinite(want_l).all()) and int((want_c[0] > 0).sum()) > 0
+    bad_offsets = {"decreasing": [0, 20, 17, 75], "beyond T_total": [0, 20, T + 150, T + 400],
+                   "count above max_truths": [0, 20, 20 + Tmax + 25, 75]}
+    for name, off in bad_offsets.items():
+        loc_t, conf_t = Guarded((B, P, 4), offset=16), Guarded((B, P), torch.int32, offset=4)
+        ws = Guarded(dtype=torch.uint8, nbytes=nb)
+        run(off, loc_t.t, conf_t.t, ws.t)
+        loc_t.check("match loc_t, truth_off %s" % name)
+        conf_t.check("match conf_t, truth_off %s" % name)
+        ws.check("match workspace, truth_off %s" % name, full=False)
+        assert bool(torch.isfinite(loc_t.t).all()), "truth_off %s: a truth was read from outside the buffer" % name
+        assert int(conf_t.t.min()) >= 0 and int(conf_t.t.max()) <= 20, name
+        _assert_same_bits(loc_t.t[0], want_l[0], "image 0 loc_t, truth_off %s" % name)
+        _assert_same_bits(conf_t.t[0], want_c[0], "image 0 conf_t, truth_off %s" % name)
+    assert bool(torch.isnan(big[:pad * 5]).all()) and bool(torch.isnan(big[(pad + T) * 5:]).all())
