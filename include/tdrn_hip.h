@@ -310,6 +310,62 @@ TDRN_API int tdrn_augment_sample(const int32_t *hw, const double *truths, const 
 TDRN_API int tdrn_augment_apply(const tdrn_augment_image *images, const tdrn_augment_params *params, int B, const float *mean,
                                 int S, int to_rgb, float *out, void *stream);
 
+/* ========================================================================================
+ * (ii-d) Training augmentation for TRN pairs, pairSSDAugmentation on the device -- replaces, for a batch of raw frames,
+ *     VOCDetection.pull_translational_item's translated second frame and truths            data/voc0712.py:400-458
+ *     pairSSDAugmentation(size, mean) = pairPhotometricDistort, pairExpand(mean), pairRandomSampleCrop, pairRandomMirror,
+ *     then per frame percent coordinates, cv2.resize and the mean                          utils/augmentations.py:637-689
+ *   in two launches and with no host synchronisation.  A pair is a frame (frame 0) and a second frame (frame 1) of the same
+ *   size under shared decisions; everything section (ii-c) says holds, and on top of it:
+ *   - Translation (only when the caller supplies no second frame, for an image with truths), r = max_trans_ratio: for
+ *     attempt a = 1, 2, 3 draw u_x = rand(), then u_y = rand(); x_trans = (-r / a) + ((u_x * 2) * r) / a, y_trans alike;
+ *     add x_trans to columns 0 and 2 of the truths and y_trans to columns 1 and 3; the attempt is accepted when every box
+ *     centre (x1 + x2) / 2, (y1 + y2) / 2 lies strictly inside (0, 1) on both axes.  On accept the pixel shift is
+ *     trans_x = int(x_trans * W), trans_y = int(y_trans * H) (truncated toward zero) while the boxes move by the fraction
+ *     itself -- the reference's mismatch, kept -- and the moved truths are clipped to [0, 1].  After three failures frame 1
+ *     is a copy of frame 0, its truths are frame 0's, unclipped, and status gets TDRN_AUGMENT_TRANS_FALLBACK;
+ *   - frame 1 is cv2.warpAffine(frame 0, [[1,0,tx],[0,1,ty]]) on uint8: dst(x, y) = src(x - tx, y - ty), 0 outside.  The
+ *     black border belongs to the frame: it goes through the photometric distortion like any pixel, and only places
+ *     outside the frame's rect on the expand canvas get the mean;
+ *   - the photometric, expand and mirror draws and their order are section (ii-c)'s; one set of values serves both frames;
+ *     canvas and mirror width come from frame 0;
+ *   - a crop trial is kept when some index i has the centre of box i of frame 0 AND the centre of box i of frame 1 strictly
+ *     inside the int rect; that one mask selects the kept rows of both frames (the same count), each set is clamped to the
+ *     rect and shifted.
+ *   Deviations, by design: those of (ii-c); an image with no truths gets no translation either (attempts = 0, frame 1 =
+ *   frame 0); Philox: the shared decisions use the slots of tdrn_augment_sample, so for one (seed, sample id) the embedded
+ *   record's photometric, expand and mirror fields equal that entry's; the translation attempts take slots 16-21 (attempt a:
+ *   16 + 2(a-1) for u_x, the next for u_y), which tdrn_augment_sample never draws.  Tape mode replays the translation's
+ *   rand() values first (two per attempt made), then the chain's.
+ *
+ * tdrn_augment_pair_sample: one launch.  hw, truths, truth_off, T_total, max_truths, B, seed, sample_ids, tape, tape_off as
+ *   tdrn_augment_sample.  truths_t NULL: frame 1's truths are made by the translation rule.  truths_t (T_total,5) fp64
+ *   DEVICE: frame 1's rows under the same offsets (the same count per image), used as they are; no translation, no
+ *   translation draws, attempts = 0.  max_trans_ratio outside [0, 1) -> TDRN_E_ARG.  Writes params (B) pair records and two
+ *   packed row sets out_truths, out_truths_t (T_total,5) fp32 behind the one out_off (B+1) int32.
+ * tdrn_augment_pair_apply: one launch.  images as tdrn_augment_apply.  images_t NULL: frame 1 is frame 0 read at
+ *   (x - trans_x, y - trans_y), 0 outside.  images_t (B) DEVICE table: the second frames (the same sizes; a pixel outside a
+ *   smaller one reads as 0) and trans_x, trans_y are ignored.  out, out_t (B,3,S,S) fp32, both fully overwritten.  Only
+ *   pixels inside a frame are read, whatever the records say.  Limits and errors as tdrn_augment_apply.
+ *   No allocation, no host synchronisation, no workspace in either entry.
+ * ====================================================================================== */
+#define TDRN_AUGMENT_TRANS_FALLBACK 4    /* status bit: three translation attempts failed, frame 1 is a copy */
+typedef struct {
+    tdrn_augment_params base;        /* the shared decisions; kept counts either frame's rows */
+    double shift_x, shift_y;         /* the accepted x_trans, y_trans (fractions added to the truths), else 0 */
+    int32_t trans_x, trans_y;        /* the pixel shift int(x_trans * w), int(y_trans * h), else 0 */
+    int32_t attempts;                /* translation attempts made: 1-3; 0 when frame 1 was supplied or there are no truths */
+    int32_t reserved;
+} tdrn_augment_pair_params;
+TDRN_API int tdrn_augment_pair_sample(const int32_t *hw, const double *truths, const double *truths_t, const int32_t *truth_off,
+                                      int T_total, int max_truths, int B, double max_trans_ratio, uint64_t seed,
+                                      const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
+                                      tdrn_augment_pair_params *params, float *out_truths, float *out_truths_t,
+                                      int32_t *out_off, void *stream);
+TDRN_API int tdrn_augment_pair_apply(const tdrn_augment_image *images, const tdrn_augment_image *images_t,
+                                     const tdrn_augment_pair_params *params, int B, const float *mean, int S, int to_rgb,
+                                     float *out, float *out_t, void *stream);
+
 /* PriorBox.forward -- layers/functions/prior_box.py:33-64 (host, double arithmetic, cast to
  * fp32, clamp).  aspect_ratios ragged: ar_count[k] values per map, concatenated in `ars`.
  * out == NULL: returns the number of priors only.  Returns P (>= 0) or a negative error. */

@@ -74,8 +74,14 @@ class AugmentImage(C.Structure):
     _fields_ = [("data", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class AugmentPairParams(C.Structure):
+    """tdrn_augment_pair_params (tdrn_hip.h section ii-d): the shared decisions of a pair and frame 1's translation."""
+    _fields_ = [("base", AugmentParams), ("shift_x", C.c_double), ("shift_y", C.c_double), ("trans_x", C.c_int32),
+                ("trans_y", C.c_int32), ("attempts", C.c_int32), ("reserved", C.c_int32)]
+
+
 AUGMENT_MAX_TRUTHS, AUGMENT_MAX_SIZE = 512, 2048
-AUGMENT_CROP_FALLBACK, AUGMENT_TAPE_EXHAUSTED = 1, 2
+AUGMENT_CROP_FALLBACK, AUGMENT_TAPE_EXHAUSTED, AUGMENT_TRANS_FALLBACK = 1, 2, 4
 
 OP_KINDS = ("first_conv", "conv", "conv_transpose", "depthwise", "maxpool", "l2norm", "offset_conv", "deform_heads", "other")
 
@@ -107,6 +113,8 @@ _SIGS = {
     "tdrn_multibox_loss_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 3),
     "tdrn_augment_sample": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_uint64] + [C.c_void_p] * 7),
     "tdrn_augment_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdrn_augment_pair_sample": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_double, C.c_uint64] + [C.c_void_p] * 8),
+    "tdrn_augment_pair_apply": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3),
     "tdrn_prior_box": (C.c_int, [C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tdrn_nms_topk_classes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

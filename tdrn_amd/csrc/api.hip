@@ -311,6 +311,22 @@ int tdrn_augment_apply(const tdrn_augment_image *images, const tdrn_augment_para
     return launch_augment_apply(images, params, B, mean, S, to_rgb, out, (hipStream_t)stream);
 }
 
+int tdrn_augment_pair_sample(const int32_t *hw, const double *truths, const double *truths_t, const int32_t *truth_off,
+                             int T_total, int max_truths, int B, double max_trans_ratio, uint64_t seed, const int64_t *sample_ids,
+                             const double *tape, const int32_t *tape_off, tdrn_augment_pair_params *params, float *out_truths,
+                             float *out_truths_t, int32_t *out_off, void *stream)
+{
+    return launch_augment_pair_sample(hw, truths, truths_t, truth_off, T_total, max_truths, B, max_trans_ratio, seed, sample_ids,
+                                      tape, tape_off, params, out_truths, out_truths_t, out_off, (hipStream_t)stream);
+}
+
+int tdrn_augment_pair_apply(const tdrn_augment_image *images, const tdrn_augment_image *images_t,
+                            const tdrn_augment_pair_params *params, int B, const float *mean, int S, int to_rgb, float *out,
+                            float *out_t, void *stream)
+{
+    return launch_augment_pair_apply(images, images_t, params, B, mean, S, to_rgb, out, out_t, (hipStream_t)stream);
+}
+
 int tdrn_prior_box(int n_maps, const int *feature_maps, double image_size, const double *steps, const double *min_sizes,
                    const double *max_sizes, int n_max_sizes, const int *ar_count, const double *ars, int clip, int flip,
                    float *out)

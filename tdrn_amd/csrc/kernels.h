@@ -264,4 +264,14 @@ int launch_augment_sample(const int32_t *hw, const double *truths, const int32_t
 int launch_augment_apply(const tdrn_augment_image *images, const tdrn_augment_params *params, int B, const float *mean, int S,
                          int to_rgb, float *out, hipStream_t s);
 
+// pairSSDAugmentation on the device (augment_pair.hip; semantics: tdrn_hip.h section ii-d)
+int launch_augment_pair_sample(const int32_t *hw, const double *truths, const double *truths_t, const int32_t *truth_off,
+                               int T_total, int max_truths, int B, double max_trans_ratio, uint64_t seed,
+                               const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
+                               tdrn_augment_pair_params *params, float *out_truths, float *out_truths_t, int32_t *out_off,
+                               hipStream_t s);
+int launch_augment_pair_apply(const tdrn_augment_image *images, const tdrn_augment_image *images_t,
+                              const tdrn_augment_pair_params *params, int B, const float *mean, int S, int to_rgb, float *out,
+                              float *out_t, hipStream_t s);
+
 }  // namespace tdrn

@@ -1,5 +1,5 @@
-"""SSDAugmentation on the device (utils/augmentations.py:618-635 of the reference) through libtdrn_hip.so (tdrn_hip.h section
-ii-c).
+"""SSDAugmentation and pairSSDAugmentation on the device (utils/augmentations.py:618-689 of the reference) through
+libtdrn_hip.so (tdrn_hip.h sections ii-c and ii-d).
 
 Raw uint8 BGR frames go in; out come the network input (B, 3, S, S) fp32 and the packed truths that MultiBoxLoss /
 RefineMultiBoxLoss consume (PackedTargets), with no host synchronisation in between.  The semantics are the reference's,
@@ -129,3 +129,159 @@ class SSDAugmentation(object):
         k = int(packed.offsets[1])
         rows = packed.truths[:k]
         return x[0].permute(1, 2, 0), rows[:, :4], rows[:, 4]
+
+
+# ---------------------------------------------------------------------------------------------- TRN training pairs
+PAIR_PARAMS_BYTES = C.sizeof(_lib.AugmentPairParams)
+
+
+def pair_params_to_dicts(params):
+    """Decode a (B, PAIR_PARAMS_BYTES) uint8 tensor of tdrn_augment_pair_params records (synchronises when it is on the
+    device): the embedded record's fields as params_to_dicts gives them, plus shift_x, shift_y, trans_x, trans_y, attempts."""
+    raw = params.detach().cpu().contiguous().numpy().tobytes()
+    out = []
+    for b in range(len(raw) // PAIR_PARAMS_BYTES):
+        q = _lib.AugmentPairParams.from_buffer_copy(raw[b * PAIR_PARAMS_BYTES:(b + 1) * PAIR_PARAMS_BYTES])
+        d = {k: getattr(q.base, k) for k, _ in q.base._fields_}
+        d["perm"] = tuple(q.base.perm)
+        d["crop"] = (q.base.crop_x0, q.base.crop_y0, q.base.crop_x1, q.base.crop_y1)
+        for k in ("shift_x", "shift_y", "trans_x", "trans_y", "attempts"):
+            d[k] = getattr(q, k)
+        out.append(d)
+    return out
+
+
+def _image_table(images, dev, what):
+    tab = (_lib.AugmentImage * len(images))()
+    for b, im in enumerate(images):
+        _lib.require_cuda(im, "%s[%d]" % (what, b))
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.size(2) != 3 or not im.is_contiguous():
+            raise ValueError("augment: %s[%d] must be a contiguous uint8 (H, W, 3) tensor" % (what, b))
+        tab[b].data, tab[b].h, tab[b].w = im.data_ptr(), im.size(0), im.size(1)
+    return _to_device(_host_bytes(tab), dev)
+
+
+class PairSSDAugmentation(object):
+    """The reference's pairSSDAugmentation(size, mean) together with VOCDetection.pull_translational_item's translated second
+    frame (tdrn_hip.h section ii-d), batched on the GPU: what train_trn.py's VIDDETtrans loader and pair_collate hand to
+    static_net(images_ori) and net(images_trans).
+
+    batch(images, targets, sample_ids, seed) takes what SSDAugmentation.batch takes and returns (x_ori, x_trans, packed_ori,
+    packed_trans) in pair_collate's order: two (B, 3, S, S) fp32 inputs and two PackedTargets that share one offset tensor.
+    With images_t / targets_t the caller supplies the second frames and their truths (the same sizes and counts) and no
+    translation is drawn; without them the second frame is the first, translated by at most max_trans_ratio of its size.
+    A sample's result depends on (seed, sample id) alone.
+
+    __call__(img_pair, boxes_pair, labels_pair) is the one-pair convenience with the reference's signature: two frames in
+    (a None second frame is translated here), device tensors out ([img, img_t] (S, S, 3) fp32 BGR, [boxes, boxes_t],
+    [labels, labels_t]); unlike batch it synchronises to learn the kept count."""
+
+    def __init__(self, size=300, mean=(104, 117, 123), seed=0, max_trans_ratio=0.1):
+        self.size = int(size)
+        self.mean = mean
+        self.seed = int(seed)
+        self.max_trans_ratio = float(max_trans_ratio)
+        if not 0.0 <= self.max_trans_ratio < 1.0:
+            raise ValueError("augment: max_trans_ratio %r is outside [0, 1)" % (max_trans_ratio,))
+        self._mean = (C.c_float * 3)(*[float(m) for m in mean])
+        self._calls = itertools.count()
+
+    def sample(self, hw, targets, device, sample_ids=None, seed=None, tape=None, targets_t=None):
+        """The decisions and both frames' moved boxes: (params (B, PAIR_PARAMS_BYTES) uint8, PackedTargets of frame 0,
+        PackedTargets of frame 1).  Arguments as SSDAugmentation.sample; targets_t: frame 1's truths, or None to translate."""
+        B = len(hw)
+        if B == 0 or len(targets) != B:
+            raise ValueError("augment: %d images and %d targets" % (B, len(targets)))
+        counts = [int(t.reshape(-1, 5).size(0)) for t in targets]
+        if targets_t is not None:
+            counts_t = [int(t.reshape(-1, 5).size(0)) for t in targets_t]
+            if counts_t != counts:
+                raise ValueError("augment: the second frames' truth counts %r differ from the first's %r" % (counts_t, counts))
+        offs = np.zeros(B + 1, np.int32)
+        offs[1:] = np.cumsum(counts)
+        T, Tmax = int(offs[-1]), max(counts)
+        if Tmax > _lib.AUGMENT_MAX_TRUTHS:
+            raise _lib.TdrnError(-4, "augment: %d truths in one image (at most %d)" % (Tmax, _lib.AUGMENT_MAX_TRUTHS))
+
+        def pack(ts):
+            rows = [t.reshape(-1, 5).to(torch.float64) for t in ts if t.numel()]
+            return _to_device(torch.cat([r.to(rows[0].device) for r in rows]).contiguous(), device) if rows else None
+        truths = pack(targets)
+        truths_t = pack(targets_t) if targets_t is not None else None
+        off = _to_device(torch.from_numpy(offs), device)
+        hw_t = _to_device(torch.tensor([[int(h), int(w)] for h, w in hw], dtype=torch.int32), device)
+        ids = tp = tp_off = None
+        if tape is not None:
+            lens = np.zeros(B + 1, np.int32)
+            lens[1:] = np.cumsum([len(t) for t in tape])
+            tp = _to_device(torch.from_numpy(np.concatenate([np.asarray(t, np.float64) for t in tape] + [np.zeros(1)])), device)
+            tp_off = _to_device(torch.from_numpy(lens), device)
+        else:
+            if sample_ids is None:
+                raise ValueError("augment: sample_ids (with seed) or a tape is needed")
+            ids = torch.as_tensor(sample_ids, dtype=torch.int64).reshape(-1)
+            if ids.numel() != B:
+                raise ValueError("augment: %d sample ids for %d images" % (ids.numel(), B))
+            ids = _to_device(ids.contiguous(), device)
+        params = torch.empty(B, PAIR_PARAMS_BYTES, dtype=torch.uint8, device=device)
+        out_truths = torch.empty(max(T, 1), 5, dtype=torch.float32, device=device)
+        out_truths_t = torch.empty(max(T, 1), 5, dtype=torch.float32, device=device)
+        out_off = torch.empty(B + 1, dtype=torch.int32, device=device)
+        s = self.seed if seed is None else int(seed)
+        _lib.check(_lib.lib().tdrn_augment_pair_sample(_lib.ptr(hw_t), _lib.ptr(truths), _lib.ptr(truths_t), _lib.ptr(off), T,
+                                                       Tmax, B, self.max_trans_ratio, s & 0xFFFFFFFFFFFFFFFF, _lib.ptr(ids),
+                                                       _lib.ptr(tp), _lib.ptr(tp_off), _lib.ptr(params), _lib.ptr(out_truths),
+                                                       _lib.ptr(out_truths_t), _lib.ptr(out_off),
+                                                       _lib.current_stream(device)), "augment pair sample")
+        return params, PackedTargets(out_truths, out_off, T, Tmax), PackedTargets(out_truths_t, out_off, T, Tmax)
+
+    def apply(self, images, params, images_t=None, to_rgb=True, out=None, out_t=None):
+        """The pixels of both frames: two (B, 3, S, S) fp32 tensors from the frames and their pair records."""
+        B = len(images)
+        dev = images[0].device
+        tab = _image_table(images, dev, "images")
+        tab_t = None
+        if images_t is not None:
+            if len(images_t) != B or any(tuple(a.shape) != tuple(b.shape) for a, b in zip(images, images_t)):
+                raise ValueError("augment: the second frames must match the first in number and size")
+            tab_t = _image_table(images_t, dev, "images_t")
+        S = self.size
+        if out is None:
+            out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        if out_t is None:
+            out_t = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().tdrn_augment_pair_apply(_lib.ptr(tab), _lib.ptr(tab_t), _lib.ptr(params), B, self._mean, S,
+                                                      1 if to_rgb else 0, _lib.ptr(out), _lib.ptr(out_t),
+                                                      _lib.current_stream(dev)), "augment pair apply")
+        return out, out_t
+
+    def batch(self, images, targets, sample_ids=None, seed=None, tape=None, images_t=None, targets_t=None, to_rgb=True,
+              return_params=False):
+        dev = images[0].device
+        _lib.require_cuda(images[0], "images")
+        if (images_t is None) != (targets_t is None):
+            raise ValueError("augment: second frames and their truths come together")
+        params, packed, packed_t = self.sample([tuple(im.shape[:2]) for im in images], targets, dev, sample_ids, seed, tape,
+                                               targets_t)
+        x, x_t = self.apply(images, params, images_t, to_rgb)
+        return (x, x_t, packed, packed_t, params) if return_params else (x, x_t, packed, packed_t)
+
+    def __call__(self, img_pair, boxes_pair, labels_pair):
+        def frame(img):
+            img = torch.as_tensor(img)
+            return (img if img.is_cuda else img.to("cuda")).to(torch.uint8).contiguous()
+
+        def rows(boxes, labels):
+            b = torch.as_tensor(boxes, dtype=torch.float64).reshape(-1, 4)
+            return torch.cat([b, torch.as_tensor(labels, dtype=torch.float64).reshape(-1, 1).to(b.device)], 1)
+        img = frame(img_pair[0])
+        second = len(img_pair) > 1 and img_pair[1] is not None
+        x, x_t, packed, packed_t = self.batch([img], [rows(boxes_pair[0], labels_pair[0])], [next(self._calls)],
+                                              images_t=[frame(img_pair[1])] if second else None,
+                                              targets_t=[rows(boxes_pair[1], labels_pair[1])] if second else None, to_rgb=False)
+        k = int(packed.offsets[1])
+        r, r_t = packed.truths[:k], packed_t.truths[:k]
+        return [x[0].permute(1, 2, 0), x_t[0].permute(1, 2, 0)], [r[:, :4], r_t[:, :4]], [r[:, 4], r_t[:, 4]]
+
+
+pairSSDAugmentation = PairSSDAugmentation
