@@ -264,7 +264,7 @@ int launch_augment_sample(const int32_t *hw, const double *truths, const int32_t
 int launch_augment_apply(const tdrn_augment_image *images, const tdrn_augment_params *params, int B, const float *mean, int S,
                          int to_rgb, float *out, hipStream_t s);
 
-// pairSSDAugmentation on the device (augment_pair.hip; semantics: tdrn_hip.h section ii-d)
+// pairSSDAugmentation on the device: the same chain over two frames (augment.hip; semantics: tdrn_hip.h section ii-d)
 int launch_augment_pair_sample(const int32_t *hw, const double *truths, const double *truths_t, const int32_t *truth_off,
                                int T_total, int max_truths, int B, double max_trans_ratio, uint64_t seed,
                                const int64_t *sample_ids, const double *tape, const int32_t *tape_off,

@@ -17,6 +17,7 @@ import _augment_ref as R  # noqa: E402
 from tdrn_amd import _lib  # noqa: E402
 from tdrn_amd.layers.box_utils import PackedTargets  # noqa: E402
 from tdrn_amd.utils.augmentations import SSDAugmentation, params_to_dicts  # noqa: E402
+from test_gpu_caller_memory import Guarded  # noqa: E402
 
 DEV = "cuda:0"
 MEAN = (104, 117, 123)
@@ -248,20 +249,6 @@ def test_one_image_call_has_the_reference_signature():
     assert out.shape == (300, 300, 3) and out.is_cuda and boxes.shape[1] == 4 and labels.shape == boxes.shape[:1]
 
 
-SENTINEL = 0x7FBADBAD
-GUARD = 4096
-
-
-def _guarded(nbytes, offset=0):
-    raw = torch.full(((2 * GUARD + offset + nbytes + 3) // 4,), SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)
-    return raw, GUARD + offset, GUARD + offset + nbytes
-
-
-def _bands_intact(raw, lo, hi):
-    pat = torch.full(((raw.numel() + 3) // 4,), SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)[:raw.numel()]
-    return torch.equal(raw[:lo], pat[:lo]) and torch.equal(raw[hi:], pat[hi:])
-
-
 @gpu
 def test_outputs_stay_inside_guard_bands():
     B, S = 6, 320
@@ -277,21 +264,20 @@ def test_outputs_stay_inside_guard_bands():
     rows = torch.cat([t.double() for t in tt if t.numel()]).to(DEV)
     counts = [len(t) for t in targets]
     off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32, device=DEV)
-    gp = _guarded(B * C.sizeof(_lib.AugmentParams))
-    gr = _guarded(T * 20, offset=4)
-    go = _guarded((B + 1) * 4)
+    gp = Guarded((B, C.sizeof(_lib.AugmentParams)), torch.uint8)
+    gr = Guarded((T, 5), offset=4)
+    go = Guarded((B + 1,), torch.int32)
     _lib.check(_lib.lib().tdrn_augment_sample(_lib.ptr(hw), _lib.ptr(rows), _lib.ptr(off), T, max(counts), B, 17, _lib.ptr(ids),
-                                              None, None, C.c_void_p(gp[0].data_ptr() + gp[1]), C.c_void_p(gr[0].data_ptr() + gr[1]),
-                                              C.c_void_p(go[0].data_ptr() + go[1]), _lib.current_stream()))
+                                              None, None, gp.ptr(), gr.ptr(), go.ptr(), _lib.current_stream()))
     # apply: the output at a 4-byte offset
-    gx = _guarded(B * 3 * S * S * 4, offset=4)
-    xv = gx[0][gx[1]:gx[2]].view(torch.float32).view(B, 3, S, S)
-    aug.apply(dimgs, params_ref, to_rgb=True, out=xv)
-    torch.cuda.synchronize()
-    for g in (gp, gr, go, gx):
-        assert _bands_intact(*g)
-    assert torch.equal(gp[0][gp[1]:gp[2]].view(B, -1), params_ref)
-    assert torch.equal(go[0][go[1]:go[2]].view(torch.int32), packed_ref.offsets)
+    gx = Guarded((B, 3, S, S), offset=4)
+    aug.apply(dimgs, params_ref, to_rgb=True, out=gx.t)
+    gp.check("records")
+    gr.check("rows", full=False)                                                # written up to the kept count only
+    go.check("offsets")
+    gx.check("pixels")
+    assert torch.equal(gp.t, params_ref)
+    assert torch.equal(go.t, packed_ref.offsets)
     k = int(packed_ref.offsets[-1])
-    assert torch.equal(gr[0][gr[1]:gr[1] + k * 20].view(torch.float32).view(k, 5), packed_ref.truths[:k])
-    assert torch.equal(xv, x_ref)
+    assert torch.equal(gr.t[:k], packed_ref.truths[:k])
+    assert torch.equal(gx.t, x_ref)

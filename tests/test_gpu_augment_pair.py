@@ -20,9 +20,10 @@ import _augment_pair_ref as P  # noqa: E402
 from tdrn_amd import _lib  # noqa: E402
 from tdrn_amd.utils.augmentations import (PairSSDAugmentation, SSDAugmentation, pair_params_to_dicts,  # noqa: E402
                                           params_to_dicts)
+from test_gpu_augment import MEAN, _dev, _rows  # noqa: E402
+from test_gpu_caller_memory import Guarded  # noqa: E402
 
 DEV = "cuda:0"
-MEAN = (104, 117, 123)
 gpu = pytest.mark.gpu
 SHARED = ("brightness", "contrast_pre", "contrast_post", "saturation", "hue", "perm", "canvas_w", "canvas_h", "img_x", "img_y",
           "mirror")
@@ -47,18 +48,8 @@ def _fixture(golden_dir):
     return cases
 
 
-def _dev(imgs):
-    return [torch.from_numpy(np.ascontiguousarray(im)).to(DEV) for im in imgs]
-
-
 def _tt(targets):
     return [torch.from_numpy(np.ascontiguousarray(t)) for t in targets]
-
-
-def _rows(packed):
-    off = packed.offsets.cpu().numpy()
-    t = packed.truths.cpu().numpy()
-    return [t[off[b]:off[b + 1]] for b in range(len(off) - 1)]
 
 
 def _same_offsets(a, b):
@@ -347,20 +338,6 @@ def test_packed_pairs_feed_the_loss_without_a_sync():
     assert all(torch.isfinite(v).item() for v in got)
 
 
-SENTINEL = 0x7FBADBAD
-GUARD = 4096
-
-
-def _guarded(nbytes, offset=0):
-    raw = torch.full(((2 * GUARD + offset + nbytes + 3) // 4,), SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)
-    return raw, GUARD + offset, GUARD + offset + nbytes
-
-
-def _bands_intact(raw, lo, hi):
-    pat = torch.full(((raw.numel() + 3) // 4,), SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)[:raw.numel()]
-    return torch.equal(raw[:lo], pat[:lo]) and torch.equal(raw[hi:], pat[hi:])
-
-
 @gpu
 def test_outputs_stay_inside_guard_bands():
     B, S = 3, 48
@@ -374,28 +351,24 @@ def test_outputs_stay_inside_guard_bands():
     rows = torch.cat([t.double() for t in tt if t.numel()]).to(DEV)
     counts = [len(t) for t in targets]
     off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32, device=DEV)
-    gp = _guarded(B * C.sizeof(_lib.AugmentPairParams))
-    gr, gt = _guarded(T * 20, offset=4), _guarded(T * 20, offset=4)          # rows at a 4-byte offset
-    go = _guarded((B + 1) * 4)
-
-    def at(g):
-        return C.c_void_p(g[0].data_ptr() + g[1])
+    gp = Guarded((B, C.sizeof(_lib.AugmentPairParams)), torch.uint8)
+    gr, gt = Guarded((T, 5), offset=4), Guarded((T, 5), offset=4)            # rows at a 4-byte offset
+    go = Guarded((B + 1,), torch.int32)
     _lib.check(_lib.lib().tdrn_augment_pair_sample(_lib.ptr(hw), _lib.ptr(rows), None, _lib.ptr(off), T, max(counts), B, 0.1, 17,
-                                                   _lib.ptr(ids), None, None, at(gp), at(gr), at(gt), at(go),
+                                                   _lib.ptr(ids), None, None, gp.ptr(), gr.ptr(), gt.ptr(), go.ptr(),
                                                    _lib.current_stream()))
-    gx, gy = _guarded(B * 3 * S * S * 4, offset=4), _guarded(B * 3 * S * S * 4, offset=4)      # pixels at a 4-byte offset
-    xv = gx[0][gx[1]:gx[2]].view(torch.float32).view(B, 3, S, S)
-    yv = gy[0][gy[1]:gy[2]].view(torch.float32).view(B, 3, S, S)
-    aug.apply(dimgs, params_ref, to_rgb=True, out=xv, out_t=yv)
-    torch.cuda.synchronize()
-    for g in (gp, gr, gt, go, gx, gy):
-        assert _bands_intact(*g)
-    assert torch.equal(gp[0][gp[1]:gp[2]].view(B, -1), params_ref)
-    assert torch.equal(go[0][go[1]:go[2]].view(torch.int32), packed_ref.offsets)
+    gx, gy = Guarded((B, 3, S, S), offset=4), Guarded((B, 3, S, S), offset=4)      # pixels at a 4-byte offset
+    aug.apply(dimgs, params_ref, to_rgb=True, out=gx.t, out_t=gy.t)
+    for what, g in (("records", gp), ("offsets", go), ("pixels", gx), ("pixels of frame 1", gy)):
+        g.check(what)
+    for what, g in (("rows", gr), ("rows of frame 1", gt)):
+        g.check(what, full=False)                                               # written up to the kept count only
+    assert torch.equal(gp.t, params_ref)
+    assert torch.equal(go.t, packed_ref.offsets)
     k = int(packed_ref.offsets[-1])
-    assert torch.equal(gr[0][gr[1]:gr[1] + k * 20].view(torch.float32).view(k, 5), packed_ref.truths[:k])
-    assert torch.equal(gt[0][gt[1]:gt[1] + k * 20].view(torch.float32).view(k, 5), packed_t_ref.truths[:k])
-    assert torch.equal(xv, x_ref) and torch.equal(yv, xt_ref)
+    assert torch.equal(gr.t[:k], packed_ref.truths[:k])
+    assert torch.equal(gt.t[:k], packed_t_ref.truths[:k])
+    assert torch.equal(gx.t, x_ref) and torch.equal(gy.t, xt_ref)
 
 
 @gpu
