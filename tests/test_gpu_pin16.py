@@ -22,6 +22,22 @@ conv3x3_patch, ygemm_k256, deform_sample).  Three kinds of checks, all through t
       rounded per-tap weights (same bound), and deform_sample's output against a blend of THE DEVICE'S OWN Y rows with
       bilinear weights recomputed from the device's own fp32 offsets by the reference's rule
       (utils/deformconv/deform_conv_cuda_kernel.cu:15-51,189-203), fp32 accumulation noise only.
+
+Frame sizes.  The tests of this file run (b) and (c) at the build sizes, 320 and 512 px.  Multi-scale testing (eval/tta.py) feeds a
+320-net 192 ... 704 px frames, each on a plan of its own (engine_for), and the kernel a 3x3 / s1 / p1 layer gets follows its map
+(patch_conv_supported in conv3x3_patch.hip; conv3x3_pp.hip and conv3x3_ws.hip build on its choice; maps below 400 pixels and all other
+convs: conv_igemm.hip, split-K from the geometry):
+
+    tile mode                 condition                       maps at 320 / 512 px       maps of a 320-net at the other sizes
+    8 x 32 tiles              W % 32 == 0, H % 8 == 0         320, 160 / 512 ... 32      96, 192, 224, 288, 352, 448, 576, 704
+    16 x 16 tiles             W % 16 == 0, H % 16 == 0        80 (5 tiles per row)       48 (3 per row), 112 (7), 144 (9), 176 (11)
+    flat 256-pixel tiles      2 W + 258 <= 352 (W <= 47)      40, 20                     22, 24, 28, 36, 44 (346 of the 352 patch rows)
+    none: conv_igemm          everything else                 10, 5 (< 400 pixels)       56, 72, 88 (conv4_x and its TCB convs, unsplit);
+                                                                                         3 ... 18 (< 400 pixels, split-K up to 16)
+
+check_stages takes the engine that ran x and an optional selection of stages; tests/test_gpu_pin16_sizes.py runs it at 192, 448 and
+704 px (VGG) and 448 px (MobileNet), and test_kernel_choice_never_changes_a_bit_at_other_frame_sizes below runs (a) and the batch
+independence of every frame at 192, 448, 576 and 704 px.
 """
 import numpy as np
 import pytest
@@ -115,13 +131,16 @@ def _head_map(t, b, level, fm, per):
     return t[b, offs[level]:offs[level + 1]].reshape(f, f, per).permute(2, 0, 1)
 
 
-def check_stages(net, sd, x, dtype, images, skip_first_input=False, forward=None):
+def check_stages(net, sd, x, dtype, images, skip_first_input=False, forward=None, stages=None):
     """(b) + (c) for every launch of net's plan after net(x); `images`: batch rows that are recomputed on the CPU.
-    `forward`: how to run the net when net(x) alone does not (the TRN temporal net needs ref_loc)."""
+    `forward`: how to run the net when net(x) alone does not (the TRN temporal net needs ref_loc).
+    `stages(op, (H, W))`: which ops are recomputed, from the op's info and the size of its input map (default: every op); an op
+    that is not selected is not counted in `checked`.  The plan, the workspace and the pyramid geometry are those of the engine
+    that ran x (net.engine_for: a frame size other than the build size has its own)."""
     B = x.shape[0]
     outs = (forward or net)(x)
     torch.cuda.synchronize()
-    eng = net._engine
+    eng = net.engine_for(x)
     tinfo = eng.tensor_infos()
     if len(outs) >= 4:
         arm_loc, odm_loc, conf = outs[0], outs[2], outs[3]
@@ -141,6 +160,8 @@ def check_stages(net, sd, x, dtype, images, skip_first_input=False, forward=None
     for oi, op in enumerate(ops):
         kind = op["kind"]
         name = "%s:%s" % (kind, op["w"] or tinfo[op["in"]][0])
+        if stages is not None and not stages(op, tuple(tinfo[op["in"]][2:4]) if op["in"] >= 0 else (x.shape[2], x.shape[3])):
+            continue
         if kind == "first_conv":
             if oi + 1 < len(ops) and ops[oi + 1]["fused_first"]:
                 continue                                       # computed inside the next conv's loader: checked there
@@ -262,10 +283,12 @@ def _check_transform_then_sample(eng, sd, op, tensor, odm_loc, conf, fm, B, imag
     wt = torch.cat(wt, 0)
     taps = wt.shape[0]
     # ---- the device's Y, raw
-    raw = tensor(op["y"])                                    # (B, ycols, H, W): an NHWC reading of the buffer
+    # (regrouped on the device: at 704 px batch 13 the 88 x 88 level's Y is 1.1 GB in fp32; only the checked images' rows go to the CPU)
+    raw = eng.read_tensor(op["y"], B)                        # (B, ycols, H, W): an NHWC reading of the buffer
     G = max(1, op["y_groups"])                               # column groups of 80 (12 + 3 * classes > 80): one buffer region each
     ycols = raw.shape[1] // G
     flat_all = raw.permute(0, 2, 3, 1).reshape(-1)
+    del raw
     parts = []
     for g in range(G):
         flat = flat_all[g * ycols * M:(g + 1) * ycols * M]
@@ -274,7 +297,7 @@ def _check_transform_then_sample(eng, sd, op, tensor, odm_loc, conf, fm, B, imag
         else:
             rows = flat.reshape(M, ycols)
             parts.append(torch.stack([rows[:, (t // 3) * 256 + (t % 3) * 80:(t // 3) * 256 + (t % 3) * 80 + 80] for t in range(taps)], 0))
-    Yd = torch.cat(parts, 2).double()                        # (taps, M, 80 G): column c of group g = output column 80 g + c
+    Yd = parts[0] if G == 1 else torch.cat(parts, 2)         # (taps, M, 80 G) fp32: column c of group g = output column 80 g + c
     assert G == (ncol + 79) // 80, name
     assert float(Yd[:, :, ncol:].abs().max()) == 0.0, name + ": padding columns of Y are not zero"
     X = tensor(op["in"]).double()                            # (B, 256, H, W)
@@ -284,9 +307,10 @@ def _check_transform_then_sample(eng, sd, op, tensor, odm_loc, conf, fm, B, imag
         # (c1) ygemm: Y[tap][pixel][c] = sum_k X[pixel][k] W16[c][tap][k]
         yref = torch.einsum("tck,kp->tpc", wt, xb)
         S = torch.einsum("tck,kp->tpc", wt.abs(), xb.abs())
-        _assert_stage(name + ":ygemm", Yd[:, b * HW:(b + 1) * HW, :ncol], yref, S, dtype, report=report)
+        yb = Yd[:, b * HW:(b + 1) * HW, :ncol].cpu().double()
+        _assert_stage(name + ":ygemm", yb, yref, S, dtype, report=report)
         # (c2) deform_sample: blend of the DEVICE's Y rows; weights by the reference's rule in fp32 from the device's offsets
-        ydev = Yd[:, b * HW:(b + 1) * HW, :ncol].numpy()     # (taps, HW, 75)
+        ydev = yb.numpy()                                    # (taps, HW, 75)
         out = np.zeros((HW, ncol))
         Sb = np.zeros((HW, ncol))
         near = np.zeros(HW, bool)
@@ -438,6 +462,52 @@ def test_kernel_choice_never_changes_a_bit(dtype):
             for u, v in zip(got, want):
                 assert torch.equal(u, v), (dtype, size, batch, flags)
             other._engine.check()
+
+
+def _row(t, b, B):
+    """frame b of an output of a batch of B: (B, ...) tensors, and the (B * P, classes) softmax output"""
+    return t[b] if t.shape[0] == B else t.view(B, -1, t.shape[-1])[b]
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_kernel_choice_never_changes_a_bit_at_other_frame_sizes(dtype):
+    """(a) at the frame sizes of multi-scale testing, on the per-size plans of a 320-net (engine_for), where the 3x3 family meets the
+    geometries 320 and 512 px never produce: 192 px batch 5 (conv3x3_ws with SX = 6 and ragged unit ranges, 16 x 16 tiles 3 per row,
+    flat tiles at 24; single head: the 5x5 branch refuses a 3x3 map), 448 px batch 3 (7 tiles per row, flat tiles at 28, conv4_x on
+    conv_igemm at 56), 576 px batch 2 (9 tiles per row at 144, flat tiles at 36, conv_igemm at 72) and 704 px batch 13 (11 tiles per
+    row at 176, flat tiles at 44 -- the widest map flat mode takes -- with 198 items, i.e. on conv3x3_pp).  Every output of the
+    default plan torch.equal to the plan with each kernel choice off, no device status raised; and frames 0 and B - 1 of the default
+    plan's batched run equal their single-frame runs bit for bit (no frame's arithmetic depends on the batch it travels in)."""
+    cases = [(192, 5, 81, False), (448, 3, 82, True), (576, 2, 83, True), (704, 13, 84, True)]
+    flag_sets = (_lib.PLAN_NO_CONV_PP, _lib.PLAN_NO_PP_SK, _lib.PLAN_NO_CONV_WS, _lib.PLAN_NO_FUSE_FIRST,
+                 _lib.PLAN_NO_CONV_WS | _lib.PLAN_NO_FUSE_FIRST, _lib.PLAN_NO_PATCH_TAIL, _lib.PLAN_NO_YGEMM_V2, _lib.PLAN_TS_ONE_RANGE)
+    for mh in (False, True):
+        todo = [c for c in cases if c[3] == mh]
+        args = VGG[1][:5] + (mh,)
+        base, _ = _build(VGG[0], args, dtype=dtype)
+        frames, want = {}, {}
+        for size, batch, seed, _ in todo:
+            x = frames[size] = torch.from_numpy(synth.synth_frames(batch, size, seed=seed)).to(DEV)
+            want[size] = _outputs(base, x)
+            torch.cuda.synchronize()
+            base.engine_for(x).check()
+            assert base.engine_for(x) is not base._engine and base.engine_for(x).fm[0] == size // 8
+            for b in (0, batch - 1):
+                one = _outputs(base, x[b:b + 1].contiguous())
+                assert len(one) == len(want[size])
+                for u, v in zip(one, want[size]):
+                    assert torch.equal(u[0] if u.shape[0] == 1 else u, _row(v, b, batch)), (dtype, size, batch, b)
+        del base
+        for flags in flag_sets:
+            other, _ = _build(VGG[0], args, dtype=dtype, flags=flags)
+            for size, batch, seed, _ in todo:
+                got = _outputs(other, frames[size])
+                torch.cuda.synchronize()
+                assert len(got) == len(want[size])
+                for u, v in zip(got, want[size]):
+                    assert torch.equal(u, v), (dtype, size, batch, flags)
+                other.engine_for(frames[size]).check()
+            del other
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
