@@ -394,7 +394,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     // every access a contiguous 1 KiB per wave.  Hand-off = cdna_hip_programming.md Guideline 16: plain stores, every storing
     // wave's vmcnt(0), workgroup barrier, ONE agent-scope release + vmcnt(0), relaxed agent flag store; the consumer polls
     // relaxed (bounded), ONE agent-scope acquire + vmcnt(0), workgroup barrier, plain loads.  A flag has one reader, which
-    // resets it: a launch that finds the flag words zero leaves them zero (ConvArgs::sk_flags_zero: net.hip zeroes them once
+    // resets it: a launch that finds the flag words zero leaves them zero (ConvArgs::sk_flags_zero: net_run.hip zeroes them once
     // per forward on a side lane; otherwise a memset node in front of the launch).  Each of the two routines contains ONE workgroup barrier.
     auto slab_of = [&](int wg) -> f32x4 * { return (f32x4 *)(p.sk_slab + ((size_t)wg * 8 + wave) * (32 * 64 * 4)) + opaque_lane(); };
     auto begin_acc = [&](int c0) {

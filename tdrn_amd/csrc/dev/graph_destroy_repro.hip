@@ -35,7 +35,7 @@ int main(int argc, char **argv)
         bump<<<n / 256, 256, 0, main_s>>>(buf, n);
         for (int l = 0; l < 3; ++l) {
             CK(hipStreamWaitEvent(side[l], ev[0], 0));
-            CK(hipMemsetAsync(buf + (l + 1) * n, 0, 1024, side[l]));      // (net.hip zeroes flag words on a side lane)
+            CK(hipMemsetAsync(buf + (l + 1) * n, 0, 1024, side[l]));      // (net_run.hip zeroes flag words on a side lane)
             bump<<<n / 256, 256, 0, side[l]>>>(buf + (l + 1) * n, n);
             CK(hipEventRecord(ev[1 + l], side[l]));
             CK(hipStreamWaitEvent(main_s, ev[1 + l], 0));         // join

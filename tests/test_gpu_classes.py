@@ -4,7 +4,7 @@ COCO's 81 in evaluate_coco.py:245-270 (dualrefinedet_vggbn).  Every other net-le
 
 What changes with the class count: the conf heads have 3 * C output channels (93 / 243 instead of 63), the deformable heads
 12 + 3 * C columns (105 / 255) -- more than the 80 columns of a transform-then-sample Y row, so the 16-bit single-group plans
-run 2 / 4 column groups (net.hip `y_groups`) -- softmax rows of C, Detect over C - 1 classes."""
+run 2 / 4 column groups (net_plan.h `y_groups`) -- softmax rows of C, Detect over C - 1 classes."""
 import numpy as np
 import pytest
 import torch

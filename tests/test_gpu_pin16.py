@@ -7,7 +7,7 @@ conv3x3_patch, ygemm_k256, deform_sample).  Three kinds of checks, all through t
       bit-identical (full DRN net, 320 px at batch 1 and 32, 512 px at batch 3, both 16-bit types);
   (b) exact-input stage checks: for EVERY conv / conv-transpose / depthwise / pool / L2Norm launch of a plan the stage's own
       materialised input is read back (tdrn_net_read_tensor), the stage is recomputed on the CPU in fp64 with the
-      16-bit-rounded BN-folded weights (model/networks.py:136-163 arithmetic, folded as net.hip does), and every output
+      16-bit-rounded BN-folded weights (model/networks.py:136-163 arithmetic, folded as net_pack.hip does), and every output
       element must satisfy
             |got - ref| <= ulp16(|ref| + c S) + c S,     S = sum |x| |w| (+ |bias| + |residual|),  c = 2e-6 (bf16) / 4e-5 (fp16)
       i.e. one rounding of the output to the 16-bit type plus fp32 accumulation noise -- a wrong tile, a dropped tap or
@@ -81,7 +81,7 @@ def _ulp16(a, dtype):
 
 
 def _fold(sd, op):
-    """BN-folded fp32 weights and bias of a conv op, as net.hip fold()/pack() compute them (double, cast to float)."""
+    """BN-folded fp32 weights and bias of a conv op, as net_pack.hip fold() / pack_conv() compute them (double, cast to float)."""
     w = torch.from_numpy(sd[op["w"] + ".weight"]).double()
     cout = w.shape[0]
     scale = torch.ones(cout, dtype=torch.float64)
@@ -270,7 +270,7 @@ def _check_transform_then_sample(eng, sd, op, tensor, odm_loc, conf, fm, B, imag
     HW, M = H * W, B * H * W
     nc3 = conf.shape[-1] * 3
     ncol = 12 + nc3
-    # ---- per-tap weights, taps of the 3x3 branch first, then the 5x5 branch (net.hip pack(): deform_y_col order)
+    # ---- per-tap weights, taps of the 3x3 branch first, then the 5x5 branch (net_pack.hip pack_deform(): deform_y_col order)
     branches = [(op["w"], op["b"], 3, 1, op["off_c0"][0])]
     if op["n_branches"] == 2:
         branches.append((op["w2"], op["b2"], op["k2"], op["pad2"], op["off_c0"][1]))
