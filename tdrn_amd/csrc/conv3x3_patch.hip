@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "mfma_prims.h"
 
 // diagnostics build switch (never set in the product build): 1 = loaders issue nothing, 2 = consumers
 // skip ds_read + MFMA, 4 = skip the epilogue stores.  Compile-time on purpose: a runtime flag splits
@@ -83,51 +84,6 @@ struct PatchParams {
 #endif
 
 namespace {
-
-template <typename DT> struct MmaP;
-template <> struct MmaP<bf16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaP<f16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaP<float> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[j]), __uint_as_float(b[j]), c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ void glds(const char *src, char *dst)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ void wait_vmcnt(int n)   // n is wave-uniform
-{
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    }
-}
 
 #ifndef TDRN_PATCH_RING
 #define TDRN_PATCH_RING 3
@@ -189,12 +145,12 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
     // ---- work distribution: each XCD (blockIdx % 8) owns a contiguous range of items so that cout
     // siblings of a pixel tile and neighbouring tiles share its L2.  This workgroup runs items
     // item0, item0 + istride, ... (n_it of them); the step sequence is (item, chunk, tap).
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per_xcd = (p.items + 7) >> 3, istride = ((int)gridDim.x + 7) >> 3;
-    int avail = p.items - xcd * per_xcd;
-    avail = avail < per_xcd ? avail : per_xcd;
+    const XcdItems xi = xcd_items(p.items);
+    const int slot = xi.slot, istride = xi.istride;
+    int avail = p.items - xi.xcd * xi.per_xcd;          // (xi.avail without its clamp at 0 -- a negative count finds no item either way; this
+    avail = avail < xi.per_xcd ? avail : xi.per_xcd;    // kernel has always been compiled without the clamp and keeps its instructions)
     int n_full = avail > slot ? (avail - slot + istride - 1) / istride : 0;
-    const int item0 = xcd * per_xcd + slot;
+    const int item0 = xi.item0();
     // ---- tail split (round 6).  1600 items on 256 workgroups are 6.25 rounds: after six rounds an XCD has 8 items left for its 32
     // workgroups and the launch ends with 24 of every 32 CUs idle for a whole item (per-workgroup stamps, profiles/r05_experiments.md:
     // 7-13 % of the chip time of conv2_1 / 2_2 / 3_1 / 3_3).  When an XCD's last round is at most HALF filled, its items are cut in two
@@ -212,7 +168,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
                 n_full = full;
                 if (slot < 2 * rem) {
                     n_tail = 1;
-                    tail_enc = 2 * (xcd * per_xcd + full * istride) + slot;
+                    tail_enc = 2 * (xi.xcd * xi.per_xcd + full * istride) + slot;
                 }
             }
         }
@@ -342,7 +298,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) xq[jj] = pack2<DT>(xv[8 * ks + 2 * jj], xv[8 * ks + 2 * jj + 1]);
 #pragma unroll
-                    for (int ci = 0; ci < 2; ++ci) MmaP<DT>::run(wq1[ci][ks], xq, a1[ci]);
+                    for (int ci = 0; ci < 2; ++ci) Mma32<DT>::run(wq1[ci][ks], xq, a1[ci]);
                 }
                 if (valid) {
                     char *row = dstbuf + pq * 128 + 8 * f_hh;
@@ -407,7 +363,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
                 char *dst = smem + OFF_W + wslot * WBYTES;
 #pragma unroll
                 for (int k = 0; k < WL; ++k)
-                    if (!TAILOK || k < np) glds(wfixed ? p.w + (woff[k] & 0xffffu) : wbase + wk + woff[k], dst + (lw + 4 * k) * 1024);
+                    if (!TAILOK || k < np) lds_dma16_ptr(wfixed ? p.w + (woff[k] & 0xffffu) : wbase + wk + woff[k], dst + (lw + 4 * k) * 1024);
             }
             ++ws;
             wslot = wslot == RING - 1 ? 0 : wslot + 1;
@@ -426,7 +382,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
         auto load_patch = [&](int j, unsigned ccoff, char *dstbuf) {
             if (!live || lw + 4 * j >= kPatchSlots || FUSE) return;
             const unsigned o = poff[j];
-            glds(o == 0xFFFFFFFFu ? p.zero : (pfixed ? p.in + (o & 0xfffffu) : p.in + (size_t)o + ccoff), dstbuf + (lw + 4 * j) * 1024);
+            lds_dma16_ptr(o == 0xFFFFFFFFu ? p.zero : (pfixed ? p.in + (o & 0xfffffu) : p.in + (size_t)o + ccoff), dstbuf + (lw + 4 * j) * 1024);
         };
         // patch stream state: the chunk being PREFETCHED: (p_it, p_cc), buffer pbuf
         int p_it = 0, p_cc = 0, pbuf = 0;
@@ -462,7 +418,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
                 if (k < n_steps) load_weights();
             next_patch_chunk();
             if (lw == 0 && live)
-                glds(lane < (n_full > 0 ? BN : 64) / 4 ? (const char *)(p.bias + item_c0(0)) + lane * 16 : p.zero, smem + OFF_B);
+                lds_dma16_ptr(lane < (n_full > 0 ? BN : 64) / 4 ? (const char *)(p.bias + item_c0(0)) + lane * 16 : p.zero, smem + OFF_B);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -496,7 +452,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
             if (lw == 0 && c_cc == nchunks - 1 && tap == 6 && c_it + 1 < n_it) {
                 // the NEXT item's bias -> the other LDS bias slot (the consumers initialise their
                 // accumulators from it when that item starts; this item reads slot c_it & 1)
-                if (live) glds(lane < (c_it + 1 < n_full ? BN : 64) / 4 ? (const char *)(p.bias + item_c0(c_it + 1)) + lane * 16 : p.zero, smem + OFF_B);
+                if (live) lds_dma16_ptr(lane < (c_it + 1 < n_full ? BN : 64) / 4 ? (const char *)(p.bias + item_c0(c_it + 1)) + lane * 16 : p.zero, smem + OFF_B);
                 issued += 1;
             }
             // ring of 3: everything issued before this step has landed; ring of 4: before the previous step
@@ -832,7 +788,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
 #pragma unroll
         for (int ci = 0; ci < WCN; ++ci)
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt) MmaP<DT>::run(wf[ci], pf[pt], acc[ci][pt]);
+            for (int pt = 0; pt < 2; ++pt) Mma32<DT>::run(wf[ci], pf[pt], acc[ci][pt]);
     };
     // accumulators start at the bias (staged into LDS by loader wave 0 one item ahead)
     auto init_acc = [&](auto wcn_tag) {
@@ -955,7 +911,7 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
 // ---------------------------------------------------------------------------------------------
 int patch_conv_supported(const ConvArgs &a)
 {
-    if (a.kdisable & 4) return 0;
+    if (a.kdisable & KOFF_CONV_PATCH) return 0;
     if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return 0;
     if (a.phases != 1 || a.out_f32 || a.res) return 0;
     if (a.Ho != a.H || a.Wo != a.W) return 0;
@@ -973,7 +929,7 @@ template <typename DT, int BN> static int launch_patch_cfg(const PatchParams &p_
 {
     PatchParams p = p_in;
     // a multiple of 8 workgroups (the item split is per XCD); surplus workgroups find no item and exit
-    const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
+    const int grid = persistent_grid(p.items);
 #ifdef TDRN_PATCH_WGTIME
     // diagnostics build: when did every workgroup of launch number TDRN_WGTIME_CALL (and the 17 after it) start and end?  (s_memrealtime,
     // 100 MHz; never inside a stream capture: the report synchronises)
@@ -1043,14 +999,7 @@ int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s)
     p.tw = mode > 0 ? mode : 0;
     p.lgtw = mode == 32 ? 5 : (mode == 16 ? 4 : 0);
     p.M = a.B * a.H * a.W;
-    if (p.tw) {
-        p.tiles_x = a.W / p.tw;
-        p.tiles_per_img = p.tiles_x * (a.H / ((a.fuse_x ? 512 : 256) / p.tw));      // the fused first-conv variant works on 16 x 32 tiles
-        p.m_tiles = a.B * p.tiles_per_img;
-    } else {
-        p.tiles_x = 0; p.tiles_per_img = 0;
-        p.m_tiles = cdiv(p.M, 256);
-    }
+    conv_tiles(a.B, a.H, a.W, p.tw, a.fuse_x ? 512 : 256, p.tiles_x, p.tiles_per_img, p.m_tiles);      // (the fused first-conv variant works on 16 x 32 tiles)
     // 128-cout items unless they would leave most CUs idle (20x20 maps at small batch): 64-cout items double
     // the item count for the same per-output arithmetic (K order unchanged, results identical)
     int BN = a.Npad % 128 == 0 ? 128 : 64;
@@ -1061,7 +1010,7 @@ int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s)
     if (ablate < 0) ablate = dev_ablate_env("TDRN_CONV_ABLATE");     // (developer builds only: common.h)
     p.ablate = ablate;
     p.fx = a.fuse_x; p.fw = a.fuse_w; p.fb = a.fuse_b; p.fS = a.H; p.fCout = a.fuse_cout;
-    p.tail_split = !(a.kdisable & 1024);             // (TDRN_PLAN_NO_PATCH_TAIL)
+    p.tail_split = !(a.kdisable & KOFF_PATCH_TAIL);             // (TDRN_PLAN_NO_PATCH_TAIL)
     if (p.items <= 0) return TDRN_OK;
 #ifdef TDRN_PATCH_STAMP
     // diagnostics build: synchronise after every launch and print the mean cycles per wave in each state

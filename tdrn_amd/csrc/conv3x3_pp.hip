@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "mfma_prims.h"
 
 #ifndef TDRN_PP_ABLATE
 #define TDRN_PP_ABLATE 0      // diagnostics: 1 = no LDS-DMA, 2 = no ds_read/MFMA, 4 = no epilogue stores, 8 = no patch pieces, 16 = no weight pieces
@@ -70,43 +71,12 @@ struct PPParams {
 
 namespace {
 
-template <typename DT> struct MmaPP;
-template <> struct MmaPP<bf16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaPP<f16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
-};
-
-// One LDS-DMA piece (64 lanes x 16 B -> 1 KiB of LDS at lds_dst + 16*lane) from a wave-uniform base plus a 32-bit per-lane
-// byte offset.  Inline asm on purpose: (1) no 64-bit per-lane address arithmetic (the accumulators need the registers),
-// (2) hipcc's waitcnt pass does not see it, so it cannot put an `s_waitcnt vmcnt(0)` in front of the ds_reads that follow
-// (cdna_hip_programming.md 5.7 item 1: the completion is counted by hand -- the vmcnt(N) of every step below).  M0 is
-// written in the statement that uses it and restored.
+// an LDS-DMA piece (mfma_prims.h; its completion is counted by hand: the vmcnt(N) of every step below)
 __device__ __forceinline__ void glds16(const char *sbase, unsigned voff, unsigned lds_dst)
 {
-    if constexpr (!(TDRN_PP_ABLATE & 1)) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(sbase), "s"(lds_dst)
-                     : "memory");
-    }
-}
-__device__ __forceinline__ unsigned lds_addr(const void *p)
-{
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)p;
+    if constexpr (!(TDRN_PP_ABLATE & 1)) lds_dma16(sbase, voff, lds_dst);
 }
 
-// (all waves of a workgroup take part in every barrier; nothing may move across it)
-#define PP_BAR()                                  \
-    do {                                          \
-        __builtin_amdgcn_sched_barrier(0);        \
-        __builtin_amdgcn_s_barrier();             \
-        __builtin_amdgcn_sched_barrier(0);        \
-    } while (0)
 #define PP_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
 #define PP_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)   // vmcnt(0), through the builtin: the compiler's waitcnt pass sees it
 
@@ -142,12 +112,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     // Register discipline: the 128 accumulators + 48 fragment registers leave ~70 for everything else, and hipcc hoists every
     // loop-invariant lane expression of the (rarely executed) staging / epilogue code out of the step loop and then spills
     // them -- re-loaded behind an `s_waitcnt vmcnt(0)` that would drain the LDS-DMA pipeline.  So those code paths derive
-    // their lane constants from an OPAQUE copy of the lane id (a few vector instructions where they are used).
-    auto opaque_lane = [&]() -> int {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        return ln;
-    };
+    // their lane constants from opaque(lane), an OPAQUE copy of the lane id (a few vector instructions where they are used).
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave >> 2;                          // cout half / ping-pong group
     const int cw = wave & 3;                            // pixel group: pixels [64*cw, 64*cw + 64)
@@ -164,29 +129,26 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     //     the workgroups reach their epilogues at different times instead of all bursting their stores at once.
     //     A workgroup runs its unfinished LAST item first (its successor needs that slab), whole items next, and the item
     //     whose first part belongs to its predecessor last (the slab has long been written by then).
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per_xcd = (p.items + 7) >> 3, istride = ((int)gridDim.x + 7) >> 3;
-    int avail = p.items - xcd * per_xcd;
-    avail = avail < per_xcd ? avail : per_xcd;
-    avail = avail < 0 ? 0 : avail;
+    const XcdItems xi = xcd_items(p.items);
+    const int slot = xi.slot, istride = xi.istride;
     const bool sk = p.sk_slab != nullptr;
     int n_seg, seg_item0, c0_first = 0, c1_last = nchunks, tail_first = 0, head_last = 0;
     if (sk) {
-        const int units = avail * nchunks;
+        const int units = xi.avail * nchunks;
         // (units * 32 < 2^31 for any tensor below the 4-GiB limit of patch_conv_supported; 32-bit scalar arithmetic)
         const int u0 = __builtin_amdgcn_readfirstlane(units * slot / istride), u1 = __builtin_amdgcn_readfirstlane(units * (slot + 1) / istride);
         if (u1 <= u0) return;                           // (whole workgroup)
         const int fi = u0 / nchunks, li = (u1 - 1) / nchunks;
         n_seg = li - fi + 1;
-        seg_item0 = xcd * per_xcd + fi;
+        seg_item0 = xi.xcd * xi.per_xcd + fi;
         c0_first = u0 - fi * nchunks;
         c1_last = u1 - li * nchunks;
         tail_first = (c1_last != nchunks && n_seg > 1) ? 1 : 0;
         head_last = (c0_first != 0 && n_seg > 1) ? 1 : 0;
     } else {
-        n_seg = avail > slot ? (avail - slot + istride - 1) / istride : 0;
+        n_seg = xi.n_items();
         if (n_seg == 0) return;                         // (whole workgroup)
-        seg_item0 = xcd * per_xcd + slot;
+        seg_item0 = xi.item0();
     }
     // segment k of the execution order -> item and chunk range (wave-uniform scalars)
     auto seg = [&](int k, int &item, int &c0, int &c1) {
@@ -201,7 +163,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
         c0 = __builtin_amdgcn_readfirstlane(j == 0 ? c0_first : 0);
         c1 = __builtin_amdgcn_readfirstlane(j == n_seg - 1 ? c1_last : nchunks);
     };
-    const int my_wg = xcd * istride + slot;             // slab / flag index (the producer's); the consumer reads my_wg - 1
+    const int my_wg = xi.xcd * istride + slot;          // slab / flag index (the producer's); the consumer reads my_wg - 1
     const int RS = TW ? TW + 2 : p.W;                   // patch row stride of one image row
 
     // =========================== staging (LDS-DMA) state ===========================
@@ -212,14 +174,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     auto mt_of = [&](int item) -> int { return p.n_major ? item % p.m_tiles : item / p.n_tiles; };
     auto nt_of = [&](int item) -> int { return p.n_major ? item / p.m_tiles : item % p.n_tiles; };
     auto patch_tile = [&](int item) {                   // (wave-uniform scalars; once per prefetched chunk)
-        const int mt = mt_of(item);
-        if (TW) {
-            const int b = mt / p.tiles_per_img, tt = mt - b * p.tiles_per_img;
-            const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
-            pt_b = __builtin_amdgcn_readfirstlane(b); pt_y0 = __builtin_amdgcn_readfirstlane(ty * TH - 1); pt_x0 = __builtin_amdgcn_readfirstlane(tx * TW - 1);
-        } else {
-            pt_j0 = __builtin_amdgcn_readfirstlane(mt * 256 - p.W - 1);
-        }
+        patch_origin(mt_of(item), p.tiles_per_img, p.tiles_x, TH, TW, p.W, pt_b, pt_y0, pt_x0, pt_j0);
     };
     const unsigned smem_lds = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     // A patch piece is PREPARED in a load segment (source offset, which lanes are inside the image; lanes outside get their
@@ -233,7 +188,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
         const int q = wave + 8 * j;                     // piece = patch rows [8q, 8q + 8)
         pp_any = false;
         if (q >= kPPSlots) return;                      // (wave-uniform)
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int lrow = ln >> 3, pc = ln & 7;
         const unsigned lc = (unsigned)((pc ^ ((4 * wave + (lrow >> 1)) & 7)) << 4) + ccoff;
         const unsigned rowbytes = (unsigned)(p.Cin * ES);
@@ -292,7 +247,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             glds16(p.w + off, w + k * wstep, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + slot * WBYTES + grp * (WBYTES / 2) + (cw + 4 * k) * 1024));
     };
     auto load_bias = [&](int item) {                    // wave 0: the item's 256 biases = one 1-KiB piece
-        glds16((const char *)(p.bias + nt_of(item) * BN), (unsigned)opaque_lane() * 16u, smem_lds + OFF_B);
+        glds16((const char *)(p.bias + nt_of(item) * BN), (unsigned)opaque(lane) * 16u, smem_lds + OFF_B);
     };
 
     // =========================== compute state ===========================
@@ -314,7 +269,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             return;
         }
         tile_pix0 = (long long)mt * 256;
-        const int r32 = opaque_lane() & 31;
+        const int r32 = opaque(lane) & 31;
 #pragma unroll
         for (int pt = 0; pt < 2; ++pt) {
             const long long m = tile_pix0 + cw * 64 + pt * 32 + r32;
@@ -336,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     auto epilogue = [&](char *) {
         // lane-derived constants are re-derived here from an opaque copy of the lane id: hoisted out of the step loop they
         // would be live (or spilled and re-loaded behind a vmcnt(0)) across every multiply segment
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int r32 = ln & 31, hh = ln >> 5;
         auto pixel_of = [&](int i) -> long long {       // global pixel of tile-local pixel i (or -1)
             if (TW) return tile_pix0 + (long long)(i >> LGTW) * p.W + (i & (TW - 1));
@@ -375,7 +330,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
 
     // accumulators start at the bias (one 1-KiB LDS slot, re-staged by wave 0 late in the previous item)
     auto init_acc = [&]() {
-        const int hh = opaque_lane() >> 5;
+        const int hh = opaque(lane) >> 5;
         const char *bsrc = smem + OFF_B;
 #pragma unroll
         for (int ci = 0; ci < WC; ++ci)
@@ -396,7 +351,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     // relaxed (bounded), ONE agent-scope acquire + vmcnt(0), workgroup barrier, plain loads.  A flag has one reader, which
     // resets it: a launch that finds the flag words zero leaves them zero (ConvArgs::sk_flags_zero: net_run.hip zeroes them once
     // per forward on a side lane; otherwise a memset node in front of the launch).  Each of the two routines contains ONE workgroup barrier.
-    auto slab_of = [&](int wg) -> f32x4 * { return (f32x4 *)(p.sk_slab + ((size_t)wg * 8 + wave) * (32 * 64 * 4)) + opaque_lane(); };
+    auto slab_of = [&](int wg) -> f32x4 * { return (f32x4 *)(p.sk_slab + ((size_t)wg * 8 + wave) * (32 * 64 * 4)) + opaque(lane); };
     auto begin_acc = [&](int c0) {
         if (c0 == 0) {
             init_acc();
@@ -421,7 +376,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        PP_BAR();
+        wg_barrier();
         const f32x4 *src = slab_of(my_wg - 1);
 #pragma unroll
         for (int ci = 0; ci < WC; ++ci)
@@ -445,7 +400,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
                 for (int q = 0; q < 4; ++q)
                     dst[((ci * 2 + pt) * 4 + q) * 64] = f32x4{acc[ci][pt][4 * q], acc[ci][pt][4 * q + 1], acc[ci][pt][4 * q + 2], acc[ci][pt][4 * q + 3]};
         PP_VM0();                                       // my stores have left (through the builtin: hipcc sees this wait too)
-        PP_BAR();
+        wg_barrier();
         if (wave == 0) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -462,7 +417,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     u32x4 wf[WC][2], pf[2][2];
     unsigned wa = 0, pa[2] = {0, 0};                    // LDS byte addresses (relative to smem)
     auto step_addresses = [&](int wslot, int pbuf_, int rowdelta, unsigned tapbits) {
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int r32 = ln & 31, hh = ln >> 5;
         wa = (unsigned)(OFF_W + wslot * WBYTES + grp * (WBYTES / 2) + r32 * 128 + ((hh ^ ((r32 >> 1) & 7)) << 4));
 #pragma unroll
@@ -493,7 +448,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
 #pragma unroll
         for (int ci = 2 * h; ci < 2 * h + 2; ++ci)
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt) MmaPP<DT>::run(wf[ci][k2], pf[pt][k2], acc[ci][pt]);
+            for (int pt = 0; pt < 2; ++pt) Mma32<DT>::run(wf[ci][k2], pf[pt][k2], acc[ci][pt]);
     };
 #define PP_SB() __builtin_amdgcn_sched_barrier(0)
 
@@ -529,13 +484,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     if (wave == 1 && lane < 8) *(u32x4 *)(smem + OFF_Z + lane * 16) = u32x4{0u, 0u, 0u, 0u};
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     PP_VM0();                                           // (see below: hipcc's own scoreboard must be empty when the step loop starts)
-    PP_BAR();
+    wg_barrier();
     setup_item(cur_item);
     begin_acc(cc);
     step_addresses(0, 0, 0, 0u);
     PP_LGKM0();
     PP_VM0();
-    if (grp == 1) PP_BAR();                             // the stagger: group 1 runs one interval behind group 0
+    if (grp == 1) wg_barrier();                          // the stagger: group 1 runs one interval behind group 0
 
     const unsigned tapbytes = (unsigned)(p.Cin * ES);
     // one step: tap T of the current chunk.  `more`: a step follows (its weights are staged here).
@@ -553,7 +508,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             weight_piece(1, w_next, slot_next);
         }
         PP_LGKM0();
-        PP_BAR();
+        wg_barrier();
         // ---------------- M(slices 0-1): the 16 MFMAs + the other two weight pieces between the groups ----------------
         __builtin_amdgcn_s_setprio(1);
         mma_quad(0, 0);
@@ -567,7 +522,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
         PP_SB();
         mma_quad(1, 1);
         __builtin_amdgcn_s_setprio(0);
-        PP_BAR();
+        wg_barrier();
         // ---------------- L(slices 2-3): reads; this tap's piece of the NEXT chunk's patch (prepared here); the bias ----------
         read_frags(1);
         PP_SB();
@@ -587,7 +542,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             if (bias_now) load_bias(n_item);
         }
         PP_LGKM0();
-        PP_BAR();
+        wg_barrier();
         // ---------------- M(slices 2-3) + (between the MFMA groups) the read addresses of the next step ----------------
         __builtin_amdgcn_s_setprio(1);
         mma_quad(0, 0);
@@ -608,7 +563,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             else if (fly == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         }
-        PP_BAR();
+        wg_barrier();
     };
 #pragma unroll 1
     for (;;) {
@@ -636,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
         if (seg_done) {
             // group 0 waits for group 1's last multiply (one interval), then both groups run their epilogues at the
             // same time out of the patch buffer that died with this step; group 1 re-creates the stagger behind it
-            if (grp == 0) PP_BAR();
+            if (grp == 0) wg_barrier();
             if (c1_done == nchunks) epilogue(smem + dead_buf * PBYTES + wave * STRIP);
             else write_partial();                       // (chained split: the item is finished by my successor)
             if (kseg < n_seg) {
@@ -651,11 +606,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
             // matters: hipcc does not see the LDS-DMA pieces (inline asm); with a LOAD of its own -- a spill re-load, the slab
             // read -- still on its scoreboard at the loop's back edge it protects the register with an `s_waitcnt vmcnt(0)`
             // inside the step loop, which in hardware drains every piece in flight, every step: +40 % time when it happened.)
-            if (grp == 1) PP_BAR();
+            if (grp == 1) wg_barrier();
             if (kseg >= n_seg) break;
         }
     }
-    if (grp == 0) PP_BAR();                             // (matches group 1's re-stagger barrier of the last item)
+    if (grp == 0) wg_barrier();                          // (matches group 1's re-stagger barrier of the last item)
 
 }
 
@@ -666,7 +621,7 @@ size_t conv_pp_sk_bytes() { return 1024 + (size_t)256 * 8 * 32 * 64 * 16; }
 // the layers this kernel takes over from conv3x3_patch.hip: 16-bit, >= 2 channel chunks, couts in whole 256-groups
 int pp_conv_supported(const ConvArgs &a)
 {
-    if (a.kdisable & 1) return 0;
+    if (a.kdisable & KOFF_CONV_PP) return 0;
     if (a.dtype == TDRN_F32 || a.fuse_x) return 0;
     // (Cin = 128 -- two chunks, 18 steps per item -- stays with conv3x3_patch.hip: the per-item cost of this kernel, drain +
     // epilogue + re-stagger, weighs 10 % there: 125 vs 116 us on conv3_1 in the net)
@@ -685,14 +640,7 @@ int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s)
     p.relu = a.relu;
     p.M = a.B * a.H * a.W;
     const int tw = mode > 0 ? mode : 0;
-    if (tw) {
-        p.tiles_x = a.W / tw;
-        p.tiles_per_img = p.tiles_x * (a.H / (256 / tw));
-        p.m_tiles = a.B * p.tiles_per_img;
-    } else {
-        p.tiles_x = 0; p.tiles_per_img = 0;
-        p.m_tiles = cdiv(p.M, 256);
-    }
+    conv_tiles(a.B, a.H, a.W, tw, 256, p.tiles_x, p.tiles_per_img, p.m_tiles);
     p.n_tiles = a.Npad / 256;
     p.items = p.m_tiles * p.n_tiles;
     // With two or more cout tiles an XCD whose items are (pixel tile, cout tile) pairs keeps the WHOLE weight matrix live (4.7 MB at
@@ -703,13 +651,13 @@ int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s)
     // below ~3/4 of a full grid the loader/consumer kernel's smaller (128- / 64-cout) items fill more CUs: measured 2x faster
     // at 50-100 items, equal at 200 (the two kernels produce the same bits, so the choice may depend on the batch)
     if (p.items < 192) return TDRN_E_UNSUPPORTED;
-    const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
+    const int grid = persistent_grid(p.items);
     // chained split when it shortens the launch: a full grid, more than one item per workgroup, and an item count that does
     // not divide evenly (otherwise whole items are already balanced); the choice changes no output bit
     p.sk_slab = nullptr; p.sk_flag = nullptr;
     p.status = a.status; p.fault = a.fault_handoff; p.poll_max = a.fault_handoff ? (1u << 10) : (1u << 20);
     // (grid == 256: every workgroup of the launch is resident at once, see the poll in begin_acc)
-    if (a.sk_ws && !(a.kdisable & 2) && grid == 256 && p.items > grid && p.items % grid != 0) {
+    if (a.sk_ws && !(a.kdisable & KOFF_PP_SK) && grid == 256 && p.items > grid && p.items % grid != 0) {
         p.sk_flag = (unsigned *)a.sk_ws;
         p.sk_slab = (float *)((char *)a.sk_ws + 1024);
         if (!a.sk_flags_zero) TDRN_HIP_TRY(hipMemsetAsync(p.sk_flag, 0, 1024, s));

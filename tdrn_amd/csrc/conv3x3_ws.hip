@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "mfma_prims.h"
 
 namespace tdrn {
 
@@ -74,41 +75,8 @@ struct WsParams {
 
 namespace {
 
-template <typename DT> struct MmaW;
-template <> struct MmaW<bf16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaW<f16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
-};
-
-// One LDS-DMA piece from a wave-uniform base plus a 32-bit per-lane byte offset: 64 lanes x 16 B -> 1 KiB (or x 4 B -> 256 B) of LDS at
-// lds_dst + lane * size.  Inline asm as in conv3x3_pp.hip: hipcc's waitcnt pass does not see it, so it cannot put an
-// `s_waitcnt vmcnt(0)` in front of the LDS accesses that follow (the producers prefetch a raw tile a whole tile time ahead and write ring
-// rows meanwhile); completion is waited for by hand, once per period.  Lanes switched off by the caller's branch write nothing.
-__device__ __forceinline__ void ws_glds16(const char *sbase, unsigned voff, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ void ws_glds4(const char *sbase, unsigned voff, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned ws_lds_addr(const void *p)
-{
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)p;
-}
-
+// (LDS-DMA through lds_dma16 / lds_dma4 of mfma_prims.h, invisible to hipcc's waitcnt pass: the producers prefetch a raw tile a whole
+// tile time ahead and write ring rows meanwhile; completion is waited for by hand, once per period)
 constexpr int kRingRows = 18, kRingCols = 34;
 constexpr int kWBytes = 9 * 64 * 128;                   // 73 728: [tap][cout][128 B], 16-byte chunk c of row n at position c ^ ((n >> 1) & 7)
 constexpr int kRingBytes = kRingRows * kRingCols * 128; // 78 336: pixel q = slot * 34 + col, chunk c at position c ^ ((q >> 1) & 7)
@@ -138,12 +106,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
     const int r32 = lane & 31, hh = lane >> 5;
 
     // ---- my contiguous range of units ---------------------------------------------------------------------------------
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = ((int)gridDim.x + 7) >> 3;
-    const int per_xcd = (p.units + 7) >> 3;
-    int avail = p.units - xcd * per_xcd;
-    avail = avail < per_xcd ? avail : per_xcd;
-    avail = avail < 0 ? 0 : avail;
-    const int u0 = xcd * per_xcd + (int)((long long)avail * slot / nslots), u1 = xcd * per_xcd + (int)((long long)avail * (slot + 1) / nslots);
+    // (the XCD's range of units as in the item kernels, but cut into equal contiguous parts, one per workgroup, not dealt round-robin)
+    const int nslots = ((int)gridDim.x + 7) >> 3;
+    const XcdItems xi = xcd_items(p.units);
+    const int u0 = xi.xcd * xi.per_xcd + (int)((long long)xi.avail * xi.slot / nslots), u1 = xi.xcd * xi.per_xcd + (int)((long long)xi.avail * (xi.slot + 1) / nslots);
     if (u1 <= u0) return;                               // (whole workgroup)
 
     struct Unit { int nt, b, x0, y0, T; };
@@ -162,7 +128,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
         return r;
     };
 
-    const unsigned smem_lds = __builtin_amdgcn_readfirstlane(ws_lds_addr(smem));
+    const unsigned smem_lds = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     // ---- weights (and bias) of a cout tile -> LDS: 72 pieces of 8 rows, nine per wave; piece (tap t, rows 8 wave .. 8 wave + 7) ----
     auto load_weights = [&](int nt) {
         const int lrow = lane >> 3, pc = lane & 7;
@@ -170,8 +136,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
         const char *base = p.w + (size_t)nt * 64 * p.Ktot * 2;
         const unsigned voff = (unsigned)(n * p.Ktot * 2 + ((pc ^ ((n >> 1) & 7)) << 4));
 #pragma unroll
-        for (int t = 0; t < 9; ++t) ws_glds16(base, voff + t * 128, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + (t * 64 + 8 * wave) * 128));
-        if (wave == 0) ws_glds4((const char *)(p.bias + nt * 64), (unsigned)lane * 4u, __builtin_amdgcn_readfirstlane(smem_lds + OFF_BIAS));
+        for (int t = 0; t < 9; ++t) lds_dma16(base, voff + t * 128, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + (t * 64 + 8 * wave) * 128));
+        if (wave == 0) lds_dma4((const char *)(p.bias + nt * 64), (unsigned)lane * 4u, __builtin_amdgcn_readfirstlane(smem_lds + OFF_BIAS));
     };
     auto write_first_bias = [&]() {
         if constexpr (FUSE) {
@@ -255,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
                     // (elements outside the frame -- the first conv's zero padding -- and beyond the tile are ZEROED by an ordinary LDS
                     // store of the lanes concerned; the LDS-DMA runs with those lanes switched off)
                     if (!ok) *(float *)(smem + dst + lane * 4) = 0.f;
-                    if (ok) ws_glds4(xb, (unsigned)(r_off[j] * 4), __builtin_amdgcn_readfirstlane(smem_lds + dst));
+                    if (ok) lds_dma4(xb, (unsigned)(r_off[j] * 4), __builtin_amdgcn_readfirstlane(smem_lds + dst));
                 }
             }
         };
@@ -311,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
 #pragma unroll
                         for (int ci = 0; ci < 2; ++ci) {
                             if (ks == 0) a1[i][ci] = fbias[ci];
-                            MmaW<DT>::run(wq1[ci][ks], xq, a1[i][ci]);
+                            Mma32<DT>::run(wq1[ci][ks], xq, a1[i][ci]);
                         }
                     }
 #pragma unroll
@@ -358,7 +324,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
                     const bool ok = inrow && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
                     const int dst = OFF_RING + (sl_ * kRingCols + k * 8) * 128;
                     if (inrow && !ok) *(u32x4 *)(smem + dst + lane * 16) = u32x4{0u, 0u, 0u, 0u};     // the conv's zero padding
-                    if (ok) ws_glds16(base, (unsigned)((y * p.W + x) * 128 + ((pc ^ ((q >> 1) & 7)) << 4)), __builtin_amdgcn_readfirstlane(smem_lds + dst));
+                    if (ok) lds_dma16(base, (unsigned)((y * p.W + x) * 128 + ((pc ^ ((q >> 1) & 7)) << 4)), __builtin_amdgcn_readfirstlane(smem_lds + dst));
                 }
             }
         };
@@ -577,13 +543,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
 #pragma unroll
                         for (int pt = 0; pt < 2; ++pt) {
                             acc[ci][pt] = cbias[ci];
-                            MmaW<DT>::run(wf[0][ci], pf[0][pt], acc[ci][pt]);
+                            Mma32<DT>::run(wf[0][ci], pf[0][pt], acc[ci][pt]);
                         }
                 } else {
 #pragma unroll
                     for (int ci = 0; ci < 2; ++ci)
 #pragma unroll
-                        for (int pt = 0; pt < 2; ++pt) MmaW<DT>::run(wf[s % 3][ci], pf[s % 3][pt], acc[ci][pt]);
+                        for (int pt = 0; pt < 2; ++pt) Mma32<DT>::run(wf[s % 3][ci], pf[s % 3][pt], acc[ci][pt]);
                 }
             } else if constexpr (s == 0) {
 #pragma unroll
@@ -662,7 +628,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
 // the layers this kernel takes over from conv3x3_patch.hip: 16-bit, ONE 64-channel chunk, 2-D geometry in whole 8 x 32 tiles
 int ws_conv_supported(const ConvArgs &a)
 {
-    if (a.kdisable & 64) return 0;
+    if (a.kdisable & KOFF_CONV_WS) return 0;
     if (a.dtype == TDRN_F32 || a.Cin != 64 || a.Npad % 64 || a.Cout % 64) return 0;       // (Cout = the output tensor's padded channel count)
     if (a.W % 32 || a.H % 8) return 0;
     return patch_conv_supported(a) != 0;
@@ -710,7 +676,7 @@ int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
     if (units <= 0) return TDRN_OK;
     if (units >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
     p.units = (int)units;
-    if (p.units < grid) grid = ((p.units + 7) / 8) * 8;
+    if (p.units < grid) grid = persistent_grid(p.units);
     // below ~3/4 of the chip conv3x3_patch.hip's independent 256-pixel items spread better (small batches)
     if (p.units < 192) return TDRN_E_UNSUPPORTED;
 #ifdef TDRN_WS_STAMP

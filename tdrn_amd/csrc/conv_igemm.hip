@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "mfma_prims.h"
 
 #ifndef TDRN_IGEMM_PRIO
 #define TDRN_IGEMM_PRIO 0
@@ -39,40 +40,10 @@ struct ConvParams {
     int batch_minor, B;   // batch_minor: GEMM row m = (ho*Wo + wo)*B + b instead of (b*Ho + ho)*Wo + wo (see conv_igemm_kernel)
 };
 
-template <typename DT> struct Mma;
-template <> struct Mma<bf16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<f16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    // lane half h holds k = 4*(2kk+h)+j of the 128-byte row; A and B use the same map, so the
-    // four x2 MFMAs below cover each k exactly once.
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[j]), __uint_as_float(b[j]), c, 0, 0, 0);
-    }
-};
-
 // COH = agent-coherent access (the `sc1` cache-policy bit: served by / written through to the memory side, past the XCD's own
-// L2): what conv_chain_kernel uses for every tensor one of its tasks writes and another -- possibly on another XCD -- reads,
-// instead of agent-scope fences (a fence writes back / invalidates a whole L2: with ~3000 tasks a launch that was 3x slower
-// than the launches it replaces and slowed every concurrent kernel by 3-5x).
-template <bool COH = false>
-__device__ __forceinline__ void glds16(const char *src, char *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, COH ? 16 : 0);
-}
+// L2; lds_dma16_ptr<COH> of mfma_prims.h for the LDS-DMA): what conv_chain_kernel uses for every tensor one of its tasks writes
+// and another -- possibly on another XCD -- reads, instead of agent-scope fences (a fence writes back / invalidates a whole L2:
+// with ~3000 tasks a launch that was 3x slower than the launches it replaces and slowed every concurrent kernel by 3-5x).
 template <bool COH>
 __device__ __forceinline__ void st8(void *p, uint2 v)
 {
@@ -191,7 +162,7 @@ __device__ __forceinline__ void igemm_tile(const ConvParams &p, const int wg, co
 #pragma unroll
         for (int i = 0; i < PB; ++i) {
             const char *src = wbase + ((size_t)(n0 + i * RPP + lrow) * p.Ktot + kofs) * ES + lc16;
-            glds16(src, sb + (i * RPP + wave * 8) * 128);
+            lds_dma16_ptr(src, sb + (i * RPP + wave * 8) * 128);
         }
         const int dh = tr * p.dil, dw = tq * p.dil;
 #pragma unroll
@@ -199,7 +170,7 @@ __device__ __forceinline__ void igemm_tile(const ConvParams &p, const int wg, co
             const int hi = hi0[i] + dh, wi = wi0[i] + dw;
             const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
             const size_t off = (size_t)(pbase[i] + (hi * p.W + wi) * p.Cin + c0) * ES + lc16;
-            glds16<COH>(ok ? p.in + off : p.zero, sb + BN * 128 + (i * RPP + wave * 8) * 128);
+            lds_dma16_ptr<COH>(ok ? p.in + off : p.zero, sb + BN * 128 + (i * RPP + wave * 8) * 128);
         }
     };
     // taps that touch the image for at least one row of this tile (bit = tr*kw + tq); all ones without padding
@@ -257,7 +228,7 @@ __device__ __forceinline__ void igemm_tile(const ConvParams &p, const int wg, co
 #pragma unroll
             for (int ci = 0; ci < WC; ++ci)
 #pragma unroll
-                for (int pi = 0; pi < WP; ++pi) Mma<DT>::run(wf[ci], pf[pi], acc[ci][pi]);
+                for (int pi = 0; pi < WP; ++pi) Mma32<DT>::run(wf[ci], pf[pi], acc[ci][pi]);
         }
     };
 

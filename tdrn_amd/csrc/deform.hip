@@ -15,6 +15,7 @@
 
 #include "deform_sampler.h"
 #include "kernels.h"
+#include "mfma_prims.h"
 
 namespace tdrn {
 
@@ -42,24 +43,6 @@ struct DeformMulti {
     DeformParams p[kMaxDeformProblems];
     int block_start[kMaxDeformProblems + 1];
     int n;
-};
-
-template <typename DT> struct MmaD;
-template <> struct MmaD<bf16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaD<f16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaD<float> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[j]), __uint_as_float(b[j]), c, 0, 0, 0);
-    }
 };
 
 // 128 pixels x (NTL*32) couts per workgroup; wave w owns pixels [32w, 32w+32) and all cout tiles.
@@ -187,8 +170,7 @@ __global__ __launch_bounds__(256) void deform_gemm_kernel(const DeformMulti mp)
 #pragma unroll
         for (int i = 0; i < NTL; ++i) {
             const char *src = B.w + ((size_t)(i * RPP + lrow) * Ktot + kofs) * ES + lc16;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)(sb + (i * RPP + wave * 8) * 128), 16, 0, 0);
+            lds_dma16_ptr(src, sb + (i * RPP + wave * 8) * 128);
         }
         const int coffs = cc * CK * ES + lc16;
 #pragma unroll
@@ -251,7 +233,7 @@ __global__ __launch_bounds__(256) void deform_gemm_kernel(const DeformMulti mp)
 #pragma unroll
             for (int ci = 0; ci < NTL; ++ci) {
                 const u32x4 wf = *(const u32x4 *)(wsb + (ci * 32 + r32) * 128 + ch);
-                MmaD<DT>::run(wf, pf, acc[ci]);
+                Mma32<DT>::run(wf, pf, acc[ci]);
             }
         }
     };
@@ -616,11 +598,11 @@ __global__ __launch_bounds__(512, 4) void ygemm_k256_kernel(const YGemmMulti mp)
 
     // staging: a tile = 32 rows x 512 B = 16 pieces of 1 KiB (2 rows each); wave w issues pieces PPW w .. PPW w + PPW - 1.
     // LDS image linear; the 16-byte chunk c of row r is stored at chunk position c ^ (r & 31) (swizzle on the SOURCE address)
-    // The LDS-DMA goes out as inline asm (round 5): behind the builtin hipcc put an `s_waitcnt vmcnt(0)` in front of the first LDS read
+    // The LDS-DMA goes out as inline asm (lds_dma16, round 5): behind the builtin hipcc put an `s_waitcnt vmcnt(0)` in front of the first LDS read
     // of every tile -- it cannot tell the DMA's LDS writes from the tile being read -- which drained the NEXT tile's pieces (issued a few
     // instructions earlier) and every store in flight: the double buffer never overlapped anything (stamps: 2800 of a tile's 5500
     // cycles in the multiply phase, 16 MFMAs).  Completion is waited for by hand below, as before.
-    const unsigned smem_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)smem;
+    const unsigned smem_lds = lds_addr(smem);
     auto stage = [&](int t, int buf) {
         const long long mb = (long long)(t0 + t) * TP;   // (wave-uniform)
         const char *sb = p.x + (size_t)mb * 512;
@@ -631,11 +613,7 @@ __global__ __launch_bounds__(512, 4) void ygemm_k256_kernel(const YGemmMulti mp)
             int r = row;
             if (mb + r >= p.M) r = (int)(p.M - 1 - mb);  // (rows past the end re-read the last pixel; their results are not stored)
             const unsigned voff = (unsigned)(r * 512 + ((cpos ^ (row & 31)) << 4));
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(voff), "s"(sb), "s"(__builtin_amdgcn_readfirstlane(smem_lds + buf * TBYTES + piece * 1024))
-                         : "memory");
+            lds_dma16(sb, voff, __builtin_amdgcn_readfirstlane(smem_lds + buf * TBYTES + piece * 1024));
         }
     };
     stage(0, 0);
@@ -678,7 +656,7 @@ __global__ __launch_bounds__(512, 4) void ygemm_k256_kernel(const YGemmMulti mp)
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             const u32x4 a = *(const u32x4 *)(ab + (((2 * kk + hh) ^ r32) << 4));
-            MmaD<DT>::run(wf[kk], a, acc);
+            Mma32<DT>::run(wf[kk], a, acc);
         }
         // lane = pixel r32; register e = column (e & 3) + 8 (e >> 2) + 4 hh of a 32-column tile.  The tile goes through an LDS image
         // [pixel][256 columns] so that the stores are whole 128-byte lines (512 B per pixel row, 16 B per lane): written as
@@ -772,7 +750,7 @@ __global__ __launch_bounds__(512, 4) void ygemm_k256_v2_kernel(const YGemmMulti 
     if (nt <= 0) return;
     YG_STAMP_DECL
 
-    const unsigned smem_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)smem;
+    const unsigned smem_lds = lds_addr(smem);
     // (as above: 32 rows x 512 B, chunk c of row r at position c ^ (r & 31); `sb` = the tile's first row, `avail` = rows of the tensor
     // from there on -- rows past the end re-read the last one, their results are not stored; kept incrementally: the 64-bit index
     // arithmetic of the first version was ~60 scalar instructions per tile in front of two DMA instructions)
@@ -783,11 +761,7 @@ __global__ __launch_bounds__(512, 4) void ygemm_k256_v2_kernel(const YGemmMulti 
             const int row = 2 * piece + (lane >> 5), cpos = lane & 31;
             const int r = row < avail ? row : avail - 1;
             const unsigned voff = (unsigned)(r * 512 + ((cpos ^ (row & 31)) << 4));
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(voff), "s"(sb), "s"(__builtin_amdgcn_readfirstlane(smem_lds + buf * TBYTES + piece * 1024))
-                         : "memory");
+            lds_dma16(sb, voff, __builtin_amdgcn_readfirstlane(smem_lds + buf * TBYTES + piece * 1024));
         }
     };
     // the store trips of this wave: trip j carries (tap, 6-pixel group) number it = wave + 8 j of the slice's 3 x 6 from the image to Y
@@ -852,7 +826,7 @@ __global__ __launch_bounds__(512, 4) void ygemm_k256_v2_kernel(const YGemmMulti 
             }
             if (kk == 1 || kk == 6 || kk == 11) sv = carry_read((kk - 1) / 5, buf ^ 1);
             __builtin_amdgcn_sched_barrier(0);
-            MmaD<DT>::run(wf[kk], a[kk & 3], acc);
+            Mma32<DT>::run(wf[kk], a[kk & 3], acc);
             if (kk == 5 || kk == 10 || kk == 15) carry_store((kk - 5) / 5, rows_prev, sv);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -976,7 +950,7 @@ int launch_ygemm_multi(const YGemmProblem *pr, int n, int dtype, hipStream_t s, 
 #endif
     bool tapmajor = true;
     for (int i = 0; i < mp.n; ++i) tapmajor = tapmajor && mp.p[i].taps > 0;
-    if (!(kdisable & 128) && tapmajor) {
+    if (!(kdisable & KOFF_YGEMM_V2) && tapmajor) {
         if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_v2_kernel<bf16_t>), grid, dim3(512), 0, s, mp);
         else hipLaunchKernelGGL((ygemm_k256_v2_kernel<f16_t>), grid, dim3(512), 0, s, mp);
     } else {

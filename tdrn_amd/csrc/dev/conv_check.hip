@@ -1,8 +1,8 @@
 // dev/conv_check.hip -- developer harness (not part of libtdrn_hip.so, never shipped): runs one 3x3/s1/p1 layer through the
 // loader/consumer kernel (conv3x3_patch.hip) and through the all-waves-compute kernel (conv3x3_pp.hip) on the same random
 // operands, requires the outputs to be BIT-IDENTICAL (same K order per output element), and times both with hipEvents.  The kernel
-// of each arm is chosen with ConvArgs::kdisable, the bits the net's plan flags set (1: no conv3x3_pp, 2: no chained split, 64: no
-// conv3x3_ws).
+// of each arm is chosen with ConvArgs::kdisable, the KOFF_* switches the net's plan flags set (KOFF_CONV_PP, KOFF_PP_SK,
+// KOFF_CONV_WS).
 //   make -C tdrn_amd/csrc dev      ->  tdrn_amd/csrc/_build/conv_check
 //   conv_check [B H W Cin Cout relu dtype(1=bf16,2=f16) iters]   (no arguments: the layer list of the 320 / 512 nets)
 //   conv_check ws [B H W Cout fuse dtype iters]                  (conv3x3_patch vs conv3x3_ws, pooled output)
@@ -71,7 +71,7 @@ static int run_case(int B, int H, int W, int Cin, int Cout, int relu, int dtype,
     CK(hipMalloc(&sk_ws, conv_pp_sk_bytes()));
     CK(hipMemset(sk_ws, 0xFF, conv_pp_sk_bytes()));      // (poisoned: the launcher must zero its flags itself)
     for (int k = 0; k < 3; ++k) {                        // 0: conv3x3_patch, 1: conv3x3_pp whole items, 2: conv3x3_pp chained split
-        a.kdisable = k == 0 ? 1 : (k == 1 ? 2 : 0);
+        a.kdisable = k == 0 ? KOFF_CONV_PP : (k == 1 ? KOFF_PP_SK : 0);
         a.sk_ws = k == 2 ? sk_ws : nullptr;
         a.sk_flags_zero = false;                          // first launch: the launcher's own memset node
         a.out = dout[k];
@@ -162,7 +162,7 @@ static int run_case_ws(int B, int H, int W, int Cout, int fuse, int dtype, int i
     double us[2] = {0, 0};
     int rcs[2] = {0, 0};
     for (int k = 0; k < 2; ++k) {                        // 0: conv3x3_patch, 1: conv3x3_ws
-        a.kdisable = k ? 0 : 64;
+        a.kdisable = k ? 0 : KOFF_CONV_WS;
         rcs[k] = k ? launch_conv3x3_ws(a, dpool[k], s) : launch_conv3x3_patch(a, dpool[k], s);
         if (rcs[k] != TDRN_OK) break;
         CK(hipStreamSynchronize(s));

@@ -6,6 +6,10 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "../mfma_prims.h"
+
+using namespace tdrn;
+
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(2); } } while (0)
 
 struct P { const char *src; unsigned row_stride; unsigned table_bytes; unsigned cu_stride; int iters; };
@@ -13,13 +17,10 @@ struct P { const char *src; unsigned row_stride; unsigned table_bytes; unsigned 
 template <int FORM> __device__ __forceinline__ void piece(const char *sbase, unsigned voff, unsigned lds_dst, char *lds_ptr)
 {
     if constexpr (FORM == 0) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(sbase + voff),
-                                         (__attribute__((address_space(3))) void *)lds_ptr, 16, 0, 0);
+        lds_dma16_ptr(sbase + voff, lds_ptr);
     } else if constexpr (FORM == 1) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-    } else {
+        lds_dma16(sbase, voff, lds_dst);
+    } else {                                            // (the kernels' form minus the M0 save / restore: what the restore costs)
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
     }
 }
@@ -54,8 +55,6 @@ template <int FORM, int SHAPE, int K> __global__ __launch_bounds__(512, 2) void 
 
 // the conv3x3_pp skeleton: two wave groups alternate between barriers; per step a wave issues 3 pieces in one interval and 2 in
 // another, then waits vmcnt(2).  MFMA = 1: 16 bare MFMAs in the issuing intervals (4 between pieces), as the kernel does.
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short i16x8;
 template <int MFMA, int NBAR> __global__ __launch_bounds__(512, 2) void pp_skeleton(const P p, float *sink)
 {
     __shared__ __attribute__((aligned(16))) char smem[128 * 1024];
@@ -68,10 +67,14 @@ template <int MFMA, int NBAR> __global__ __launch_bounds__(512, 2) void pp_skele
     unsigned cur = (unsigned)wave * 5u * piece_bytes;
     f32x16 acc[8];
     for (int i = 0; i < 8; ++i) for (int j = 0; j < 16; ++j) acc[i][j] = 0.f;
-    i16x8 a, b;
-    for (int j = 0; j < 8; ++j) { a[j] = (short)(lane * 3 + j); b[j] = (short)(lane + 7 * j); }
+    u32x4 a, b;
+    {
+        i16x8 a16, b16;
+        for (int j = 0; j < 8; ++j) { a16[j] = (short)(lane * 3 + j); b16[j] = (short)(lane + 7 * j); }
+        a = __builtin_bit_cast(u32x4, a16); b = __builtin_bit_cast(u32x4, b16);
+    }
 #define BAR() do { __builtin_amdgcn_sched_barrier(0); if (NBAR) __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MM4(o) do { if (MFMA) { for (int q = 0; q < 4; ++q) acc[(o) + q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[(o) + q], 0, 0, 0); } __builtin_amdgcn_sched_barrier(0); } while (0)
+#define MM4(o) do { if (MFMA) { for (int q = 0; q < 4; ++q) Mma32<bf16_t>::run(a, b, acc[(o) + q]); } __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PIECE(j) do { const int slot = (wave * 16 + (j)) * 1024; piece<2>(base, cur + lane_off, __builtin_amdgcn_readfirstlane(lds0 + slot), smem + slot); cur += piece_bytes; __builtin_amdgcn_sched_barrier(0); } while (0)
     if (grp == 1) BAR();
     for (int i = 0; i < p.iters; ++i) {
@@ -95,7 +98,6 @@ template <int MFMA, int NBAR> __global__ __launch_bounds__(512, 2) void pp_skele
     if (t == 12345.f) sink[threadIdx.x] = t + smem[threadIdx.x];
 }
 // schedule B of conv3x3_pp: load segments = 12 ds_read_b128 (+ 3 / 2 pieces), multiply segments = 16 bare MFMAs
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 template <int DMA, int READS> __global__ __launch_bounds__(512, 2) void pp_skeleton2(const P p, float *sink)
 {
     __shared__ __attribute__((aligned(16))) char smem[150 * 1024];
@@ -117,7 +119,7 @@ template <int DMA, int READS> __global__ __launch_bounds__(512, 2) void pp_skele
         for (int ci = 0; ci < 4; ++ci) fr[k2 * 6 + ci] = *(const u32x4 *)(smem + ((ra ^ kx) + ci * 4096)); \
         fr[k2 * 6 + 4] = *(const u32x4 *)(smem + (rp ^ kx)); fr[k2 * 6 + 5] = *(const u32x4 *)(smem + ((rp + 4096) ^ kx)); } } __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PC(j) do { if (DMA) { const int slot = 88 * 1024 + ((i & 1) * 32768) + grp * 16384 + ((wave & 3) + 4 * ((j) & 3)) * 1024; piece<2>(base, cur + lane_off, __builtin_amdgcn_readfirstlane(lds0 + slot), smem + slot); cur += piece_bytes; } __builtin_amdgcn_sched_barrier(0); } while (0)
-#define MM16() do { __builtin_amdgcn_s_setprio(1); for (int k2 = 0; k2 < 2; ++k2) for (int q = 0; q < 8; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, fr[k2 * 6 + (q >> 1)]), __builtin_bit_cast(i16x8, fr[k2 * 6 + 4 + (q & 1)]), acc[q], 0, 0, 0); __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define MM16() do { __builtin_amdgcn_s_setprio(1); for (int k2 = 0; k2 < 2; ++k2) for (int q = 0; q < 8; ++q) Mma32<bf16_t>::run(fr[k2 * 6 + (q >> 1)], fr[k2 * 6 + 4 + (q & 1)], acc[q]); __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0); } while (0)
     for (int j = 0; j < 12; ++j) fr[j] = u32x4{(unsigned)lane * 0x01010101u + j, 0x3c003c00u, 0x3c003c00u + j, 0x40004000u};
     if (grp == 1) BAR2();
     for (int i = 0; i < p.iters; ++i) {

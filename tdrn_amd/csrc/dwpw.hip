@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "mfma_prims.h"
 
 namespace tdrn {
 
@@ -42,35 +43,6 @@ struct DwPwParams {
 
 namespace {
 
-template <typename DT> struct MmaDP;
-template <> struct MmaDP<bf16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0); }
-};
-template <> struct MmaDP<f16_t> {
-    __device__ static __forceinline__ void run(const u32x4 &a, const u32x4 &b, f32x16 &c)
-    { c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
-};
-
-// (see conv3x3_pp.hip: inline asm so that hipcc's waitcnt pass neither sees nor drains the LDS-DMA queue)
-__device__ __forceinline__ void dp_glds16(const char *sbase, unsigned voff, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned dp_lds_addr(const void *p)
-{
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)p;
-}
-#define DP_BAR()                                  \
-    do {                                          \
-        __builtin_amdgcn_sched_barrier(0);        \
-        __builtin_amdgcn_s_barrier();             \
-        __builtin_amdgcn_sched_barrier(0);        \
-    } while (0)
 #define DP_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
 
 constexpr int kDPSlots = 44;                      // 8-row LDS-DMA pieces per patch buffer (352 rows)
@@ -104,11 +76,6 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
     __shared__ __attribute__((aligned(16))) char smem[LDS];
 
     const int lane = threadIdx.x & 63;
-    auto opaque_lane = [&]() -> int {                   // (see conv3x3_pp.hip: keeps hipcc from hoisting -- and spilling -- lane constants)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        return ln;
-    };
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave >> 2;                          // cout half
     const int cw = wave & 3;                            // pixel quarter: pixels [64*cw, 64*cw + 64)
@@ -116,38 +83,25 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
 
     // ---- work distribution: every XCD label (blockIdx % 8) owns a contiguous range of items; cout-tile-major numbering
     // (item = nt * m_tiles + mt): an XCD's range needs one cout tile's weights
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per_xcd = (p.items + 7) >> 3, istride = ((int)gridDim.x + 7) >> 3;
-    int avail = p.items - xcd * per_xcd;
-    avail = avail < per_xcd ? avail : per_xcd;
-    avail = avail < 0 ? 0 : avail;
-    const int n_items = avail > slot ? (avail - slot + istride - 1) / istride : 0;
+    const XcdItems xi = xcd_items(p.items);
+    const int n_items = xi.n_items(), istride = xi.istride;
     if (n_items == 0) return;                           // (whole workgroup)
-    const int item0 = xcd * per_xcd + slot;
+    const int item0 = xi.item0();
     const int RS = TW ? TW + 2 : p.W;                   // patch row stride of one image row
 
     // =========================== patch staging (as conv3x3_pp.hip) ===========================
     int pt_b = 0, pt_y0 = 0, pt_x0 = 0, pt_j0 = 0;
     auto mt_of = [&](int item) -> int { return item % p.m_tiles; };
     auto nt_of = [&](int item) -> int { return item / p.m_tiles; };
-    auto patch_tile = [&](int item) {
-        const int mt = mt_of(item);
-        if (TW) {
-            const int b = mt / p.tiles_per_img, tt = mt - b * p.tiles_per_img;
-            const int ty = tt / p.tiles_x, tx = tt - ty * p.tiles_x;
-            pt_b = __builtin_amdgcn_readfirstlane(b); pt_y0 = __builtin_amdgcn_readfirstlane(ty * TH - 1); pt_x0 = __builtin_amdgcn_readfirstlane(tx * TW - 1);
-        } else {
-            pt_j0 = __builtin_amdgcn_readfirstlane(mt * 256 - p.W - 1);
-        }
-    };
-    const unsigned smem_lds = __builtin_amdgcn_readfirstlane(dp_lds_addr(smem));
+    auto patch_tile = [&](int item) { patch_origin(mt_of(item), p.tiles_per_img, p.tiles_x, TH, TW, p.W, pt_b, pt_y0, pt_x0, pt_j0); };
+    const unsigned smem_lds = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     int pp_yx = 0;
     // one 8-row piece of the patch: rows outside the image are zeroed by an LDS store of the lanes concerned, the DMA runs with
     // those lanes off; returns 1 when a DMA was issued (the caller counts them for its vmcnt)
     auto patch_piece = [&](int j, unsigned ccoff, int dstbuf_off) -> int {
         const int q = wave + 8 * j;
         if (q >= kDPSlots) return 0;                    // (wave-uniform)
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int lrow = ln >> 3, pc = ln & 7;
         const unsigned lc = (unsigned)((pc ^ ((4 * wave + (lrow >> 1)) & 7)) << 4) + ccoff;
         const unsigned rowbytes = (unsigned)(p.Cin * ES);
@@ -180,7 +134,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
         }
         const bool any = __builtin_amdgcn_ballot_w64(ok) != 0ull;
         if (any) {
-            if (ok) dp_glds16(p.in, off + lc, __builtin_amdgcn_readfirstlane(smem_lds + piece));
+            if (ok) lds_dma16(p.in, off + lc, __builtin_amdgcn_readfirstlane(smem_lds + piece));
             return 1;
         }
         return 0;
@@ -194,17 +148,17 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
         for (int k = 0; k < 4; ++k) {
             unsigned w = wo;
             asm volatile("" : "+v"(w));
-            dp_glds16(p.w + off, w + k * wstep, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + grp * (BN * 64) + (cw + 4 * k) * 1024));
+            lds_dma16(p.w + off, w + k * wstep, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + grp * (BN * 64) + (cw + 4 * k) * 1024));
         }
     };
     // the chunk's depthwise weights: three 1-KiB pieces = rows of 64 fp32 (taps 0..8, the bias, two rows of padding), by wave 1
     auto dw_pieces = [&](int c, int par) {
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const int t = 4 * q + (ln >> 4);
             const unsigned src = (t < 9 ? (unsigned)(t * p.Cin * 4) : p.bdw_off) + (unsigned)(c * 256 + (ln & 15) * 16);
-            if (t < 10) dp_glds16(p.wdw, src, __builtin_amdgcn_readfirstlane(smem_lds + OFF_DW + par * 3072 + q * 1024));
+            if (t < 10) lds_dma16(p.wdw, src, __builtin_amdgcn_readfirstlane(smem_lds + OFF_DW + par * 3072 + q * 1024));
         }
     };
 
@@ -312,7 +266,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
 
     // ---- epilogue of one item (wave-private staging strip in the dead patch buffer -> whole-line stores) ----------
     auto epilogue = [&](char *stg) {
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int r32 = ln & 31, hh = ln >> 5;
         constexpr int CPR = BNH * ES / 16, RPI = 64 / CPR;
         const int my_ch = ln % CPR, my_row = ln / CPR;
@@ -368,7 +322,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
 
     // the 32 MFMAs of one chunk: K slices 0..3 in order, operand fragments straight from LDS (8 weight + 4 pixel reads per half)
     auto mma_phase = [&]() {
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int r32 = ln & 31, hh = ln >> 5;
         const unsigned wa = (unsigned)(OFF_W + grp * (BN * 64) + r32 * 128 + ((hh ^ ((r32 >> 1) & 7)) << 4));
         unsigned pa[2];
@@ -393,7 +347,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
 #pragma unroll
                 for (int ci = 0; ci < WC; ++ci)
 #pragma unroll
-                    for (int pt = 0; pt < 2; ++pt) MmaDP<DT>::run(wf[ci][k2], pf[pt][k2], acc[ci][pt]);
+                    for (int pt = 0; pt < 2; ++pt) Mma32<DT>::run(wf[ci][k2], pf[pt][k2], acc[ci][pt]);
         }
     };
 
@@ -405,7 +359,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
     if (wave == 1) dw_pieces(0, 0);
     if (wave == 2 && lane < 8) *(u32x4 *)(smem + OFF_Z + lane * 16) = u32x4{0u, 0u, 0u, 0u};
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    DP_BAR();
+    wg_barrier();
     setup_item(cur_item);
     zero_acc();
     int pbuf = 0, par = 0;
@@ -441,7 +395,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
             case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
             default: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
         }
-        DP_BAR();
+        wg_barrier();
         // ---- pointwise: 32 MFMAs per wave
         __builtin_amdgcn_s_setprio(1);
         mma_phase();
@@ -459,7 +413,7 @@ __global__ __launch_bounds__(512, 2) void dwpw_kernel(const DwPwParams p)
         pbuf ^= 1; par ^= 1;
         // everything issued for the next unit has landed, my LDS reads of this chunk are done -> (barrier) everybody's
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        DP_BAR();
+        wg_barrier();
     }
 }
 
@@ -507,21 +461,14 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
     __shared__ __attribute__((aligned(16))) char smem[LDS];
 
     const int lane = threadIdx.x & 63;
-    auto opaque_lane = [&]() -> int {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        return ln;
-    };
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = wave >> 2, cw = wave & 3;
     const int nchunks = p.Cin / 64;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per_xcd = (p.items + 7) >> 3, istride = ((int)gridDim.x + 7) >> 3;
-    int avail = p.items - xcd * per_xcd;
-    avail = avail < per_xcd ? avail : per_xcd;
-    avail = avail < 0 ? 0 : avail;
+    const XcdItems xi = xcd_items(p.items);
+    const int slot = xi.slot, istride = xi.istride, avail = xi.avail;
+    // (xi.n_items() and xi.item0() written out: behind the member calls hipcc lays this kernel's tail-split code out differently)
     int n_full = avail > slot ? (avail - slot + istride - 1) / istride : 0;
-    const int item0 = xcd * per_xcd + slot;
+    const int item0 = xi.xcd * xi.per_xcd + slot;
     // ---- tail split (round 6; conv3x3_patch.hip has the same idea).  800 items on 256 workgroups are 3.125 rounds: after three rounds an
     // XCD has 4 items left for its 32 workgroups and the launch's last quarter runs on an eighth of the chip (the five 512 -> 512 layers of
     // config 4, 256 -> 512, ...).  When the XCD's last round is at most a quarter (half) filled, its items are cut ALONG THE COUTS into
@@ -536,7 +483,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
             n_full = full;
             if (slot < f * rem) {
                 n_tail = 1;
-                tail_item = xcd * per_xcd + full * istride + slot / f;
+                tail_item = xi.xcd * xi.per_xcd + full * istride + slot / f;
                 tail_wcn = WC / f;
                 tail_c0 = (slot % f) * (BN / f);
             }
@@ -548,7 +495,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
     auto seq_item = [&](int i) -> int { return i < n_full ? item0 + i * istride : tail_item; };
     auto seq_c0 = [&](int i) -> int { return i < n_full ? 0 : tail_c0; };
     auto seq_wcn = [&](int i) -> int { return i < n_full ? WC : tail_wcn; };
-    const unsigned smem_lds = __builtin_amdgcn_readfirstlane(dp_lds_addr(smem));
+    const unsigned smem_lds = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     // item numbering: pixel-tile major -- the cout tiles of one pixel tile are neighbouring items of ONE XCD, dealt to
     // neighbouring workgroups at the same time, so the pixel rows (the operand that streams from HBM) cross the fabric once; the
     // whole weight matrix (<= 2 MB) stays in every XCD's L2.  (cout-tile major, conv3x3_pp.hip's choice for its 9x bigger weight
@@ -563,7 +510,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
 #ifdef TDRN_DEV_ABLATE
         if (p.ablate & 1) return;
 #endif
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int lrow = ln >> 3, pc = ln & 7;
         const int mt = mt_of(seq_item(i));
         const unsigned lc = (unsigned)((pc ^ ((4 * wave + (lrow >> 1)) & 7)) << 4) + (unsigned)(c * 128);
@@ -571,14 +518,14 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
         for (int k = 0; k < 4; ++k) {
             int m = mt * 256 + (wave + 8 * k) * 8 + lrow;
             m = m < p.M ? m : p.M - 1;
-            dp_glds16(p.in, (unsigned)m * rowb + lc, __builtin_amdgcn_readfirstlane(smem_lds + abuf * ABYTES + (wave + 8 * k) * 1024));
+            lds_dma16(p.in, (unsigned)m * rowb + lc, __builtin_amdgcn_readfirstlane(smem_lds + abuf * ABYTES + (wave + 8 * k) * 1024));
         }
     };
     auto stage_w = [&](int i, int c, int wbuf) {
 #ifdef TDRN_DEV_ABLATE
         if (p.ablate & 2) return;
 #endif
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int lrow = ln >> 3, pc = ln & 7;
         const int wcn = seq_wcn(i);                     // my group's rows: 32 wcn of them, behind the (sub-)item's first cout
         const unsigned woff = (unsigned)__builtin_amdgcn_readfirstlane((nt_of(seq_item(i)) * BN + seq_c0(i)) * p.Cin * ES + c * 128);
@@ -586,7 +533,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < wcn)
-                dp_glds16(p.w + woff, wo + (unsigned)k * (32u * rowb), __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + wbuf * WBYTES + grp * (WBYTES / 2) + (cw + 4 * k) * 1024));
+                lds_dma16(p.w + woff, wo + (unsigned)k * (32u * rowb), __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + wbuf * WBYTES + grp * (WBYTES / 2) + (cw + 4 * k) * 1024));
     };
     const int n_units = n_items * nchunks;
     // (item, chunk) of unit u + d, advanced incrementally (no division in the loop)
@@ -611,7 +558,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
 #ifdef TDRN_DEV_ABLATE
         if (p.ablate & 4) return;
 #endif
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int r32 = ln & 31, hh = ln >> 5;
         const unsigned wa = (unsigned)(OFF_W + wbuf * WBYTES + grp * (WBYTES / 2) + r32 * 128 + ((hh ^ ((r32 >> 1) & 7)) << 4));
         unsigned pa[2];
@@ -637,7 +584,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
 #pragma unroll
                 for (int ci = 0; ci < WCN; ++ci)
 #pragma unroll
-                    for (int pt = 0; pt < 2; ++pt) MmaDP<DT>::run(wf[ci][k2], pf[pt][k2], acc[ci][pt]);
+                    for (int pt = 0; pt < 2; ++pt) Mma32<DT>::run(wf[ci][k2], pf[pt][k2], acc[ci][pt]);
         }
     };
     // my group's 128 biases: one f32x4 per lane (lanes 0..31), fetched BEFORE the item's last MFMA phase (the latency hides under
@@ -645,7 +592,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
     // rounds -- eight rounds, sixteen loads each -- the epilogue cost 30 us of a 105-us launch.)
     f32x4 bias4 = f32x4{0.f, 0.f, 0.f, 0.f};
     auto fetch_bias = [&](int i) {
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         const int wcn = seq_wcn(i);
         if (ln < 8 * wcn) bias4 = *(const f32x4 *)(p.bias + nt_of(seq_item(i)) * BN + seq_c0(i) + grp * 32 * wcn + 4 * ln);
     };
@@ -662,7 +609,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
         const int item = seq_item(i);
         char *base = (wave < 4 ? smem + dead_abuf * ABYTES : smem + OFF_W + dead_wbuf * WBYTES) + (wave & 3) * (SBYTES + 512);
         char *stg = base, *sbias = base + SBYTES;
-        const int ln = opaque_lane();
+        const int ln = opaque(lane);
         if (ln < 32) *(f32x4 *)(sbias + ln * 16) = bias4;
         DP_LGKM0();
         __builtin_amdgcn_wave_barrier();
@@ -729,7 +676,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
         // unit u's operands have landed: its weights were issued BEFORE the (younger) pixel pieces of unit u+1
         if (u + 1 < n_units) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        DP_BAR();                                       // ... everybody's; and every wave has left the MFMAs of unit u-1
+        wg_barrier();                                    // ... everybody's; and every wave has left the MFMAs of unit u-1
         // (round 6: wave group 1 issues a unit's eight LDS-DMA pieces between its two MFMA halves, group 0 in front of them, so the two
         // waves of a SIMD no longer issue and multiply in lockstep: -2 % on the 8-chunk layers, -9...-10 % on the 16-chunk ones (512 ->
         // 1024, 1024 -> 1024 at 20 x 20); same arithmetic, same bits.  Round 4 had moved only the pixel pieces behind ALL the MFMAs: nothing.)
@@ -750,7 +697,7 @@ __global__ __launch_bounds__(512, 2) void pw1x1_kernel(const Pw1x1Params p)
         __builtin_amdgcn_s_setprio(0);
         if (last) {
             DP_LGKM0();
-            DP_BAR();                                   // every wave has read unit u's pixels: that buffer is the staging area now
+            wg_barrier();                                // every wave has read unit u's pixels: that buffer is the staging area now
             epilogue(wtag, q0.item, abuf, wbuf);
             zero_acc();
             DP_LGKM0();
@@ -802,18 +749,11 @@ int launch_dwpw(const DwPwArgs &a, hipStream_t s)
     p.relu_dw = a.relu_dw; p.relu = a.relu;
     p.M = a.B * a.H * a.W;
     const int tw = mode > 0 ? mode : 0;
-    if (tw) {
-        p.tiles_x = a.W / tw;
-        p.tiles_per_img = p.tiles_x * (a.H / (256 / tw));
-        p.m_tiles = a.B * p.tiles_per_img;
-    } else {
-        p.tiles_x = 0; p.tiles_per_img = 0;
-        p.m_tiles = cdiv(p.M, 256);
-    }
+    conv_tiles(a.B, a.H, a.W, tw, 256, p.tiles_x, p.tiles_per_img, p.m_tiles);
     p.n_tiles = a.Npad / 256;
     p.items = p.m_tiles * p.n_tiles;
     if (p.items <= 0) return TDRN_OK;
-    const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
+    const int grid = persistent_grid(p.items);
 #define DP_LAUNCH(DT)                                                                                        \
     do {                                                                                                     \
         if (tw == 0) hipLaunchKernelGGL((dwpw_kernel<DT, 0>), dim3(grid), dim3(512), 0, s, p);              \
@@ -831,7 +771,7 @@ int launch_dwpw(const DwPwArgs &a, hipStream_t s)
 // 256-groups, a plain NHWC output tensor, no residual, no split-K, and enough items to fill the chip
 int pw1x1_supported(const ConvArgs &a)
 {
-    if ((a.kdisable & 8) || a.dtype == TDRN_F32) return 0;
+    if ((a.kdisable & KOFF_PW1X1) || a.dtype == TDRN_F32) return 0;
     if (a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0 || a.phases != 1 || a.res || a.out_f32 || a.splitk > 1 || a.fuse_x) return 0;
     if (a.Ho != a.H || a.Wo != a.W || a.Cin % 64 || a.Npad % 256 || a.Cout > a.Npad) return 0;
     if (a.o_rs != (long long)a.Wo * a.o_cs || a.o_bs != (long long)a.Ho * a.Wo * a.o_cs || a.o_base) return 0;
@@ -854,8 +794,8 @@ int launch_pw1x1(const ConvArgs &a, hipStream_t s)
     static int ablate = -1;
     if (ablate < 0) ablate = dev_ablate_env("TDRN_PW_ABLATE");     // (developer builds only: common.h)
     p.ablate = ablate;
-    p.tail_split = !(a.kdisable & 1024);             // (TDRN_PLAN_NO_PATCH_TAIL)
-    const int grid = p.items >= 256 ? 256 : ((p.items + 7) / 8) * 8;
+    p.tail_split = !(a.kdisable & KOFF_PATCH_TAIL);             // (TDRN_PLAN_NO_PATCH_TAIL)
+    const int grid = persistent_grid(p.items);
     if (a.dtype == TDRN_BF16) hipLaunchKernelGGL((pw1x1_kernel<bf16_t>), dim3(grid), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((pw1x1_kernel<f16_t>), dim3(grid), dim3(512), 0, s, p);
     return hip_status(hipGetLastError());

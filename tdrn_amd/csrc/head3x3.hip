@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "mfma_prims.h"
 
 namespace tdrn {
 
@@ -36,32 +37,12 @@ constexpr int kH3PatchRows = 256 + 2 * kH3MaxW + 2 + 6;          // (+6: whole 8
 constexpr int kH3PatchBytes = ((kH3PatchRows + 7) / 8) * 1024;
 constexpr int kH3WBytes = 9 * 16 * 128;
 
-__device__ __forceinline__ void h3_glds16(const char *sbase, unsigned voff, unsigned lds_dst)
-{
-    // (inline asm: hipcc neither sees nor drains the LDS-DMA queue -- conv3x3_pp.hip)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-
-template <typename DT> struct Mma16;
-template <> struct Mma16<bf16_t> {
-    __device__ static __forceinline__ f32x4 run(const u32x4 &a, const u32x4 &b, const f32x4 &c)
-    { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b), c, 0, 0, 0); }
-};
-template <> struct Mma16<f16_t> {
-    __device__ static __forceinline__ f32x4 run(const u32x4 &a, const u32x4 &b, const f32x4 &c)
-    { return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
-};
-
 template <typename DT>
 __global__ __launch_bounds__(512, 2) void head3x3_kernel(const Head3Params p)
 {
     // LDS: two patch buffers, two weight buffers, one zeroed row
     __shared__ __attribute__((aligned(16))) char smem[2 * kH3PatchBytes + 2 * kH3WBytes + 128];
-    const unsigned smem_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)smem;
+    const unsigned smem_lds = lds_addr(smem);
     constexpr int OFF_W = 2 * kH3PatchBytes, OFF_Z = OFF_W + 2 * kH3WBytes;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = (int)blockIdx.x / p.tiles_per_img, tile = (int)blockIdx.x - b * p.tiles_per_img;
@@ -80,14 +61,14 @@ __global__ __launch_bounds__(512, 2) void head3x3_kernel(const Head3Params p)
             const int r = 8 * j + r8, g = g0 + r;
             const bool ok = g >= 0 && g < HW;
             // rows above / below the image: an ordinary LDS store of zeros by the lanes concerned (the LDS-DMA runs with them switched off)
-            if (ok) h3_glds16(img, (unsigned)(((size_t)g * p.Cin + cc * 64) * 2 + ((cpos ^ (r & 7)) << 4)),
+            if (ok) lds_dma16(img, (unsigned)(((size_t)g * p.Cin + cc * 64) * 2 + ((cpos ^ (r & 7)) << 4)),
                               __builtin_amdgcn_readfirstlane(smem_lds + buf * kH3PatchBytes + j * 1024));
             else *(u32x4 *)(smem + buf * kH3PatchBytes + j * 1024 + lane * 16) = u32x4{0u, 0u, 0u, 0u};
         }
         for (int j = wave; j < 18; j += 8) {              // weight rows (tap, column): 144 rows of 128 B = 18 pieces
             const int row = 8 * j + r8, tap = row >> 4, co = row & 15;
             const unsigned voff = (unsigned)(((size_t)(co * 9 + tap) * p.Cin + cc * 64) * 2 + ((cpos ^ (row & 7)) << 4));
-            h3_glds16(p.w, voff, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + buf * kH3WBytes + j * 1024));
+            lds_dma16(p.w, voff, __builtin_amdgcn_readfirstlane(smem_lds + OFF_W + buf * kH3WBytes + j * 1024));
         }
     };
     // ---- my lanes' roles ----
@@ -164,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void head3x3_kernel(const Head3Params p)
 
 int head3x3_supported(const ConvArgs &a)
 {
-    if (a.kdisable & 256) return 0;
+    if (a.kdisable & KOFF_HEAD3X3) return 0;
     if (a.dtype == TDRN_F32 || a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return 0;
     if (a.phases != 1 || !a.out_f32 || a.res || a.fuse_x || a.fuse_x8) return 0;
     if (a.Ho != a.H || a.Wo != a.W || a.W > kH3MaxW || a.W < 2) return 0;

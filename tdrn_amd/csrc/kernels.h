@@ -15,6 +15,23 @@ constexpr size_t kZeroPageBytes = 256;
 // idempotent, so a race between threads only repeats the call).  (layers.hip)
 int allow_big_lds(const void *kernel);
 
+// Kernel-choice switches of a launch (ConvArgs::kdisable, the kdisable argument of launch_dwconv3 / launch_ygemm_multi): each
+// turns one kernel or one of its work-distribution schemes OFF.  Plan::build (net_plan.hip) sets them from
+// tdrn_net_config.plan_flags; apart from KOFF_HEAD3X3 (another fp32 K order) the output bits are the same either way.
+enum KernelOff {
+    KOFF_CONV_PP = 1,          // TDRN_PLAN_NO_CONV_PP: conv3x3_pp.hip's layers stay on conv3x3_patch.hip
+    KOFF_PP_SK = 2,            // TDRN_PLAN_NO_PP_SK: conv3x3_pp.hip runs whole items only (no chained split)
+    KOFF_CONV_PATCH = 4,       // TDRN_PLAN_NO_CONV_PATCH: neither 3x3 direct-conv kernel (everything on conv_igemm.hip)
+    KOFF_PW1X1 = 8,            // TDRN_PLAN_NO_PW1X1: the wide 1x1 convs stay on conv_igemm.hip (not dwpw.hip pw1x1_kernel)
+    KOFF_DW_SLIDE = 16,        // TDRN_PLAN_NO_DW_SLIDE: depthwise 3x3 on the one-row strip kernel, not the sliding-window one
+    KOFF_DW_STRIP_SMALL = 32,  // TDRN_PLAN_DW_SLIDE_ALL: no strip kernel at small batches either (sliding-window, 8-row segments, always)
+    KOFF_CONV_WS = 64,         // TDRN_PLAN_NO_CONV_WS: the pooled Cin = 64 layer stays on conv3x3_patch.hip (not conv3x3_ws.hip)
+    KOFF_YGEMM_V2 = 128,       // TDRN_PLAN_NO_YGEMM_V2: the heads' transform GEMM on ygemm_k256_kernel's older schedule
+    KOFF_HEAD3X3 = 256,        // TDRN_PLAN_NO_HEAD3X3: the narrow fp32 3x3 heads stay on conv_igemm.hip (not head3x3.hip)
+    KOFF_TS_RANGES = 512,      // TDRN_PLAN_TS_ONE_RANGE: transform-then-sample heads take the whole batch as one range
+    KOFF_PATCH_TAIL = 1024,    // TDRN_PLAN_NO_PATCH_TAIL: conv3x3_patch.hip and pw1x1_kernel run whole items only (no tail split)
+};
+
 // ---------------------------------------------------------------------------------------------
 // Dense convolution as implicit GEMM on MFMA (conv_igemm.hip).
 //   in  : NHWC [B][H][W][Cin]      (DT; Cin a multiple of the 128-byte K-step)
@@ -44,9 +61,7 @@ struct ConvArgs {
     float fuse_mean[3] = {0.f, 0.f, 0.f};
     void *sk_ws = nullptr;          // conv3x3_pp.hip: scratch of conv_pp_sk_bytes() for the chained split (one launch at a time), or null
     bool sk_flags_zero = false;     // the first 1024 bytes of sk_ws are zero on entry (every launch leaves them zero): no memset node
-    // kernel-choice switches of this launch (tdrn_net_config.plan_flags TDRN_PLAN_NO_CONV_PP / _NO_PP_SK / _NO_CONV_PATCH):
-    // bit 0: not conv3x3_pp.hip, bit 1: no chained split, bit 2: neither 3x3 direct-conv kernel, bit 3: not pw1x1 (dwpw.hip), bit 6: not
-    // conv3x3_ws.hip (TDRN_PLAN_NO_CONV_WS).  Same output bits either way.
+    // kernel-choice switches of this launch: an OR of KOFF_* (above).  Same output bits either way.
     int kdisable = 0;
     // host-visible status words (pinned, device-mapped; tdrn_net_check): [0] <- 1 when a chained-split poll runs out,
     // [1] <- 1 when a poll of the chain launch does.  Null: a timed-out poll is not reported (dev harness only).
@@ -64,7 +79,7 @@ size_t conv_chain_ctr_bytes();
 int launch_conv_chain(const ChainLayer *layers, int n, unsigned *ctr, hipStream_t s, unsigned *status = nullptr);
 int conv_splitk_choice(const ConvArgs &a);          // 1 = no split
 size_t conv_splitk_bytes(const ConvArgs &a, int splits);
-// narrow 3x3/s1/p1 heads with fp32 output (<= 16 columns: the ARM loc heads), head3x3.hip; kdisable bit 8 (TDRN_PLAN_NO_HEAD3X3) declines
+// narrow 3x3/s1/p1 heads with fp32 output (<= 16 columns: the ARM loc heads), head3x3.hip; KOFF_HEAD3X3 declines
 int head3x3_supported(const ConvArgs &a);
 int launch_head3x3(const ConvArgs &a, hipStream_t s);
 // warp-specialised 3x3/s1/p1 kernel (conv3x3_patch.hip); out_pool = optional fused MaxPool2d(2,2) output
@@ -72,16 +87,27 @@ int patch_conv_supported(const ConvArgs &a);   // 0 = no, 32/16 = 2-D tiles, -1 
 int patch_conv_takes(const ConvArgs &a);       // launch_conv hands this (unsplit) layer to launch_conv3x3_patch (conv_igemm.hip)
 int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s);
 // all-waves-compute ("ping-pong") 3x3/s1/p1 kernel for the 16-bit Cin >= 128, Cout % 256 == 0 layers (conv3x3_pp.hip);
-// launch_conv3x3_patch hands those layers over to it when their output is not pooled (kdisable bit 0 keeps the loader/consumer kernel)
+// launch_conv3x3_patch hands those layers over to it when their output is not pooled (KOFF_CONV_PP keeps the loader/consumer kernel)
 int pp_conv_supported(const ConvArgs &a);      // 0 = no, else the tile mode of patch_conv_supported
 int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s);
 size_t conv_pp_sk_bytes();
 // weight-stationary 3x3/s1/p1 kernel for the 16-bit Cin == 64 layers (conv3x3_ws.hip: the whole weight tile resident in LDS, the
 // activations in a ring of image rows, the first conv optionally computed by its producer waves); launch_conv3x3_patch hands those
 // layers over to it when their output is POOLED (conv1_2; a full-resolution output stays on the loader/consumer kernel, as does
-// everything under kdisable bit 6).  Same output bits.
+// everything under KOFF_CONV_WS).  Same output bits.
 int ws_conv_supported(const ConvArgs &a);
 int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s);   // out_pool only (a.out null)
+// Item geometry of the persistent kernels (conv3x3_patch / _pp / _ws, dwpw_kernel, pw1x1_kernel).
+// grid: one workgroup per CU, in a multiple of 8 (the item split is per XCD, mfma_prims.h xcd_items); surplus workgroups find no item and exit
+inline int persistent_grid(int items) { return items >= 256 ? 256 : ((items + 7) / 8) * 8; }
+// pixel tiles: tw = 32 / 16 (the tile mode of patch_conv_supported): 2-D tiles of (px / tw) x tw pixels of one image; tw = 0: flat
+// tiles of 256 consecutive NHW pixels
+inline void conv_tiles(int B, int H, int W, int tw, int px, int &tiles_x, int &tiles_per_img, int &m_tiles)
+{
+    tiles_x = tw ? W / tw : 0;
+    tiles_per_img = tw ? tiles_x * (H / (px / tw)) : 0;
+    m_tiles = tw ? B * tiles_per_img : cdiv(B * H * W, 256);
+}
 // rows of the packed weight matrix must be padded to a multiple of this
 int conv_n_pad(int cout);
 // channels of every NHWC activation tensor are padded to a multiple of this
@@ -101,7 +127,7 @@ int launch_maxpool2(const void *in, void *out, int B, int H, int W, int C, int c
 int launch_l2norm(const void *in, const float *w, void *out, long long pixels, int C, int dtype,
                   hipStream_t s);
 // depthwise 3x3, pad 1, stride 1|2, folded BN + ReLU, NHWC DT.  w: fp32 [9][Cpad], bias [Cpad]
-// (kdisable bit 4: the one-row strip kernel instead of the sliding-window one, bit 5: the sliding-window one always -- same bits)
+// (KOFF_DW_SLIDE: the one-row strip kernel instead of the sliding-window one, KOFF_DW_STRIP_SMALL: the sliding-window one always -- same bits)
 int launch_dwconv3(const void *in, const float *w, const float *bias, void *out, int B, int H, int W,
                    int C, int stride, int relu, int dtype, hipStream_t s, int kdisable = 0);
 // conv_dw block fused (dwpw.hip): depthwise 3x3 (stride 1, pad 1, fp32 weights [9][Cin] + bias [Cin], ReLU) -> pointwise 1x1
@@ -115,7 +141,7 @@ struct DwPwArgs {
 };
 int dwpw_supported(const DwPwArgs &a);           // 0 = no, else the tile mode
 int launch_dwpw(const DwPwArgs &a, hipStream_t s);
-// wide 1x1 convs as a persistent 256 x 256-item GEMM (dwpw.hip pw1x1_kernel); launch_conv hands them over (kdisable bit 3: off)
+// wide 1x1 convs as a persistent 256 x 256-item GEMM (dwpw.hip pw1x1_kernel); launch_conv hands them over (KOFF_PW1X1: off)
 int pw1x1_supported(const ConvArgs &a);
 int launch_pw1x1(const ConvArgs &a, hipStream_t s);
 // softmax over rows of (R, C) fp32, in place allowed

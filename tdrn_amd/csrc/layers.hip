@@ -631,7 +631,7 @@ int launch_dwconv3(const void *in, const float *w, const float *bias, void *out,
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const int per16 = 16 / dtype_bytes(dtype);
     if (C % per16) return TDRN_E_UNSUPPORTED;
-    if (!(kdisable & 16) && (stride == 1 || stride == 2) && Wo >= 4) {
+    if (!(kdisable & KOFF_DW_SLIDE) && (stride == 1 || stride == 2) && Wo >= 4) {
         // strips of 4 outputs at stride 1, of 2 at stride 2 (9 input columns per row do not fit the registers of two waves per
         // SIMD there).  Segment height: the tallest of 8 / 4 / 2 rows that still leaves >= 768 workgroups (3 per CU); below
         // that the strip kernel (one row per thread).  Measured on dualrefinedet_mobilenet 320 x 64 (profiles/r04_experiments.md):
@@ -641,7 +641,7 @@ int launch_dwconv3(const void *in, const float *w, const float *bias, void *out,
         int th = 0;
         for (int t = 8; t >= 2 && !th; t >>= 1)
             if (per_row * ((Ho + t - 1) / t) >= 768ll * 256) th = t;
-        if (kdisable & 32) th = 8;                          // (TDRN_PLAN_DW_SLIDE_ALL)
+        if (kdisable & KOFF_DW_STRIP_SMALL) th = 8;                          // (TDRN_PLAN_DW_SLIDE_ALL)
         if (th) {
             const int nseg = (Ho + th - 1) / th;
             dim3 grid((unsigned)((per_row * nseg + 255) / 256));

@@ -532,7 +532,7 @@ void Plan::hoist_l2norm_to_side_lanes()
 void Plan::plan_fuse_first()
 {
     fuse_first = -1;
-    if ((cfg.plan_flags & TDRN_PLAN_NO_FUSE_FIRST) || cfg.dtype == TDRN_F32 || (kdisable & 4) || ops.size() <= 1 || ops[0].kind != OP_FIRST ||
+    if ((cfg.plan_flags & TDRN_PLAN_NO_FUSE_FIRST) || cfg.dtype == TDRN_F32 || (kdisable & KOFF_CONV_PATCH) || ops.size() <= 1 || ops[0].kind != OP_FIRST ||
         ops[1].kind != OP_CONV || ops[0].stride != 1 || tensors[ops[0].out].Cpad != 64) return;
     const Op &c = ops[1];
     const Tensor &ti = tensors[ops[0].out];
@@ -690,12 +690,17 @@ void Plan::mark_shared_tensors()
 int Plan::build()
 {
     es = dtype_bytes(cfg.dtype);
-    kdisable = ((cfg.plan_flags & TDRN_PLAN_NO_CONV_PP) ? 1 : 0) | ((cfg.plan_flags & TDRN_PLAN_NO_PP_SK) ? 2 : 0) |
-               ((cfg.plan_flags & TDRN_PLAN_NO_CONV_PATCH) ? 4 : 0) | ((cfg.plan_flags & TDRN_PLAN_NO_PW1X1) ? 8 : 0) |
-               ((cfg.plan_flags & TDRN_PLAN_NO_DW_SLIDE) ? 16 : 0) | ((cfg.plan_flags & TDRN_PLAN_DW_SLIDE_ALL) ? 32 : 0) |
-               ((cfg.plan_flags & TDRN_PLAN_NO_CONV_WS) ? 64 : 0) | ((cfg.plan_flags & TDRN_PLAN_NO_YGEMM_V2) ? 128 : 0) |
-               ((cfg.plan_flags & TDRN_PLAN_NO_HEAD3X3) ? 256 : 0) | ((cfg.plan_flags & TDRN_PLAN_TS_ONE_RANGE) ? 512 : 0) |
-               ((cfg.plan_flags & TDRN_PLAN_NO_PATCH_TAIL) ? 1024 : 0);
+    static const struct { int plan_flag, koff; } kSwitches[] = {
+        {TDRN_PLAN_NO_CONV_PP, KOFF_CONV_PP},       {TDRN_PLAN_NO_PP_SK, KOFF_PP_SK},
+        {TDRN_PLAN_NO_CONV_PATCH, KOFF_CONV_PATCH}, {TDRN_PLAN_NO_PW1X1, KOFF_PW1X1},
+        {TDRN_PLAN_NO_DW_SLIDE, KOFF_DW_SLIDE},     {TDRN_PLAN_DW_SLIDE_ALL, KOFF_DW_STRIP_SMALL},
+        {TDRN_PLAN_NO_CONV_WS, KOFF_CONV_WS},       {TDRN_PLAN_NO_YGEMM_V2, KOFF_YGEMM_V2},
+        {TDRN_PLAN_NO_HEAD3X3, KOFF_HEAD3X3},       {TDRN_PLAN_TS_ONE_RANGE, KOFF_TS_RANGES},
+        {TDRN_PLAN_NO_PATCH_TAIL, KOFF_PATCH_TAIL},
+    };
+    kdisable = 0;
+    for (const auto &sw : kSwitches)
+        if (cfg.plan_flags & sw.plan_flag) kdisable |= sw.koff;
     fault_handoff = (cfg.plan_flags & TDRN_PLAN_FAULT_HANDOFF) ? 1 : 0;
     late_side = !(cfg.plan_flags & TDRN_PLAN_NO_LATE_SIDE);
     use_lanes = !(cfg.plan_flags & TDRN_PLAN_ONE_STREAM);

@@ -426,7 +426,7 @@ struct Run {
         // 16 frames; ranges of 8 / 4 frames lose it again to the extra launches), 520 -> 488 us at MobileNet's batch 64.
         // Per-frame arithmetic untouched.  TDRN_PLAN_TS_ONE_RANGE switches it off.
         constexpr size_t kRangeBytes = (size_t)192 << 20;
-        if (per_frame > 0 && !(p.kdisable & 512)) {
+        if (per_frame > 0 && !(p.kdisable & KOFF_TS_RANGES)) {
             long long fit = (long long)kRangeBytes / (long long)per_frame;
             fit = fit < 1 ? 1 : fit;
             if (fit < Bc) Bc = (int)fit;
