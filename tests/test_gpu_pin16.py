@@ -1,7 +1,7 @@
 """The 16-bit kernels pinned from OUTSIDE the repo's own drift measurements.
 
 The bf16 / fp16 plans run kernels the fp32 every-stage test never executes (conv3x3_pp, the FUSE instantiation of
-conv3x3_patch, ygemm_k256, deform_sample).  Three kinds of checks, all through the C ABI:
+conv3x3_patch, ygemm_k256, deform_sample, the 16-bit instantiations of deform_gemm_kernel).  Four kinds of checks, all through the C ABI:
 
   (a) plan equalities: the default plan against the same net with conv3x3_pp off, with its chained split off -- every output
       bit-identical (full DRN net, 320 px at batch 1 and 32, 512 px at batch 3, both 16-bit types);
@@ -22,6 +22,11 @@ conv3x3_patch, ygemm_k256, deform_sample).  Three kinds of checks, all through t
       rounded per-tap weights (same bound), and deform_sample's output against a blend of THE DEVICE'S OWN Y rows with
       bilinear weights recomputed from the device's own fp32 offsets by the reference's rule
       (utils/deformconv/deform_conv_cuda_kernel.cu:15-51,189-203), fp32 accumulation noise only.
+  (d) the heads on the fused gather kernel (deform_gemm_kernel: more than one deformable group, more than 34 taps, or
+      TDRN_PLAN_NO_DEFORM_TS): their fp32 outputs against tests/_deform_gather_ref.py's exact restatement of the kernel -- fp32 sampling
+      decisions and bilinear weights, the fp32 fma chain of the blend, one nearest-even rounding of the blend to the type, exact
+      products -- from the device's own input map and offsets: c S plus one ulp16 |w| for blend values at a rounding tie, nothing else
+      (tests/test_gpu_pin16_gather.py runs the plans that launch it; tests/test_deform_gather_ref.py proves the restatement on the CPU).
 
 Frame sizes.  The tests of this file run (b) and (c) at the build sizes, 320 and 512 px.  Multi-scale testing (eval/tta.py) feeds a
 320-net 192 ... 704 px frames, each on a plan of its own (engine_for), and the kernel a 3x3 / s1 / p1 layer gets follows its map
@@ -46,6 +51,8 @@ import torch.nn.functional as F
 
 from tdrn_amd import _lib
 from tdrn_amd.utils import synth
+
+from _deform_gather_ref import gather_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -131,9 +138,10 @@ def _head_map(t, b, level, fm, per):
     return t[b, offs[level]:offs[level + 1]].reshape(f, f, per).permute(2, 0, 1)
 
 
-def check_stages(net, sd, x, dtype, images, skip_first_input=False, forward=None, stages=None):
-    """(b) + (c) for every launch of net's plan after net(x); `images`: batch rows that are recomputed on the CPU.
+def check_stages(net, sd, x, dtype, images, skip_first_input=False, forward=None, stages=None, key_frames=None):
+    """(b) + (c) + (d) for every launch of net's plan after net(x); `images`: batch rows that are recomputed on the CPU.
     `forward`: how to run the net when net(x) alone does not (the TRN temporal net needs ref_loc).
+    `key_frames`: Bk when `forward` runs a TRN clip with the ref_loc maps of Bk < B key frames (the offset tensors hold Bk frames).
     `stages(op, (H, W))`: which ops are recomputed, from the op's info and the size of its input map (default: every op); an op
     that is not selected is not counted in `checked`.  The plan, the workspace and the pyramid geometry are those of the engine
     that ran x (net.engine_for: a frame size other than the build size has its own)."""
@@ -259,6 +267,9 @@ def check_stages(net, sd, x, dtype, images, skip_first_input=False, forward=None
                 _assert_stage(name, tensor(op["out"])[b:b + 1], y, y.abs() * 4, dtype, report=report)      # (fp32 norm + divide: a few 1e-7 relative)
         elif kind == "deform_heads" and op["y"] >= 0:
             _check_transform_then_sample(eng, sd, op, tensor, odm_loc.cpu(), conf.cpu(), fm, B, images, dtype, report, name)
+        elif kind == "deform_heads":
+            _check_gather(eng, sd, op, tensor, (arm_loc if op["out_kind"] == 1 else odm_loc).cpu(), conf.cpu(), fm, B, images, dtype, report,
+                          name, key_frames or B)
         else:
             continue
         checked[kind] = checked.get(kind, 0) + 1
@@ -353,6 +364,44 @@ def _check_transform_then_sample(eng, sd, op, tensor, odm_loc, conf, fm, B, imag
         got = torch.cat([_head_map(odm_loc, b, op["level"], fm, 12), _head_map(conf, b, op["level"], fm, nc3)], 0).reshape(ncol, HW).t()
         _assert_stage(name + ":sample", got[keep], torch.from_numpy(out)[keep], torch.from_numpy(Sb)[keep] + 1e-30, dtype, out16=False, report=report)
         assert int(near.sum()) < HW // 4
+
+
+def _check_gather(eng, sd, op, tensor, loc, conf, fm, B, images, dtype, report, name, Bk):
+    """(d) a deformable head on the fused gather kernel (deform_gemm_kernel; op["y"] < 0: more than one deformable group, more than 34
+    taps or TDRN_PLAN_NO_DEFORM_TS): its outputs against tests/_deform_gather_ref.py's exact restatement of the kernel, fed with the
+    device's own input map and fp32 offsets and the state dict's [loc ; conf] rows rounded to the type (net_pack.hip pack_deform()).
+    Both branches of a multihead level are summed, whether the launch runs them as one K loop or as two work items that add
+    atomically; so are the two group halves of the TRN heads.  Under the key-frame broadcast the offset tensor holds the Bk key
+    frames only and output pixel m reads offset row m % (Bk H W): frame b the offsets of key frame b % Bk.  fp32 outputs, fp32
+    accumulation noise only (C_ACC * S + extra), on the pixels that are not `near` a discontinuity of the rejection test."""
+    H = W = fm[op["level"]]
+    conf = conf.view(B, eng.num_priors, -1)
+    loc = loc.view(B, eng.num_priors, 4)
+    nc3 = conf.shape[-1] * 3
+    ncol = 12 + nc3
+    G = max(1, op["groups"])
+    branches = [(op["w"], op["b"], 3, 1, op["off_c0"][0])]
+    if op["n_branches"] == 2:
+        branches.append((op["w2"], op["b2"], op["k2"], op["pad2"], op["off_c0"][1]))
+    w16 = []
+    for ln, cn, k, pad, c0 in branches:
+        wcat = torch.cat([torch.from_numpy(sd[ln + ".weight"]), torch.from_numpy(sd[cn + ".weight"])], 0)     # (12 + 3 classes, Cin, k, k)
+        assert wcat.shape[0] == ncol, name
+        w16.append(_round16(wcat, dtype).numpy())
+    X = tensor(op["in"])
+    # (Bk, Coff, H, W) fp32, exact; read at the forward's batch: a tensor's place in the workspace scales with it (tdrn_net_read_tensor)
+    off = tensor(op["off"])[:Bk].numpy()
+    for b in images:
+        x16 = X[b:b + 1].double()
+        assert torch.equal(_round16(x16, dtype), x16), name + ": the head's input is not in the net dtype"
+        specs = [dict(off=off[b % Bk:b % Bk + 1, c0:c0 + G * 2 * k * k], w16=w, stride=1, padding=pad, dilation=1, G=G)
+                 for (ln, cn, k, pad, c0), w in zip(branches, w16)]
+        ref, S, extra, near = gather_ref(x16.numpy(), dtype=dtype, second=specs[1] if len(specs) == 2 else None, **specs[0])
+        keep = torch.from_numpy(~near[0].reshape(-1))
+        rows = lambda a: torch.as_tensor(a).reshape(ncol, H * W).t()[keep]
+        got = torch.cat([_head_map(loc, b, op["level"], fm, 12), _head_map(conf, b, op["level"], fm, nc3)], 0)
+        _assert_stage(name + ":gather", rows(got), rows(ref[0]), rows(S[0]), dtype, out16=False, extra=rows(extra[0]), report=report)
+        assert int(near.sum()) < H * W // 4, name
 
 
 def _print_report(title, report, checked):
