@@ -1,5 +1,5 @@
 """Print the layer plan of a list of net configurations: parameters, tensors, every op_info field, blob / workspace sizes and the
-library's own `plan:` lines (lane, split-K, patch / igemm, chain index).  CPU only: no GPU, no torch device.  Two builds of the
+library's own `plan:` lines (lane, split-K, the kernel at batch 1 / at batch 32, chain index).  CPU only: no GPU, no torch device.  Two builds of the
 library plan alike exactly when their outputs are byte-identical:
 
     TDRN_LIB_PATH=/path/to/other/libtdrn_hip.so python scripts/plan_dump.py | sha256sum

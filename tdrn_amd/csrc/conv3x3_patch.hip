@@ -909,20 +909,14 @@ __global__ __launch_bounds__(768) void conv3x3_patch_kernel(const PatchParams p)
 }
 
 // ---------------------------------------------------------------------------------------------
-int patch_conv_supported(const ConvArgs &a)
+bool patch_takes(const ConvArgs &a, bool pooled)
 {
-    if (a.kdisable & KOFF_CONV_PATCH) return 0;
-    if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return 0;
-    if (a.phases != 1 || a.out_f32 || a.res) return 0;
-    if (a.Ho != a.H || a.Wo != a.W) return 0;
-    if (a.Npad % 64) return 0;
-    if (a.o_rs != (long long)a.Wo * a.o_cs || a.o_bs != (long long)a.Ho * a.Wo * a.o_cs || a.o_base) return 0;
-    // (32-bit byte offsets into the input tensor; the fused-first-conv instantiation never reads it -- its input is the raw frame)
-    if (!a.fuse_x && (long long)a.B * a.H * a.W * a.Cin * dtype_bytes(a.dtype) >= (1ll << 32)) return 0;
-    if (a.W % 32 == 0 && a.H % 8 == 0) return 32;
-    if (a.W % 16 == 0 && a.H % 16 == 0) return 16;
-    if (2 * a.W + 2 + 256 <= kPatchSlots * 8) return -1;       // flat tiles
-    return 0;
+    if ((a.kdisable & KOFF_CONV_PATCH) || a.fuse_x8 || !conv3x3_input_fits(a)) return false;
+    const int mode = conv3x3_tile_mode(a, kPatchSlots);
+    if (pooled && (mode < 0 || (a.H & 1) || (a.W & 1))) return false;
+    // the fused first-conv instantiation: 16-bit, 16 x 32 tiles, one 64-cout tile
+    if (a.fuse_x && (a.dtype == TDRN_F32 || mode != 32 || a.Npad != 64 || a.H % 16)) return false;
+    return mode != 0;
 }
 
 template <typename DT, int BN> static int launch_patch_cfg(const PatchParams &p_in, hipStream_t s)
@@ -963,12 +957,11 @@ template <typename DT, int BN> static int launch_patch_cfg(const PatchParams &p_
 #endif
     if constexpr (BN == 64 && sizeof(DT) == 2) {
         if (p.fx) {
-            if (p.tw != 32 || p.n_tiles != 1 || p.H % 16) return TDRN_E_UNSUPPORTED;
             hipLaunchKernelGGL((conv3x3_patch_kernel<DT, 64, 32, true>), dim3(grid), dim3(768), 0, s, p);
             return hip_status(hipGetLastError());
         }
     }
-    if (p.fx) return TDRN_E_UNSUPPORTED;
+    if (p.fx) return TDRN_E_UNSUPPORTED;                 // (patch_takes is false)
     if (p.tw == 0) hipLaunchKernelGGL((conv3x3_patch_kernel<DT, BN, 0>), dim3(grid), dim3(768), 0, s, p);
     else if (p.tw == 32) hipLaunchKernelGGL((conv3x3_patch_kernel<DT, BN, 32>), dim3(grid), dim3(768), 0, s, p);
     else hipLaunchKernelGGL((conv3x3_patch_kernel<DT, BN, 16>), dim3(grid), dim3(768), 0, s, p);
@@ -978,19 +971,10 @@ template <typename DT, int BN> static int launch_patch_cfg(const PatchParams &p_
 // out_pool: optional fused MaxPool2d(2,2) output; `a.out` may then be null (pooled output only).
 int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s)
 {
-    const int mode = patch_conv_supported(a);
-    if (!mode) return TDRN_E_UNSUPPORTED;
-    if (out_pool && (mode < 0 || (a.H & 1) || (a.W & 1))) return TDRN_E_UNSUPPORTED;
-    if (out_pool && ws_conv_supported(a)) {              // conv3x3_ws.hip (Cin == 64, pooled output): same arithmetic, same bits
-        const int rc = launch_conv3x3_ws(a, out_pool, s);
-        if (rc != TDRN_E_UNSUPPORTED) return rc;         // (it declines launches too small to fill the chip and fused launches it has no LDS for)
-    }
+    if (!patch_takes(a, out_pool != nullptr)) return TDRN_E_UNSUPPORTED;
+    const int mode = conv3x3_tile_mode(a, kPatchSlots);
     // (pooled layers stay here: a pooled variant of conv3x3_pp.hip was bit-identical, but conv3_3 measured 210 us there against
     // 204-210 us here: no gain)
-    if (!out_pool && pp_conv_supported(a)) {             // conv3x3_pp.hip: same arithmetic, same bits
-        const int rc = launch_conv3x3_pp(a, s);
-        if (rc != TDRN_E_UNSUPPORTED) return rc;         // (it declines launches too small to fill the chip)
-    }
     PatchParams p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.zero = (const char *)a.zero_page; p.bias = a.bias;
     p.out = (char *)a.out; p.out_pool = (char *)out_pool;

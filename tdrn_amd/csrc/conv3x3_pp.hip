@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
     int n_seg, seg_item0, c0_first = 0, c1_last = nchunks, tail_first = 0, head_last = 0;
     if (sk) {
         const int units = xi.avail * nchunks;
-        // (units * 32 < 2^31 for any tensor below the 4-GiB limit of patch_conv_supported; 32-bit scalar arithmetic)
+        // (units * 32 < 2^31 for any tensor below the 4-GiB limit of conv3x3_input_fits; 32-bit scalar arithmetic)
         const int u0 = __builtin_amdgcn_readfirstlane(units * slot / istride), u1 = __builtin_amdgcn_readfirstlane(units * (slot + 1) / istride);
         if (u1 <= u0) return;                           // (whole workgroup)
         const int fi = u0 / nchunks, li = (u1 - 1) / nchunks;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
         const int lrow = ln >> 3, pc = ln & 7;
         const unsigned lc = (unsigned)((pc ^ ((4 * wave + (lrow >> 1)) & 7)) << 4) + ccoff;
         const unsigned rowbytes = (unsigned)(p.Cin * ES);
-        unsigned off;                                   // (the tensor is < 4 GiB: patch_conv_supported)
+        unsigned off;                                   // (the tensor is < 4 GiB: conv3x3_input_fits)
         bool ok;
         if (TW) {
             if (j == 0) {
@@ -618,39 +618,50 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p)
 // scratch of the chained split: 256 flag words + one 256-KiB accumulator slab per workgroup
 size_t conv_pp_sk_bytes() { return 1024 + (size_t)256 * 8 * 32 * 64 * 16; }
 
-// the layers this kernel takes over from conv3x3_patch.hip: 16-bit, >= 2 channel chunks, couts in whole 256-groups
-int pp_conv_supported(const ConvArgs &a)
+// the layers this kernel takes: 16-bit, >= 4 channel chunks, couts in whole 256-groups
+bool pp_takes_geometry(const ConvArgs &a)
 {
-    if (a.kdisable & KOFF_CONV_PP) return 0;
-    if (a.dtype == TDRN_F32 || a.fuse_x) return 0;
+    if ((a.kdisable & (KOFF_CONV_PP | KOFF_CONV_PATCH)) || a.dtype == TDRN_F32) return false;
     // (Cin = 128 -- two chunks, 18 steps per item -- stays with conv3x3_patch.hip: the per-item cost of this kernel, drain +
     // epilogue + re-stagger, weighs 10 % there: 125 vs 116 us on conv3_1 in the net)
-    if (a.Cin < 256 || a.Cin % 64 || a.Npad % 256) return 0;
-    return patch_conv_supported(a);
+    if (a.Cin < 256 || a.Cin % 64 || a.Npad % 256) return false;
+    return conv3x3_tile_mode(a, kPPSlots) != 0;
+}
+
+// items = (256-pixel tile, 256-cout tile) pairs; returns the tile width (0: flat tiles)
+static int pp_items(const ConvArgs &a, PPParams &p)
+{
+    const int mode = conv3x3_tile_mode(a, kPPSlots), tw = mode > 0 ? mode : 0;
+    conv_tiles(a.B, a.H, a.W, tw, 256, p.tiles_x, p.tiles_per_img, p.m_tiles);
+    p.n_tiles = a.Npad / 256;
+    p.items = p.m_tiles * p.n_tiles;
+    return tw;
+}
+
+bool pp_takes(const ConvArgs &a, bool pooled)
+{
+    if (pooled || a.fuse_x || a.fuse_x8 || !pp_takes_geometry(a) || !conv3x3_input_fits(a)) return false;
+    PPParams p;
+    pp_items(a, p);
+    // below ~3/4 of a full grid the loader/consumer kernel's smaller (128- / 64-cout) items fill more CUs: measured 2x faster
+    // at 50-100 items, equal at 200 (the two kernels produce the same bits, so the choice may depend on the batch)
+    return p.items >= 192;
 }
 
 int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s)
 {
-    const int mode = pp_conv_supported(a);
-    if (!mode) return TDRN_E_UNSUPPORTED;
+    if (!pp_takes(a, false)) return TDRN_E_UNSUPPORTED;
     PPParams p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.zero = (const char *)a.zero_page; p.bias = a.bias;
     p.out = (char *)a.out;
     p.B = a.B; p.H = a.H; p.W = a.W; p.Cin = a.Cin; p.Cout = a.Cout; p.Cs = (int)a.o_cs; p.Ktot = 9 * a.Cin;
     p.relu = a.relu;
     p.M = a.B * a.H * a.W;
-    const int tw = mode > 0 ? mode : 0;
-    conv_tiles(a.B, a.H, a.W, tw, 256, p.tiles_x, p.tiles_per_img, p.m_tiles);
-    p.n_tiles = a.Npad / 256;
-    p.items = p.m_tiles * p.n_tiles;
+    const int tw = pp_items(a, p);
     // With two or more cout tiles an XCD whose items are (pixel tile, cout tile) pairs keeps the WHOLE weight matrix live (4.7 MB at
     // 512 x 512, more than its 4-MB L2, and under the chained split its workgroups are at different channel chunks at the same
     // time): cout-tile-major numbering gives an XCD one cout tile's weights (2.4 MB) at the price of reading every patch on two XCDs.
     p.n_major = p.n_tiles > 1 ? 1 : 0;
-    if (p.items <= 0) return TDRN_OK;
-    // below ~3/4 of a full grid the loader/consumer kernel's smaller (128- / 64-cout) items fill more CUs: measured 2x faster
-    // at 50-100 items, equal at 200 (the two kernels produce the same bits, so the choice may depend on the batch)
-    if (p.items < 192) return TDRN_E_UNSUPPORTED;
     const int grid = persistent_grid(p.items);
     // chained split when it shortens the launch: a full grid, more than one item per workgroup, and an item count that does
     // not divide evenly (otherwise whole items are already balanced); the choice changes no output bit

@@ -40,7 +40,7 @@ struct WsParams {
     const void *reserved;          // never read: with the arguments behind it moved up, hipcc schedules the fused variants differently
     char *out_pool;                // pooled NHWC [B][H/2][W/2][Cs]
     int B, H, W, Cout, Cs, Ktot;   // Cin == 64 (one 128-byte chunk); Ktot = 9 * 64
-    int relu;                      // always 1 (the launcher declines others); never read either, kept for the same reason
+    int relu;                      // always 1 (ws_takes); never read either, kept for the same reason
     int SX, TY, TSEG, NSEG, NT;    // strips per row (W / 32), tiles per column (H / 8), tiles per segment, segments, cout tiles
     int units;                     // NT * B * SX * NSEG; unit = ((nt * B + b) * SX + sx) * NSEG + seg
     // FUSE: the layer's input is the first conv's output, computed here from the raw frames
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
         if constexpr (TDRN_WS_ABLATE & 4) return;
         // MaxPool2d(2,2) + ReLU on the PACKED values, as signed 16-bit maxima: rounding to 16 bits is monotonic, so it commutes with the
         // maximum; after max(., 0) every candidate is a non-negative 16-bit float, whose bit patterns order like integers -- and
-        // max(max(a, b), 0) = max(max(a, 0), max(b, 0)).  (Pooled layers always carry a ReLU: the launcher declines otherwise.)
+        // max(max(a, b), 0) = max(max(a, 0), max(b, 0)).  (Pooled layers always carry a ReLU: ws_takes.)
         // Only compiler-visible instructions here: the accumulators come straight out of the MFMAs, and hipcc pads the MFMA -> VALU
         // and VALU -> DPP wait states for its own instructions only, not around inline asm.
 #pragma unroll
@@ -625,60 +625,57 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const WsParams p)
 }
 
 // ---------------------------------------------------------------------------------------------
-// the layers this kernel takes over from conv3x3_patch.hip: 16-bit, ONE 64-channel chunk, 2-D geometry in whole 8 x 32 tiles
-int ws_conv_supported(const ConvArgs &a)
+// Work units of a launch: a unit = TSEG consecutive 8 x 32 tiles of one tile column of one image and cout tile.
+// Rows per unit: a unit of T tiles costs ~T + 0.6 tile times (its first 10 rows are produced before its first tile can start, 8 of
+// them under the previous unit's last tile); the launch takes ceil(units / grid) units per workgroup.  Depends on the geometry
+// and the batch only through the unit count -- and the choice changes no output bit.
+static long long ws_units(const ConvArgs &a, WsParams &p)
 {
-    if (a.kdisable & KOFF_CONV_WS) return 0;
-    if (a.dtype == TDRN_F32 || a.Cin != 64 || a.Npad % 64 || a.Cout % 64) return 0;       // (Cout = the output tensor's padded channel count)
-    if (a.W % 32 || a.H % 8) return 0;
-    return patch_conv_supported(a) != 0;
+    p.SX = a.W / 32; p.TY = a.H / 8; p.NT = a.Cout / 64;      // (cout tiles of all-padding rows beyond Cout are not computed)
+    double best = 1e30;
+    int best_t = p.TY;
+    for (int t = p.TY; t >= 2; --t) {
+        const int nseg = cdiv(p.TY, t);
+        const long long units = (long long)p.NT * a.B * p.SX * nseg;
+        const double cost = (double)((units + 255) / 256) * (t + 0.6);
+        if (cost < best - 1e-9) { best = cost; best_t = t; }
+    }
+    p.TSEG = best_t;
+    p.NSEG = cdiv(p.TY, p.TSEG);
+    return (long long)p.NT * a.B * p.SX * p.NSEG;
+}
+
+// the layers this kernel takes: 16-bit, ONE 64-channel chunk, 2-D geometry in whole 8 x 32 tiles, pooled output only.  (A full-resolution
+// output -- conv2_1 -- would be eight 1-KiB stores per tile and consumer wave, ~150 cycles of the wave's time each, against two for a
+// pooled tile: it measured 127-128 us in the net against 123-126 us on conv3x3_patch.hip, whose two consumer waves per SIMD hide each
+// other's stores.)
+bool ws_takes(const ConvArgs &a, bool pooled)
+{
+    if ((a.kdisable & (KOFF_CONV_WS | KOFF_CONV_PATCH)) || !pooled) return false;
+    if (a.dtype == TDRN_F32 || a.Cin != 64 || a.Npad % 64 || a.Cout % 64) return false;       // (Cout = the output tensor's padded channel count)
+    if (a.W % 32 || a.H % 8 || !conv3x3_tile_mode(a, 0) || !conv3x3_input_fits(a)) return false;
+    if (!a.relu) return false;                           // (the pooled epilogue's integer maxima assume the ReLU)
+    if (a.fuse_x && a.fuse_x8) return false;
+    // the fused variant keeps LDS for the raw tiles instead of a full staging strip: one cout tile
+    if ((a.fuse_x || a.fuse_x8) && (a.Cout != 64 || a.H != a.W || a.fuse_cout > 64)) return false;
+    WsParams p;
+    const long long units = ws_units(a, p);
+    // below ~3/4 of the chip conv3x3_patch.hip's independent 256-pixel items spread better (small batches)
+    return units >= 192 && units < (1ll << 31);
 }
 
 int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
 {
-    if (!ws_conv_supported(a)) return TDRN_E_UNSUPPORTED;
-    // Pooled output only.  A full-resolution output (conv2_1) would be eight 1-KiB stores per tile and consumer wave, ~150 cycles of the
-    // wave's time each, against two for a pooled tile: it measured 127-128 us in the net against 123-126 us on conv3x3_patch.hip (whose
-    // two consumer waves per SIMD hide each other's stores), so conv3x3_patch.hip keeps such layers.
-    if (!out_pool || a.out) return TDRN_E_UNSUPPORTED;
-    if ((a.H & 1) || (a.W & 1) || !a.relu) return TDRN_E_UNSUPPORTED;      // (the pooled epilogue's integer maxima assume the ReLU)
+    if (!out_pool || !ws_takes(a, true)) return TDRN_E_UNSUPPORTED;
     WsParams p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.zero = (const char *)a.zero_page; p.bias = a.bias;
     p.reserved = nullptr; p.out_pool = (char *)out_pool;
     p.B = a.B; p.H = a.H; p.W = a.W; p.Cout = a.Cout; p.Cs = (int)a.o_cs; p.Ktot = 9 * a.Cin;
     p.relu = a.relu;
-    p.SX = a.W / 32; p.TY = a.H / 8; p.NT = a.Cout / 64;      // (cout tiles of all-padding rows beyond Cout are not computed)
     p.fx = a.fuse_x; p.fw = a.fuse_w; p.fb = a.fuse_b; p.fS = a.H; p.fCout = a.fuse_cout;
     p.fx8 = a.fuse_x8; p.fmean[0] = a.fuse_mean[0]; p.fmean[1] = a.fuse_mean[1]; p.fmean[2] = a.fuse_mean[2];
-    if (a.fuse_x && a.fuse_x8) return TDRN_E_ARG;
-    if (a.fuse_x || a.fuse_x8) {
-        // the fused variant keeps LDS for the raw tiles instead of a full staging strip: one cout tile
-        if (p.NT != 1 || a.H != a.W || a.fuse_cout > 64) return TDRN_E_UNSUPPORTED;
-    }
-    int grid = 256;
-    // Rows per unit: a unit of T tiles costs ~T + 0.6 tile times (its first 10 rows are produced before its first tile can start, 8 of
-    // them under the previous unit's last tile); the launch takes ceil(units / grid) units per workgroup.  Depends on the geometry
-    // and the batch only through the unit count -- and the choice changes no output bit.
-    {
-        double best = 1e30;
-        int best_t = p.TY;
-        for (int t = p.TY; t >= 2; --t) {
-            const int nseg = cdiv(p.TY, t);
-            const long long units = (long long)p.NT * a.B * p.SX * nseg;
-            const double cost = (double)((units + grid - 1) / grid) * (t + 0.6);
-            if (cost < best - 1e-9) { best = cost; best_t = t; }
-        }
-        if (p.TY < 2) best_t = p.TY;
-        p.TSEG = best_t;
-        p.NSEG = cdiv(p.TY, p.TSEG);
-    }
-    const long long units = (long long)p.NT * a.B * p.SX * p.NSEG;
-    if (units <= 0) return TDRN_OK;
-    if (units >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    p.units = (int)units;
-    if (p.units < grid) grid = persistent_grid(p.units);
-    // below ~3/4 of the chip conv3x3_patch.hip's independent 256-pixel items spread better (small batches)
-    if (p.units < 192) return TDRN_E_UNSUPPORTED;
+    p.units = (int)ws_units(a, p);
+    const int grid = persistent_grid(p.units);
 #ifdef TDRN_WS_STAMP
     static unsigned *stamps = nullptr;
     if (!stamps) TDRN_HIP_TRY(hipMalloc((void **)&stamps, 256 * 8 * 4 * sizeof(unsigned)));

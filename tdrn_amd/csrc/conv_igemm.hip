@@ -412,10 +412,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_kernel(const ConvPa
     igemm_tile<DT, BM, BN, WGM, WGN, STAGES>(p, wg, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.z, smem);
 }
 
-// (chosen by layer geometry only, never by batch size: a frame's result must not depend on what else is in the batch)
-constexpr int kPatchMinPixels = 400;            // smaller maps (the 10x10 / 5x5 pyramid levels) stay on the implicit GEMM
-int patch_conv_takes(const ConvArgs &a) { return patch_conv_supported(a) && a.H * a.W >= kPatchMinPixels; }
-
 int conv_n_pad(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : (int)align_up((size_t)cout, 128)); }
 
 template <typename DT, int BM, int BN, int WGM, int WGN, int STAGES>
@@ -513,14 +509,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p, 
 }
 
 // number of K slices for a small-M problem: fill the chip (~2 workgroups per CU) but keep >= 4 K-steps each
-int conv_splitk_choice(const ConvArgs &a)
+int igemm_splitk_choice(const ConvArgs &a)
 {
     const int es = dtype_bytes(a.dtype);
     const int nk = a.kh * a.kw * (a.Cin / (128 / es));
     const int bn = a.Npad % 128 == 0 ? 128 : (a.Npad % 64 == 0 ? 64 : 32);
     const long long blocks = (long long)cdiv(a.B * a.Ho * a.Wo, 128) * (a.Npad / bn) * a.phases;
-    if (patch_conv_takes(a)) return 1;
-    if (head3x3_supported(a)) return 1;                  // (head3x3.hip takes the launch whole)
     if (blocks >= 160 || nk < 8) return 1;
     int s = (int)((384 + blocks - 1) / blocks);
     if (s > nk / 4) s = nk / 4;
@@ -569,20 +563,12 @@ static int make_params(const ConvArgs &a, ConvParams &p)
     return TDRN_OK;
 }
 
-int launch_conv(const ConvArgs &a, hipStream_t s)
+int launch_conv_igemm(const ConvArgs &a, hipStream_t s)
 {
+    if (a.fuse_x || a.fuse_x8) return TDRN_E_UNSUPPORTED;   // (conv_route: CONV_NONE)
     ConvParams p;
     TDRN_TRY(make_params(a, p));
     if (p.M <= 0) return TDRN_OK;
-    // 3x3/s1/p1 layers with enough tiles go to the warp-specialised patch kernel (TDRN_PLAN_NO_CONV_PATCH: off)
-    if (p.splits == 1 && patch_conv_takes(a))
-        return launch_conv3x3_patch(a, nullptr, s);
-    if (a.fuse_x) return TDRN_E_UNSUPPORTED;             // only the patch kernel computes the first conv itself
-    if (p.splits == 1 && head3x3_supported(a)) return launch_head3x3(a, s);      // the narrow fp32 heads (ARM loc)
-    if (p.splits == 1 && pw1x1_supported(a)) {           // wide pointwise layers: dwpw.hip's persistent GEMM (same bits)
-        const int rc1 = launch_pw1x1(a, s);
-        if (rc1 != TDRN_E_UNSUPPORTED) return rc1;       // (it declines launches too small to fill the chip)
-    }
     int rc = TDRN_E_ARG;
     switch (a.dtype) {
         case TDRN_F32: rc = launch_dt<float>(p, a.phases, s); break;
@@ -726,12 +712,7 @@ __global__ __launch_bounds__(256) void conv_chain_kernel(const ChainParams cp)
 size_t conv_chain_ctr_bytes() { return 256; }    // 1 + 2 * kChainMax counters, two diagnostic words at [40], [41]
 int conv_chain_max_layers() { return kChainMax; }
 
-int conv_chain_supported(const ConvArgs &a)
-{
-    if (a.out_f32 || a.fuse_x || a.Npad % 128 != 0) return 0;
-    if (a.splitk == 1 && patch_conv_takes(a)) return 0;   // the patch kernels' layer
-    return 1;
-}
+int conv_chain_supported(const ConvArgs &a) { return !(a.out_f32 || a.fuse_x || a.Npad % 128 != 0); }
 
 int launch_conv_chain(const ChainLayer *layers, int n, unsigned *ctr, hipStream_t s, unsigned *status)
 {

@@ -75,13 +75,13 @@ static int run_case(int B, int H, int W, int Cin, int Cout, int relu, int dtype,
         a.sk_ws = k == 2 ? sk_ws : nullptr;
         a.sk_flags_zero = false;                          // first launch: the launcher's own memset node
         a.out = dout[k];
-        rcs[k] = launch_conv3x3_patch(a, nullptr, s);
+        rcs[k] = launch_conv(a, s);
         if (rcs[k] != TDRN_OK) break;
         CK(hipStreamSynchronize(s));
         a.sk_flags_zero = true;                           // from here on every launch must leave the flag words zero itself
-        for (int i = 0; i < 3; ++i) launch_conv3x3_patch(a, nullptr, s);
+        for (int i = 0; i < 3; ++i) launch_conv(a, s);
         CK(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) launch_conv3x3_patch(a, nullptr, s);
+        for (int i = 0; i < iters; ++i) launch_conv(a, s);
         CK(hipEventRecord(e1, s));
         CK(hipEventSynchronize(e1));
         float ms = 0;
@@ -163,12 +163,12 @@ static int run_case_ws(int B, int H, int W, int Cout, int fuse, int dtype, int i
     int rcs[2] = {0, 0};
     for (int k = 0; k < 2; ++k) {                        // 0: conv3x3_patch, 1: conv3x3_ws
         a.kdisable = k ? 0 : KOFF_CONV_WS;
-        rcs[k] = k ? launch_conv3x3_ws(a, dpool[k], s) : launch_conv3x3_patch(a, dpool[k], s);
+        rcs[k] = k ? launch_conv3x3_ws(a, dpool[k], s) : launch_conv(a, s, dpool[k]);
         if (rcs[k] != TDRN_OK) break;
         CK(hipStreamSynchronize(s));
-        for (int i = 0; i < 3; ++i) launch_conv3x3_patch(a, dpool[k], s);
+        for (int i = 0; i < 3; ++i) launch_conv(a, s, dpool[k]);
         CK(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) launch_conv3x3_patch(a, dpool[k], s);
+        for (int i = 0; i < iters; ++i) launch_conv(a, s, dpool[k]);
         CK(hipEventRecord(e1, s));
         CK(hipEventSynchronize(e1));
         float ms = 0;

@@ -18,7 +18,7 @@
 // exact-input stage tests of the unfused plan (tests/test_gpu_pin16.py) pin it.  A pixel tile's depthwise conv is recomputed once
 // per 256-cout tile (Cout = 512: twice): its operand tile for ALL chunks (256 px x 512 ch) does not fit LDS beside the
 // accumulators of a second cout tile.
-// Scope: stride 1, Cin % 64 == 0, Cout % 256 == 0, the tile shapes of patch_conv_supported (80x80 and up as 2-D tiles, 40x40 /
+// Scope: stride 1, Cin % 64 == 0, Cout % 256 == 0, the tile shapes of conv3x3_tile_mode (80x80 and up as 2-D tiles, 40x40 /
 // 20x20 as flat tiles): 8 of the 13 trunk blocks at 320 px (blocks 4, 5, 7-11, 13: 85 % of the trunk's FLOPs); stride-2 blocks and
 // the narrow first three stay on the two-launch path.
 #include <cstdio>
@@ -767,30 +767,37 @@ int launch_dwpw(const DwPwArgs &a, hipStream_t s)
 }
 
 
-// the 1x1 / stride 1 / unpadded convs this kernel takes over from conv_igemm.hip: 16-bit, whole 64-channel chunks, couts in whole
-// 256-groups, a plain NHWC output tensor, no residual, no split-K, and enough items to fill the chip
-int pw1x1_supported(const ConvArgs &a)
+// items = (256-pixel tile, 256-cout tile) pairs
+static void pw1x1_items(const ConvArgs &a, Pw1x1Params &p)
 {
-    if ((a.kdisable & KOFF_PW1X1) || a.dtype == TDRN_F32) return 0;
-    if (a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0 || a.phases != 1 || a.res || a.out_f32 || a.splitk > 1 || a.fuse_x) return 0;
-    if (a.Ho != a.H || a.Wo != a.W || a.Cin % 64 || a.Npad % 256 || a.Cout > a.Npad) return 0;
-    if (a.o_rs != (long long)a.Wo * a.o_cs || a.o_bs != (long long)a.Ho * a.Wo * a.o_cs || a.o_base) return 0;
+    p.M = a.B * a.H * a.W;
+    p.m_tiles = cdiv(p.M, 256); p.n_tiles = a.Npad / 256; p.items = p.m_tiles * p.n_tiles;
+}
+
+// the 1x1 / stride 1 / unpadded convs this kernel takes: 16-bit, whole 64-channel chunks, couts in whole 256-groups, a plain NHWC
+// output tensor, no residual, no split-K, and enough items to fill the chip
+bool pw1x1_takes(const ConvArgs &a, bool pooled)
+{
+    if ((a.kdisable & KOFF_PW1X1) || a.dtype == TDRN_F32 || pooled) return false;
+    if (a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0 || a.phases != 1 || a.res || a.out_f32 || a.splitk > 1 || a.fuse_x) return false;
+    if (a.Ho != a.H || a.Wo != a.W || a.Cin % 64 || a.Npad % 256 || a.Cout > a.Npad) return false;
+    if (a.o_rs != (long long)a.Wo * a.o_cs || a.o_bs != (long long)a.Ho * a.Wo * a.o_cs || a.o_base) return false;
     const long long M = (long long)a.B * a.H * a.W;
-    if (M * a.Cin * 2 >= (1ll << 32) || (long long)a.Npad * a.Cin * 2 >= (1ll << 31)) return 0;
-    return 1;
+    if (M * a.Cin * 2 >= (1ll << 32) || (long long)a.Npad * a.Cin * 2 >= (1ll << 31)) return false;
+    Pw1x1Params p;
+    pw1x1_items(a, p);
+    // (below ~3/4 of a full grid conv_igemm's 128 x 128 tiles fill more CUs; the two kernels produce the same bits, so the choice
+    // may depend on the batch)
+    return p.items >= 192;
 }
 
 int launch_pw1x1(const ConvArgs &a, hipStream_t s)
 {
-    if (!pw1x1_supported(a)) return TDRN_E_UNSUPPORTED;
+    if (!pw1x1_takes(a, false)) return TDRN_E_UNSUPPORTED;
     Pw1x1Params p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.bias = a.bias; p.out = (char *)a.out;
-    p.M = a.B * a.H * a.W; p.Cin = a.Cin; p.Cout = a.Cout; p.Cs = (int)a.o_cs; p.relu = a.relu;
-    p.m_tiles = cdiv(p.M, 256); p.n_tiles = a.Npad / 256; p.items = p.m_tiles * p.n_tiles;
-    if (p.items <= 0) return TDRN_OK;
-    // (below ~3/4 of a full grid conv_igemm's 128 x 128 tiles fill more CUs; the two kernels produce the same bits, so the choice
-    // may depend on the batch)
-    if (p.items < 192) return TDRN_E_UNSUPPORTED;
+    p.Cin = a.Cin; p.Cout = a.Cout; p.Cs = (int)a.o_cs; p.relu = a.relu;
+    pw1x1_items(a, p);
     static int ablate = -1;
     if (ablate < 0) ablate = dev_ablate_env("TDRN_PW_ABLATE");     // (developer builds only: common.h)
     p.ablate = ablate;

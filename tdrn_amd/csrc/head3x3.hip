@@ -143,29 +143,29 @@ __global__ __launch_bounds__(512, 2) void head3x3_kernel(const Head3Params p)
     }
 }
 
-int head3x3_supported(const ConvArgs &a)
+bool head3x3_takes(const ConvArgs &a, bool pooled)
 {
-    if (a.kdisable & KOFF_HEAD3X3) return 0;
-    if (a.dtype == TDRN_F32 || a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return 0;
-    if (a.phases != 1 || !a.out_f32 || a.res || a.fuse_x || a.fuse_x8) return 0;
-    if (a.Ho != a.H || a.Wo != a.W || a.W > kH3MaxW || a.W < 2) return 0;
+    if ((a.kdisable & KOFF_HEAD3X3) || pooled) return false;
+    if (a.dtype == TDRN_F32 || a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return false;
+    if (a.phases != 1 || !a.out_f32 || a.res || a.fuse_x || a.fuse_x8) return false;
+    if (a.Ho != a.H || a.Wo != a.W || a.W > kH3MaxW || a.W < 2) return false;
     // a level has to give every image at least two tiles' worth of pixels: the 10x10 / 5x5 levels (one 39 % / 10 % filled tile per image,
     // 32 workgroups at batch 32) measured 32 / 18 us here against 25 / 19 us on conv_igemm.hip with its split-K (geometry only, never
     // the batch: a frame's result must not depend on what else is in the batch)
-    if (a.H * a.W < 400) return 0;
-    if (a.Cout < 1 || a.Cout > 16 || a.Npad < 16 || a.Cin % 64) return 0;
-    if ((long long)a.H * a.W * a.Cin * 2 >= (1ll << 32)) return 0;                 // 32-bit byte offsets inside an image
-    if ((long long)a.Npad * 9 * a.Cin * 2 >= (1ll << 32)) return 0;
+    if (a.H * a.W < 400) return false;
+    if (a.Cout < 1 || a.Cout > 16 || a.Npad < 16 || a.Cin % 64) return false;
+    if ((long long)a.H * a.W * a.Cin * 2 >= (1ll << 32)) return false;                 // 32-bit byte offsets inside an image
+    if ((long long)a.Npad * 9 * a.Cin * 2 >= (1ll << 32)) return false;
     // 16-byte stores: four consecutive columns of a pixel.  Geometry only -- the caller's POINTER alignment must not choose the
     // kernel (head3x3 and conv_igemm differ in fp32 K order, and a frame's arithmetic depends on geometry alone): a base that is
     // not 16-byte aligned (a sliced `out=` tensor) keeps this kernel and stores the four columns one by one (p.vec16 = 0).
-    if ((a.o_base | a.o_bs | a.o_rs | a.o_cs) & 3) return 0;
-    return 1;
+    if ((a.o_base | a.o_bs | a.o_rs | a.o_cs) & 3) return false;
+    return (long long)a.B * ((a.H * a.W + 255) / 256) < (1ll << 31);       // (one workgroup per 256-pixel tile)
 }
 
 int launch_head3x3(const ConvArgs &a, hipStream_t s)
 {
-    if (!head3x3_supported(a)) return TDRN_E_UNSUPPORTED;
+    if (!head3x3_takes(a, false)) return TDRN_E_UNSUPPORTED;
     if (!a.in || !a.w || !a.out || !a.bias) return TDRN_E_ARG;
     Head3Params p;
     p.in = (const char *)a.in; p.w = (const char *)a.w; p.bias = a.bias;
@@ -176,7 +176,6 @@ int launch_head3x3(const ConvArgs &a, hipStream_t s)
     p.tiles_per_img = (a.H * a.W + 255) / 256;
     const long long blocks = (long long)a.B * p.tiles_per_img;
     if (blocks <= 0) return TDRN_OK;
-    if (blocks >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
     if (a.dtype == TDRN_BF16) hipLaunchKernelGGL((head3x3_kernel<bf16_t>), dim3((unsigned)blocks), dim3(512), 0, s, p);
     else hipLaunchKernelGGL((head3x3_kernel<f16_t>), dim3((unsigned)blocks), dim3(512), 0, s, p);
     return hip_status(hipGetLastError());

@@ -68,39 +68,64 @@ struct ConvArgs {
     unsigned *status = nullptr;
     int fault_handoff = 0;          // fault injection (tests): producers never raise their flag, the polls are short
 };
-int launch_conv(const ConvArgs &a, hipStream_t s);
+// Which kernel runs a dense conv layer (conv_route.hip: the whole precedence, once).  Pure: it reads geometry, dtype, batch, kdisable, fuse_* and
+// splitk, tests pointers for null only and makes no HIP call, so a plan can be asked without a GPU (TDRN_PLAN_DUMP).  pooled: MaxPool2d(2,2) of
+// the output is wanted: CONV_WS / CONV_PATCH pool in their epilogue, CONV_IGEMM leaves it to launch_maxpool2.  CONV_NONE: a fused-first launch
+// (fuse_x / fuse_x8) nobody takes: the caller runs the first conv on its own.  All but CONV_HEAD3X3 (another fp32 K order; geometry only)
+// give the same output bits, so the choice may depend on the batch.
+enum ConvKernel { CONV_IGEMM, CONV_PATCH, CONV_PP, CONV_WS, CONV_HEAD3X3, CONV_PW1X1, CONV_NONE };
+ConvKernel conv_route(const ConvArgs &a, bool pooled);
+const char *conv_kernel_name(ConvKernel k);
+// the kernel of conv_route(a, out_pool != null); out_pool: the MaxPool2d(2,2) output (a.out is then written on the CONV_IGEMM route only)
+int launch_conv(const ConvArgs &a, hipStream_t s, void *out_pool = nullptr);
+int conv_splitk_choice(const ConvArgs &a);          // 1 = no split (only layers that stay on conv_igemm.hip are split)
+// One predicate per kernel file: X_takes(a, pooled) is all launch_X needs, item-count thresholds included; launch_X returns
+// TDRN_E_UNSUPPORTED exactly where it is false.  Only conv_route.hip combines them.  conv_igemm.hip takes every layer:
+int launch_conv_igemm(const ConvArgs &a, hipStream_t s);
+int igemm_splitk_choice(const ConvArgs &a);         // K slices that fill the chip for a small-M layer
+size_t conv_splitk_bytes(const ConvArgs &a, int splits);
 // Several small dependent layers in ONE launch (conv_igemm.hip, conv_chain_kernel): layer i may depend on up to two EARLIER
 // layers of the list (dep = index or -1); everything else a layer reads must be complete when the launch starts.  Every layer
 // keeps its own splitk / partial slab.  `ctr`: conv_chain_ctr_bytes() of zeroed device words.  Output bits equal launch_conv's.
 struct ChainLayer { ConvArgs a; int dep[2] = {-1, -1}; };
-int conv_chain_supported(const ConvArgs &a);
+int conv_chain_supported(const ConvArgs &a);        // (the planner keeps conv3x3_patch / _pp layers out of a chain)
 int conv_chain_max_layers();
 size_t conv_chain_ctr_bytes();
 int launch_conv_chain(const ChainLayer *layers, int n, unsigned *ctr, hipStream_t s, unsigned *status = nullptr);
-int conv_splitk_choice(const ConvArgs &a);          // 1 = no split
-size_t conv_splitk_bytes(const ConvArgs &a, int splits);
-// narrow 3x3/s1/p1 heads with fp32 output (<= 16 columns: the ARM loc heads), head3x3.hip; KOFF_HEAD3X3 declines
-int head3x3_supported(const ConvArgs &a);
+// narrow 3x3/s1/p1 heads with fp32 output (<= 16 columns: the ARM loc heads at levels of >= 400 pixels), head3x3.hip
+bool head3x3_takes(const ConvArgs &a, bool pooled);
 int launch_head3x3(const ConvArgs &a, hipStream_t s);
-// warp-specialised 3x3/s1/p1 kernel (conv3x3_patch.hip); out_pool = optional fused MaxPool2d(2,2) output
-int patch_conv_supported(const ConvArgs &a);   // 0 = no, 32/16 = 2-D tiles, -1 = flat tiles
-int patch_conv_takes(const ConvArgs &a);       // launch_conv hands this (unsplit) layer to launch_conv3x3_patch (conv_igemm.hip)
+// The layers of the 3x3/s1/p1 direct-conv kernels (conv3x3_patch / _pp / _ws) and their pixel tiles, from the geometry alone (no batch, no
+// kdisable): 0 = not such a layer, 32 / 16 = 2-D tiles, -1 = flat tiles of 256 consecutive pixels (+ halo) in a patch buffer of `slots` 8-row pieces
+inline int conv3x3_tile_mode(const ConvArgs &a, int slots)
+{
+    if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1 || a.phases != 1 || a.out_f32 || a.res) return 0;
+    if (a.Ho != a.H || a.Wo != a.W || a.Npad % 64) return 0;
+    if (a.o_rs != (long long)a.Wo * a.o_cs || a.o_bs != (long long)a.Ho * a.Wo * a.o_cs || a.o_base) return 0;
+    if (a.W % 32 == 0 && a.H % 8 == 0) return 32;
+    if (a.W % 16 == 0 && a.H % 16 == 0) return 16;
+    return 2 * a.W + 2 + 256 <= slots * 8 ? -1 : 0;
+}
+// ... and their one limit that grows with the batch: 32-bit byte offsets into the input tensor (the fused-first instantiation never reads it)
+inline bool conv3x3_input_fits(const ConvArgs &a) { return a.fuse_x || (long long)a.B * a.H * a.W * a.Cin * dtype_bytes(a.dtype) < (1ll << 32); }
+// warp-specialised loader/consumer kernel (conv3x3_patch.hip): any such layer unless KOFF_CONV_PATCH; pooled (out_pool = fused MaxPool2d(2,2)
+// output, a.out may then be null) with 2-D tiles only
+bool patch_takes(const ConvArgs &a, bool pooled);
 int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s);
-// all-waves-compute ("ping-pong") 3x3/s1/p1 kernel for the 16-bit Cin >= 128, Cout % 256 == 0 layers (conv3x3_pp.hip);
-// launch_conv3x3_patch hands those layers over to it when their output is not pooled (KOFF_CONV_PP keeps the loader/consumer kernel)
-int pp_conv_supported(const ConvArgs &a);      // 0 = no, else the tile mode of patch_conv_supported
+// all-waves-compute ("ping-pong") kernel for the unpooled 16-bit Cin >= 256, Cout % 256 == 0 layers (conv3x3_pp.hip), from 192 items up
+// (KOFF_CONV_PP: off).  pp_takes_geometry: the part of pp_takes that no batch changes (what a plan may depend on).
+bool pp_takes_geometry(const ConvArgs &a);
+bool pp_takes(const ConvArgs &a, bool pooled);
 int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s);
 size_t conv_pp_sk_bytes();
-// weight-stationary 3x3/s1/p1 kernel for the 16-bit Cin == 64 layers (conv3x3_ws.hip: the whole weight tile resident in LDS, the
-// activations in a ring of image rows, the first conv optionally computed by its producer waves); launch_conv3x3_patch hands those
-// layers over to it when their output is POOLED (conv1_2; a full-resolution output stays on the loader/consumer kernel, as does
-// everything under KOFF_CONV_WS).  Same output bits.
-int ws_conv_supported(const ConvArgs &a);
-int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s);   // out_pool only (a.out null)
+// weight-stationary kernel for the POOLED 16-bit Cin == 64 layers (conv3x3_ws.hip: the whole weight tile resident in LDS, the activations in a
+// ring of image rows, the first conv optionally computed by its producer waves from fp32 or uint8 frames), from 192 units up (KOFF_CONV_WS: off)
+bool ws_takes(const ConvArgs &a, bool pooled);
+int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s);   // out_pool only (a.out is not written)
 // Item geometry of the persistent kernels (conv3x3_patch / _pp / _ws, dwpw_kernel, pw1x1_kernel).
 // grid: one workgroup per CU, in a multiple of 8 (the item split is per XCD, mfma_prims.h xcd_items); surplus workgroups find no item and exit
 inline int persistent_grid(int items) { return items >= 256 ? 256 : ((items + 7) / 8) * 8; }
-// pixel tiles: tw = 32 / 16 (the tile mode of patch_conv_supported): 2-D tiles of (px / tw) x tw pixels of one image; tw = 0: flat
+// pixel tiles: tw = 32 / 16 (conv3x3_tile_mode): 2-D tiles of (px / tw) x tw pixels of one image; tw = 0: flat
 // tiles of 256 consecutive NHW pixels
 inline void conv_tiles(int B, int H, int W, int tw, int px, int &tiles_x, int &tiles_per_img, int &m_tiles)
 {
@@ -141,8 +166,8 @@ struct DwPwArgs {
 };
 int dwpw_supported(const DwPwArgs &a);           // 0 = no, else the tile mode
 int launch_dwpw(const DwPwArgs &a, hipStream_t s);
-// wide 1x1 convs as a persistent 256 x 256-item GEMM (dwpw.hip pw1x1_kernel); launch_conv hands them over (KOFF_PW1X1: off)
-int pw1x1_supported(const ConvArgs &a);
+// wide 1x1 convs as a persistent 256 x 256-item GEMM (dwpw.hip pw1x1_kernel), from 192 items up (KOFF_PW1X1: off)
+bool pw1x1_takes(const ConvArgs &a, bool pooled);
 int launch_pw1x1(const ConvArgs &a, hipStream_t s);
 // softmax over rows of (R, C) fp32, in place allowed
 int launch_softmax_rows(const float *in, float *out, long long R, int C, hipStream_t s);

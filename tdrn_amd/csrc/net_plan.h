@@ -50,6 +50,7 @@ struct Op {
 // independent branches of the tail (TCB laterals, ARM heads) run on side streams; dependencies
 // between lanes are hipEvents on the producing tensor.
 constexpr int kLanes = 4;
+constexpr int kPlanRefBatch = 32; // the batch (the benchmark's) at which split-K is chosen, per layer, from its geometry
 constexpr size_t kTailCtl = 256;  // bytes of chain counters in front of the chained split's scratch (workspace tail)
 
 // Everything build() produces; a forward reads it and changes none of it.
@@ -86,6 +87,7 @@ struct Plan {
     int readers_of(int t) const;        // number of op inputs / residuals that read tensor t
     // the fields of a conv op's launch that follow from the plan alone (no pointers, no output view), at batch B
     void conv_geometry(const Op &o, int B, ConvArgs &a) const;
+    ConvArgs conv_question(const Op &o, int B) const;   // ... as conv_route is asked while planning (no buffers)
     // ops i and i + 1 share ONE launch: consecutive deformable heads / offset convs are batched (up to four, the pyramid levels)
     bool launch_continues(size_t i) const
     {

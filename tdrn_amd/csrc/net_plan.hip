@@ -473,6 +473,23 @@ void Plan::conv_geometry(const Op &o, int B, ConvArgs &a) const
     a.kdisable = kdisable;
 }
 
+// ... plus what else conv_route reads, for a question asked while planning (no buffers yet: pointers are null or a non-null mark)
+ConvArgs Plan::conv_question(const Op &o, int B) const
+{
+    static const float mark = 0.f;
+    ConvArgs a;
+    conv_geometry(o, B, a);
+    a.relu = o.relu;
+    a.out_f32 = o.out_kind != OUT_TENSOR;
+    a.o_cs = o.out_kind == OUT_TENSOR ? tensors[o.out].Cpad : 0;
+    a.o_rs = (long long)a.Wo * a.o_cs; a.o_bs = (long long)a.Ho * a.Wo * a.o_cs;
+    a.res = o.res >= 0 ? &mark : nullptr;
+    a.splitk = o.splitk;
+    a.partial = o.splitk > 1 ? (void *)&mark : nullptr;
+    if (fuse_first >= 0 && &o == &ops[fuse_first]) { a.fuse_x = &mark; a.fuse_cout = ops[0].Cout; }
+    return a;
+}
+
 // The fp32 (3, S, S) copy of uint8 frames (plans whose first conv reads fp32: every one but the conv3x3_ws route) costs no
 // workspace and no tensor index of a layer: it is appended LAST and ALIASED with the first layer output behind the second op
 // that is large enough -- that tensor is dead while ops 0 / 1, the only readers of the copy, run (the engine's forwards are
@@ -527,18 +544,18 @@ void Plan::hoist_l2norm_to_side_lanes()
     }
 }
 
-// first conv fused into the loader of the conv behind it (conv3x3_patch.hip FUSE): 16-bit modes, stride 1, 64 channels,
-// 8x32 tiles, and nobody else reads the first conv's output (TDRN_PLAN_NO_FUSE_FIRST keeps the two launches)
+// first conv fused into the loader of the conv behind it (conv3x3_patch.hip FUSE; conv3x3_ws.hip at the batches it takes): where
+// patch_takes says so for the fused launch, and nobody else reads the first conv's output (TDRN_PLAN_NO_FUSE_FIRST keeps the two launches)
 void Plan::plan_fuse_first()
 {
     fuse_first = -1;
-    if ((cfg.plan_flags & TDRN_PLAN_NO_FUSE_FIRST) || cfg.dtype == TDRN_F32 || (kdisable & KOFF_CONV_PATCH) || ops.size() <= 1 || ops[0].kind != OP_FIRST ||
-        ops[1].kind != OP_CONV || ops[0].stride != 1 || tensors[ops[0].out].Cpad != 64) return;
+    if ((cfg.plan_flags & TDRN_PLAN_NO_FUSE_FIRST) || ops.size() <= 1 || ops[0].kind != OP_FIRST || ops[1].kind != OP_CONV || ops[0].stride != 1 ||
+        tensors[ops[0].out].Cpad != 64) return;
     const Op &c = ops[1];
     const Tensor &ti = tensors[ops[0].out];
-    if (c.in == ops[0].out && readers_of(ops[0].out) == 1 && c.k == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && c.phases == 1 && c.res < 0 &&
-        c.out_kind == OUT_TENSOR && c.Npad == 64 && c.Cin == 64 && ti.W % 32 == 0 && ti.H % 16 == 0 && ti.H == ti.W && c.lane == 0)
-        fuse_first = 1;
+    fuse_first = 1;                          // (the fused launch never reads the layer's input tensor: no limit of it grows with the batch)
+    if (c.in != ops[0].out || readers_of(ops[0].out) != 1 || c.out_kind != OUT_TENSOR || c.lane != 0 || ti.H != ti.W ||
+        !patch_takes(conv_question(c, 0), c.pool_t >= 0)) fuse_first = -1;
     if (fuse_first >= 0) {                   // the fused launch carries both layers' algorithmic work
         ops[1].flops += ops[0].flops;
         ops[1].bytes += 3.0 * ops[0].hw * ops[0].hw * 4 - (double)ti.H * ti.W * ti.Cpad * es;
@@ -550,19 +567,18 @@ void Plan::plan_fuse_first()
 // depends on the batch it travels in; the partial slabs live in a per-lane region of the workspace
 void Plan::plan_splitk()
 {
-    constexpr int kSplitkRefBatch = 32;
     for (Op &o : ops) {
         if (o.kind == OP_CONV && o.pool_t >= 0) o.stat = ST_CONV3;
         if (o.kind != OP_CONV || o.pool_t >= 0) continue;
         ConvArgs a;
-        conv_geometry(o, kSplitkRefBatch, a);
+        conv_geometry(o, kPlanRefBatch, a);
         a.out_f32 = o.out_kind != OUT_TENSOR;
-        o.splitk = conv_splitk_choice(a);
-        a.o_cs = o.out_kind == OUT_TENSOR ? tensors[o.out].Cpad : 0;
-        a.o_rs = (long long)a.Wo * a.o_cs; a.o_bs = (long long)a.Ho * a.Wo * a.o_cs;
-        a.res = o.res >= 0 ? (const void *)1 : nullptr;
-        if (o.splitk == 1 && patch_conv_takes(a)) o.stat = ST_CONV3;
-        if (o.chain_tag && !(o.out_kind == OUT_TENSOR && conv_chain_supported(a))) o.chain_tag = false;
+        o.splitk = conv_splitk_choice(a);    // (asked of the bare geometry, as ever: a residual layer of the patch kernels' shape is not split either)
+        a = conv_question(o, kPlanRefBatch);
+        const ConvKernel k = conv_route(a, false);
+        const bool direct = k == CONV_PATCH || k == CONV_PP;
+        if (direct) o.stat = ST_CONV3;
+        if (o.chain_tag && !(o.out_kind == OUT_TENSOR && !direct && conv_chain_supported(a))) o.chain_tag = false;
     }
 }
 
@@ -625,9 +641,10 @@ void Plan::place_splitk_slabs()
     if (const char *pd = getenv("TDRN_PLAN_DUMP")) {
         if (atoi(pd))
             for (const Op &o : ops)
-                if (o.kind == OP_CONV)
-                    fprintf(stderr, "plan: %-28s lane %d  %dx%d k%d s%d d%d  Cin %4d Cout %4d  splitk %d  %s  chain %d\n", o.w.c_str(), o.lane,
-                            o.hw >> 16, o.hw & 0xffff, o.k, o.stride, o.dil, o.Cin, o.Cout, o.splitk, o.stat == ST_CONV3 ? "patch" : "igemm", o.chain);
+                if (o.kind == OP_CONV)       // (... %s/%s: the kernel at batch 1 / at the reference batch)
+                    fprintf(stderr, "plan: %-28s lane %d  %dx%d k%d s%d d%d  Cin %4d Cout %4d  splitk %d  %s/%s  chain %d\n", o.w.c_str(), o.lane,
+                            o.hw >> 16, o.hw & 0xffff, o.k, o.stride, o.dil, o.Cin, o.Cout, o.splitk, conv_kernel_name(conv_route(conv_question(o, 1), o.pool_t >= 0)),
+                            conv_kernel_name(conv_route(conv_question(o, kPlanRefBatch), o.pool_t >= 0)), o.chain);
     }
     for (int l = 0; l < kLanes; ++l) {
         splitk_off[l] = ws_per_sample;
@@ -668,9 +685,12 @@ void Plan::plan_workspace_tail()
 {
     ws_fixed = 0;
     pp_sk_planned = false;
-    if (cfg.dtype != TDRN_F32)
-        for (const Op &o : ops)
-            if (o.kind == OP_CONV && o.stat == ST_CONV3 && o.lane == 0 && o.Cin >= 256 && o.Npad % 256 == 0) pp_sk_planned = true;
+    for (const Op &o : ops) {
+        if (o.kind != OP_CONV || o.stat != ST_CONV3 || o.lane != 0) continue;
+        ConvArgs a = conv_question(o, 0);
+        a.kdisable = 0;                      // (the workspace is sized alike whatever the kernel-choice switches say)
+        pp_sk_planned = pp_sk_planned || pp_takes_geometry(a);
+    }
     if (pp_sk_planned || !chain_ops.empty()) ws_fixed = kTailCtl + (pp_sk_planned ? align_up(conv_pp_sk_bytes(), 256) : 1024);
 }
 

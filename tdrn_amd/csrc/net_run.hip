@@ -303,43 +303,35 @@ struct Run {
     int run_conv(size_t oi, hipStream_t s)
     {
         const Op &o = p.ops[oi];
+        const bool pooled = o.pool_t >= 0;
         ConvArgs a;
         conv_args(o, a);
         if (o.lane == 0 && p.pp_sk_planned) {
             a.sk_ws = tail + kTailCtl;
             a.sk_flags_zero = true;
-            if (skz_pending && pp_conv_supported(a)) TDRN_TRY(wait_tail_zeroed());
+            if (skz_pending && pp_takes_geometry(a)) TDRN_TRY(wait_tail_zeroed());
         }
-        const Op &f = p.ops[0];
         if ((int)oi == p.fuse_first) {
+            const Op &f = p.ops[0];
             a.fuse_w = (const float *)(wb + f.w_off); a.fuse_b = (const float *)(wb + f.b_off);
             a.fuse_cout = f.Cout;
-            if (!xin && o.pool_t >= 0) {
+            if (!xin) {
                 // uint8 frames: conv3x3_ws.hip's producers read the planes themselves (the frame never exists in fp32)
                 a.fuse_x8 = u8->planes; a.fuse_mean[0] = u8->mean[0]; a.fuse_mean[1] = u8->mean[1]; a.fuse_mean[2] = u8->mean[2];
-                a.out = nullptr;
-                const int rc = ws_conv_supported(a) ? launch_conv3x3_ws(a, tptr(o.pool_t), s) : TDRN_E_UNSUPPORTED;
-                if (rc != TDRN_E_UNSUPPORTED) return rc;          // (done, or a real error)
-                a.fuse_x8 = nullptr;
-                a.out = tptr(o.out);
+                if (conv_route(a, pooled) != CONV_WS) {           // (a small batch): the fp32 route from here on
+                    a.fuse_x8 = nullptr;
+                    TDRN_TRY(ensure_f32_input(s));
+                }
             }
-            TDRN_TRY(ensure_f32_input(s));                        // it declined (a small batch): the fp32 route from here on
             a.fuse_x = xin;
+            if (conv_route(a, pooled) == CONV_NONE) {
+                // the fusion was planned from the layer geometry; should no kernel take THIS launch (a limit that depends on
+                // the batch), run the two layers as two launches: the first conv's tensor keeps its place in the workspace
+                TDRN_TRY(launch_first(f, s));
+                a.fuse_x = nullptr; a.fuse_w = nullptr; a.fuse_b = nullptr; a.fuse_cout = 0;
+            }
         }
-        if (a.fuse_x && patch_conv_supported(a) <= 0) {
-            // the fusion was planned from the layer geometry; should the patch kernel decline THIS launch (a limit
-            // that depends on the batch), run the two layers as two launches: the first conv's tensor keeps its place
-            // in the workspace
-            TDRN_TRY(launch_first(f, s));
-            a.fuse_x = nullptr; a.fuse_w = nullptr; a.fuse_b = nullptr; a.fuse_cout = 0;
-        }
-        if (o.pool_t < 0) return launch_conv(a, s);
-        if (patch_conv_supported(a) > 0) {
-            a.out = nullptr;                 // only the pooled map leaves the chip
-            return launch_conv3x3_patch(a, tptr(o.pool_t), s);
-        }
-        TDRN_TRY(launch_conv(a, s));
-        return launch_maxpool2(a.out, tptr(o.pool_t), B, a.Ho, a.Wo, p.tensors[o.pool_t].Cpad, 0, p.cfg.dtype, s);
+        return launch_conv(a, s, pooled ? tptr(o.pool_t) : nullptr);
     }
 
     int run_dw(size_t oi, hipStream_t s)

@@ -1,8 +1,8 @@
 """The exact-input stage checks of test_gpu_pin16.py at the frame sizes of multi-scale testing (eval/tta.py: a 320-net also
 runs 192, 384, 448, 512, 576 and 704 px frames, each size on a plan of its own: EngineModule.engine_for).
 
-Which kernel a 3x3 layer gets depends on its map (patch_conv_supported, conv3x3_patch.hip; conv3x3_pp.hip and conv3x3_ws.hip build
-on its choice); 320 and 512 px reach only a few of the geometries the kernels accept:
+Which kernel a 3x3 layer gets depends on its map (conv_route.hip; conv3x3_tile_mode in kernels.h is the tile mode conv3x3_patch.hip,
+conv3x3_pp.hip and conv3x3_ws.hip share); 320 and 512 px reach only a few of the geometries the kernels accept:
 
     tile mode         condition                       maps at 320 / 512 px       maps at the other sizes (checked below: *)
     8 x 32 tiles      W % 32 == 0, H % 8 == 0         320, 160 / 512 ... 32      96*, 192*, 224*, 448*, 288, 352, 576, 704
