@@ -112,6 +112,42 @@ TDRN_API int tdrn_deform_conv_backward_parameters(const float *input, const floa
                                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-c) Dense conv2d with gradients -- what nn.Conv2d + autograd give the reference's training loop (train.py; the
+ *     dense layers of model/dualrefinedet_vggbn.py:30-117): forward, input gradient, weight / bias gradient.
+ *   input (N, Cin, H, W), weight (Cout, Cin, kH, kW) OIHW, bias (Cout) or NULL, output / grad_output (N, Cout, Ho, Wo),
+ *   grad_input like input, grad_weight like weight, grad_bias (Cout) or NULL: all fp32, contiguous, device.
+ *   `compute` selects the MFMA input type as in (i): TDRN_F32 is exact fp32; TDRN_BF16 / TDRN_F16 round input, weight and
+ *   grad_output ONCE, to nearest even, to the type (bias is not rounded).  Accumulation and every output are fp32.
+ *   forward:             output is OVERWRITTEN.
+ *   backward_input:      grad_input is OVERWRITTEN (a stride-1 conv over grad_output with the kernel rotated and transposed).
+ *   backward_parameters: grad_weight += scale * sum_p grad_output[p] input[p (+) tap], grad_bias += scale * sum_p grad_output[p],
+ *                        split over K = N*Ho*Wo and summed in a fixed order.
+ *   All gradients are bitwise reproducible run to run: nothing on this path uses float atomics, and the split count depends
+ *   on the geometry alone.
+ *   Geometry (the argument order is the query's in all four functions): square kernels kH = kW in {1, 3}, stride 1,
+ *   dilationH = dilationW >= 1, 0 <= padH = padW <= dilation * (k - 1), groups = 1.
+ *   Errors, all decided before any launch: a null pointer -> TDRN_E_ARG; k <= 0, stride / dilation <= 0, negative pad,
+ *   N / Cin / Cout / H / W <= 0, an output smaller than 1 x 1 -> query 0 and TDRN_E_SHAPE; well-formed geometry outside the
+ *   list above (stride != 1, other kernel sizes, pad > dilation * (k - 1), per-axis pad / dilation, N*H*W*Cin_pad or
+ *   N*Ho*Wo*Cout_pad of 2^31 elements or more, channels padded to 64) -> query 0 and TDRN_E_UNSUPPORTED; a workspace below the
+ *   query -> TDRN_E_WORKSPACE.  One query serves all three entries.  No allocation and no host synchronisation: everything is
+ *   enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH,
+                                            int padW, int dilationH, int dilationW, tdrn_dtype compute);
+TDRN_API int tdrn_conv2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin,
+                                 int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                 int dilationW, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin,
+                                        int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                        int dilationH, int dilationW, tdrn_dtype compute, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight,
+                                             float *grad_bias, int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH,
+                                             int dW, int padH, int padW, int dilationH, int dilationW, float scale,
+                                             tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -1,4 +1,4 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i) and (ii) (section (iii) is in net.hip).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c) and (ii) (section (iii) is in net.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -72,6 +72,85 @@ int deform_bwd_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int 
     const size_t slab_end = rest + align_up((size_t)splits * p.taps * Cout * cpad * 4, 256);
     b.total = o > slab_end ? o : slab_end;
     return TDRN_OK;
+}
+
+// dense conv2d with gradients (section i-c).  Workspace: zero page | input NHWC | grad_output NHWC | the rest, which is either
+// {packed weight, padded bias, NHWC fp32 result, split-K partials of launch_conv} (forward, backward_input) or the split-K slabs (backward_parameters).
+struct Conv2dPlan {
+    ConvBwdGeom g;
+    int taps, CiPad, CoPad, NpadF, NpadD;
+    size_t o_zero, o_x, o_go, o_w, o_bias, o_out, o_partial, o_slab, total;
+};
+
+// the launch_conv arguments of the forward (dgrad = false) or of the input gradient -- a stride-1 conv over grad_output with
+// pad' = dil (k - 1) - pad -- without their pointers: fp32 NHWC result [pixels][Cout], no ReLU
+ConvArgs conv2d_args(const Conv2dPlan &p, bool dgrad, int dtype)
+{
+    const ConvBwdGeom &g = p.g;
+    ConvArgs a;
+    a.B = g.N;
+    if (!dgrad) { a.H = g.H; a.W = g.W; a.Cin = p.CiPad; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Cout; a.Npad = p.NpadF; a.pad = g.pad; }
+    else { a.H = g.Ho; a.W = g.Wo; a.Cin = p.CoPad; a.Ho = g.H; a.Wo = g.W; a.Cout = g.Cin; a.Npad = p.NpadD; a.pad = g.dil * (g.k - 1) - g.pad; }
+    a.kh = a.kw = g.k; a.stride = 1; a.dil = g.dil;
+    a.relu = 0; a.out_f32 = 1;
+    a.o_cs = a.Cout; a.o_rs = (long long)a.Wo * a.Cout; a.o_bs = (long long)a.Ho * a.Wo * a.Cout;
+    a.dtype = dtype;
+    // every shape on conv_igemm.hip: head3x3.hip would take the narrow 16-bit layers with another fp32 K order, and a layer's
+    // gradient should not change its rounding with its channel count
+    a.kdisable = KOFF_HEAD3X3;
+    a.splitk = conv_splitk_choice(a);      // the small-M layers (10 x 10, 5 x 5 maps) fill the chip by K slices, as in the engine
+    return a;
+}
+
+int conv2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
+                Conv2dPlan &p)
+{
+    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
+    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    const long long Ho = ((long long)H + 2ll * padH - ((long long)dilH * (kH - 1) + 1)) / dH + 1;
+    const long long Wo = ((long long)W + 2ll * padW - ((long long)dilW * (kW - 1) + 1)) / dW + 1;
+    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
+    if (Ho < 1 || Wo < 1) return TDRN_E_SHAPE;
+    // what the kernels cover: square k = 1 | 3, stride 1, one pad / dilation for both axes, pad <= dil (k - 1) (the input gradient
+    // is then a conv with pad' = dil (k - 1) - pad >= 0)
+    if (kH != kW || (kH != 1 && kH != 3) || dH != 1 || dW != 1 || padH != padW || dilH != dilW) return TDRN_E_UNSUPPORTED;
+    if ((long long)padH > (long long)dilH * (kH - 1)) return TDRN_E_UNSUPPORTED;
+    const int es = dtype_bytes(dtype);
+    p.taps = kH * kW;
+    p.CiPad = conv_bwd_cpad(Cin); p.CoPad = conv_bwd_cpad(Cout);
+    // 32-bit offsets of the kernels (conv_igemm.hip: elements; conv_bwd.hip: pixels)
+    if ((long long)N * H * W * p.CiPad >= (1ll << 31) || (long long)N * Ho * Wo * p.CoPad >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    if ((long long)dilH * (kH - 1) >= (1 << 20)) return TDRN_E_UNSUPPORTED;
+    p.g = ConvBwdGeom{N, Cin, H, W, Cout, kH, padH, dilH, (int)Ho, (int)Wo};
+    p.NpadF = conv_n_pad(Cout); p.NpadD = conv_n_pad(Cin);
+    const size_t wf = (size_t)p.NpadF * p.taps * p.CiPad * es, wd = (size_t)p.NpadD * p.taps * p.CoPad * es;
+    const size_t of = (size_t)N * Ho * Wo * Cout * 4, od = (size_t)N * H * W * Cin * 4;
+    size_t o = 0;
+    p.o_zero = o; o += kZeroPageBytes;
+    p.o_x = o;    o += align_up((size_t)N * H * W * p.CiPad * es, 256);
+    p.o_go = o;   o += align_up((size_t)N * Ho * Wo * p.CoPad * es, 256);
+    p.o_slab = o;
+    const size_t slab_end = o + conv_wgrad_slab_bytes(p.g);
+    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
+    p.o_bias = o; o += align_up((size_t)(p.NpadF > p.NpadD ? p.NpadF : p.NpadD) * 4, 256);
+    p.o_out = o;  o += align_up(of > od ? of : od, 256);
+    const ConvArgs af = conv2d_args(p, false, dtype), ad = conv2d_args(p, true, dtype);
+    const size_t pf = conv_splitk_bytes(af, af.splitk), pd = conv_splitk_bytes(ad, ad.splitk);
+    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
+    p.total = o > slab_end ? o : slab_end;
+    return TDRN_OK;
+}
+
+// launch_conv with an fp32 NHWC result [pixels][Cout] in the workspace, then NCHW into `out`
+int conv2d_run(const Conv2dPlan &p, char *ws, bool dgrad, int dtype, float *out, hipStream_t s)
+{
+    ConvArgs a = conv2d_args(p, dgrad, dtype);
+    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
+    a.out = ws + p.o_out;
+    if (a.splitk > 1) a.partial = ws + p.o_partial;
+    TDRN_TRY(launch_conv(a, s));
+    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.o_cs, out, p.g.N, a.Cout, a.Ho * a.Wo, s);
 }
 
 }  // namespace
@@ -182,6 +261,66 @@ int tdrn_deform_conv_backward_parameters(const float *input, const float *offset
     float *in_nhwc = (float *)(ws + b.o_in);
     TDRN_TRY(launch_nchw_to_nhwc_grouped(input, in_nhwc, N, Cin, H * W, deformable_group, deform_bwd_cpg64(b.g), TDRN_F32, s));
     return launch_deform_bwd_weight(b.g, in_nhwc, offset, grad_output, (float *)(ws + b.o_slab), grad_weight, scale, s);
+}
+
+size_t tdrn_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                   int dilationH, int dilationW, tdrn_dtype compute)
+{
+    Conv2dPlan p;
+    if (conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) != TDRN_OK) return 0;
+    return p.total;
+}
+
+int tdrn_conv2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W, int Cout,
+                        int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute,
+                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !output) return TDRN_E_ARG;
+    Conv2dPlan p;
+    TDRN_TRY(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.NpadF, Cin, p.taps, 1, p.CiPad, compute, s));
+    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_bias, 0, (size_t)p.NpadF * 4, s));
+    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+    return conv2d_run(p, ws, false, compute, output, s);
+}
+
+int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W, int Cout,
+                               int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
+    Conv2dPlan p;
+    TDRN_TRY(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
+    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.NpadD, p.taps, compute, s));
+    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_bias, 0, (size_t)p.NpadD * 4, s));
+    // a stride-1 conv over grad_output: kernel rotated and transposed (the packing above), pad' = dil (k - 1) - pad, same dilation
+    return conv2d_run(p, ws, true, compute, grad_input, s);
+}
+
+int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N, int Cin,
+                                    int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                    int dilationW, float scale, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
+    Conv2dPlan p;
+    TDRN_TRY(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
+    return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
 }
 
 size_t tdrn_nms_workspace_bytes(int n) { return nms_workspace_bytes(n); }

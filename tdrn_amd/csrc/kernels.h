@@ -246,6 +246,18 @@ int launch_deform_bwd_input_add(const DeformBwdGeom &g, const float *gin_nhwc, f
 void deform_bwd_weight_splits(const DeformBwdGeom &g, int &splits, int &per_split);
 int launch_deform_bwd_weight(const DeformBwdGeom &g, const float *in_nhwc, const float *off, const float *gout, float *slab, float *grad_weight,
                              float scale, hipStream_t s);
+// Dense stride-1 conv backward (conv_bwd.hip; tdrn_hip.h section i-c).  x_nhwc / go_nhwc: the input and grad_output as NHWC in the compute
+// type, channels padded to conv_bwd_cpad (launch_nchw_to_nhwc).  Square kernels k = 1 | 3, one pad / dilation for both axes.
+struct ConvBwdGeom { int N, Cin, H, W, Cout, k, pad, dil, Ho, Wo; };
+int conv_bwd_cpad(int c);
+// K splits of the weight gradient, from the geometry alone (the result does not depend on the device's state)
+void conv_wgrad_splits(const ConvBwdGeom &g, int &splits, int &per_split);
+size_t conv_wgrad_slab_bytes(const ConvBwdGeom &g);     // the fp32 slabs [splits][taps][CoutPad][CinPad] + [splits][CoutPad]
+// grad_weight (OIHW) += scale * sum_p go[p][co] x[p (+) tap][ci], grad_bias (or null) += scale * sum_p go[p][co]; fixed order, no atomics
+int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, float *grad_weight,
+                      float *grad_bias, float scale, int dtype, hipStream_t s);
+// OIHW fp32 -> launch_conv's packing of the input-gradient conv: out[ci][taps-1-tap][co] = w[co][ci][tap] ([Npad][taps][conv_bwd_cpad(Cout)])
+int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int Npad, int taps, int dtype, hipStream_t s);
 // transform-then-sample path of the 16-bit one-group heads (deform.hip): the caller computes Y = 1x1 GEMM of the input with the
 // per-tap weight slabs ([taps][80 columns] per pixel, deform_sample_cols(taps) channels), this launch blends the corners
 int deform_sample_supported(const DeformArgs &a);      // 0 = no, else the number of taps of all branches

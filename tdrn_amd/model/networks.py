@@ -1,6 +1,7 @@
 """Parameter-holder builders mirroring model/networks.py of the reference (vgg :136-163,
 conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615,
-ConvOffset2dFunction :617-697, ConvOffset2d :699-733).  The modules only own parameters with the reference's names and
+ConvOffset2dFunction :617-697, ConvOffset2d :699-733), plus the trainable dense conv (Conv2dFunction / conv2d / Conv2d: what
+nn.Conv2d and autograd give the reference's training loop).  The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import ctypes as C
 import math
@@ -172,3 +173,132 @@ class ConvOffset2d(nn.Module):
     def forward(self, input, offset):
         return conv_offset2d(input, offset, self.weight, self.stride, self.padding, self.dilation,
                              self.num_deformable_groups)
+
+
+def _conv2d_geometry(x, w, padding, dilation):
+    (ph, pw), (dh, dw) = _pair(padding), _pair(dilation)
+    N, Cin, H, W = x.shape
+    Cout, Cw, kh, kw = w.shape
+    if Cw != Cin:
+        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (Cw, Cin))
+    Ho = H + 2 * ph - (dh * (kh - 1) + 1) + 1
+    Wo = W + 2 * pw - (dw * (kw - 1) + 1) + 1
+    # the C ABI's argument order: N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW
+    return (N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw), (N, Cout, Ho, Wo)
+
+
+def _conv2d_workspace(lib, dims, dt, device):
+    nb = lib.tdrn_conv2d_workspace_bytes(*dims, dt)
+    if nb == 0:
+        raise RuntimeError("conv2d: geometry outside what libtdrn_hip covers (square k in {1, 3}, stride 1, "
+                           "0 <= pad <= dilation * (k - 1)): N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW = %r" % (dims,))
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+def _conv2d_forward(x, w, b, padding, dilation, compute):
+    lib = _lib.lib()
+    dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
+    dt = _lib.DTYPES[compute]
+    ws, nb = _conv2d_workspace(lib, dims, dt, x.device)
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    _lib.check(lib.tdrn_conv2d_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
+                                       _lib.current_stream(x.device)), "tdrn_conv2d_forward")
+    return out
+
+
+def _conv2d_require_cuda(input, weight, bias):
+    """a module left on the CPU is the likeliest mistake: its parameters must not reach the library as host pointers"""
+    _lib.require_cuda(input, "input")
+    _lib.require_cuda(weight, "weight")
+    if bias is not None:
+        _lib.require_cuda(bias, "bias")
+
+
+class Conv2dFunction(torch.autograd.Function):
+    """Dense stride-1 conv2d with gradients: forward through tdrn_conv2d_forward, backward through
+    tdrn_conv2d_backward_input (when the input needs a gradient) and tdrn_conv2d_backward_parameters (weight and bias
+    gradients, scale 1 into zeroed buffers).  `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the forward and
+    of both gradients.  Geometry the library rejects raises; nothing falls back to torch.
+
+        y = Conv2dFunction.apply(input, weight, bias_or_None, padding, dilation[, compute])
+    """
+
+    @staticmethod
+    def forward(ctx, input, weight, bias=None, padding=0, dilation=1, compute="fp32"):
+        if input.dim() != 4:
+            raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+        _conv2d_require_cuda(input, weight, bias)
+        x, w = input.contiguous().float(), weight.contiguous().float()
+        b = None if bias is None else bias.contiguous().float()
+        out = _conv2d_forward(x, w, b, padding, dilation, compute)
+        ctx.conf = (padding, dilation, compute, bias is not None)
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, w = ctx.saved_tensors
+        if not grad_output.is_cuda:
+            raise NotImplementedError("conv2d backward: grad_output must be a CUDA tensor")
+        padding, dilation, compute, has_bias = ctx.conf
+        lib = _lib.lib()
+        dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
+        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
+        if tuple(go.shape) != out_shape:
+            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
+        need_in, need_w = ctx.needs_input_grad[:2]
+        need_b = has_bias and ctx.needs_input_grad[2]
+        grad_input = grad_weight = grad_bias = None
+        if need_in or need_w or need_b:
+            dt = _lib.DTYPES[compute]
+            ws, nb = _conv2d_workspace(lib, dims, dt, x.device)
+            stream = _lib.current_stream(x.device)
+        if need_in:
+            grad_input = torch.empty_like(x)
+            _lib.check(lib.tdrn_conv2d_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws), nb,
+                                                      stream), "tdrn_conv2d_backward_input")
+        if need_w or need_b:
+            gw = torch.zeros_like(w)
+            gb = torch.zeros(w.shape[0], dtype=torch.float32, device=x.device) if need_b else None
+            _lib.check(lib.tdrn_conv2d_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
+                                                           _lib.ptr(ws), nb, stream), "tdrn_conv2d_backward_parameters")
+            grad_weight = gw if need_w else None
+            grad_bias = gb
+        return grad_input, grad_weight, grad_bias, None, None, None
+
+
+def conv2d(input, weight, bias=None, padding=0, dilation=1, compute="fp32"):
+    """Dense stride-1 conv2d on libtdrn_hip (NCHW fp32 CUDA tensors in, NCHW fp32 out), differentiable in input, weight and
+    bias.  With grad mode off, or when nothing requires grad, only the forward runs and the output has no grad_fn."""
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _conv2d_require_cuda(input, weight, bias)
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return Conv2dFunction.apply(input, weight, bias, padding, dilation, compute)
+    x, w = input.contiguous().float(), weight.detach().contiguous().float()
+    b = None if bias is None else bias.detach().contiguous().float()
+    return _conv2d_forward(x, w, b, padding, dilation, compute)
+
+
+class Conv2d(nn.Module):
+    """nn.Conv2d's parameters and default init (weight, bias) on conv2d above: stride 1, groups 1."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, dilation=1, bias=True, compute="fp32"):
+        super(Conv2d, self).__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.padding, self.dilation = _pair(kernel_size), _pair(padding), _pair(dilation)
+        self.compute = compute
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            fan_in = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
+            bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, input):
+        return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute)

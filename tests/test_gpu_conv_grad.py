@@ -1,0 +1,295 @@
+"""Dense conv2d with gradients (tdrn_hip.h section i-c; Conv2dFunction / conv2d / Conv2d) against torch's CPU autograd in
+float64.
+
+Oracle: torch.nn.functional.conv2d on the CPU in float64, differentiated by autograd, fed the exact inputs the op used: in the
+16-bit modes input, weight and grad_output are rounded to the type first (bias is not).
+
+Bounds.  fp32 mode: |got - ref| <= 1e-4 * max(1, max|ref|), as in test_gpu_deform_grad.py.  16-bit modes: the inputs are
+exact, the products are exact in fp32, so only the fp32 accumulation is left: |got - ref| <= c * S elementwise, S = the same
+convolution on absolute values (wgrad: sum_p |GO| |X|; forward: + |bias|), c = C_ACC of test_gpu_pin16.py (2e-6 bf16,
+4e-5 fp16).  Outputs are fp32: no output-rounding term, no element is exempted.
+"""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tdrn_amd import _lib
+from tdrn_amd.model import networks
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+# N, Cin, H, W, Cout, k, pad, dil
+CASES = {
+    "first_conv_3ch": (1, 3, 8, 8, 4, 3, 1, 1),            # channel padding 3 -> 64
+    "odd_two_images": (2, 6, 9, 7, 4, 3, 1, 1),            # H != W, odd sizes, two images
+    "tiny_images": (3, 32, 5, 5, 256, 3, 1, 1),            # images smaller than a pixel chunk: padding across image boundaries
+    "ragged_tiles": (1, 192, 12, 11, 130, 3, 1, 1),        # several cin and cout tiles, ragged last tile
+    "k800": (2, 64, 20, 20, 75, 3, 1, 1),                  # K = 800, no multiple of the chunk
+    "dil2": (1, 16, 9, 9, 8, 3, 2, 2),
+    "conv6": (1, 16, 13, 13, 24, 3, 6, 6),                 # conv6's geometry: most taps in the padding
+    "valid": (1, 8, 10, 9, 8, 3, 0, 1),                    # valid conv: pad' = 2 in dgrad, Ho x Wo = 8 x 7
+    "1x1": (2, 140, 6, 6, 12, 1, 0, 1),
+    "k6400_split": (4, 64, 40, 40, 64, 3, 1, 1),           # K = 6400: more than one K split (DESIGN 11 lists conv_wgrad_splits = 25)
+    # beyond the issue's table
+    "full_pad2": (2, 70, 12, 10, 40, 3, 2, 1),             # pad = dil (k - 1): Ho x Wo = 14 x 12 > H x W, pad' = 0 in dgrad, K = 336
+    "dil30": (1, 8, 40, 40, 8, 3, 30, 30),                 # a dilation larger than the image: eight of nine taps all padding, K = 1600
+}
+DT = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
+C_ACC = {"bf16": 2e-6, "fp16": 4e-5}
+
+
+def _dims(case):
+    N, Cin, H, W, Cout, k, pad, dil = CASES[case]
+    return (N, Cin, H, W, Cout, k, k, 1, 1, pad, pad, dil, dil)
+
+
+def _out_hw(case):
+    N, Cin, H, W, Cout, k, pad, dil = CASES[case]
+    return H + 2 * pad - dil * (k - 1), W + 2 * pad - dil * (k - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(case):
+    N, Cin, H, W, Cout, k, pad, dil = CASES[case]
+    Ho, Wo = _out_hw(case)
+    gen = torch.Generator().manual_seed(sorted(CASES).index(case) + 11)
+    x = torch.randn(N, Cin, H, W, generator=gen)
+    w = torch.randn(Cout, Cin, k, k, generator=gen) * (Cin * k * k) ** -0.5
+    b = torch.randn(Cout, generator=gen)
+    go = torch.randn(N, Cout, Ho, Wo, generator=gen)
+    return x, w, b, go
+
+
+def _round(t, mode):
+    return t if DT[mode] is None else t.to(DT[mode]).float()
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case, mode):
+    """float64 CPU autograd on the inputs as the op uses them -> ((y, gx, gw, gb), (Sy, Sgx, Sgw, Sgb)); computed once, never changed"""
+    N, Cin, H, W, Cout, k, pad, dil = CASES[case]
+    x, w, b, go = _inputs(case)
+    xr, wr, gr = (_round(t, mode).double() for t in (x, w, go))
+
+    def run(xx, ww, bb, gg):
+        xx, ww, bb = (t.clone().requires_grad_(True) for t in (xx, ww, bb))
+        y = F.conv2d(xx, ww, bb, 1, pad, dil)
+        gx, gw, gb = torch.autograd.grad(y, (xx, ww, bb), gg)
+        return y.detach(), gx, gw, gb
+    return run(xr, wr, b.double(), gr), run(xr.abs(), wr.abs(), b.double().abs(), gr.abs())
+
+
+def _check(case, mode, names, got):
+    ref, S = _reference(case, mode)
+    idx = {"output": 0, "grad_input": 1, "grad_weight": 2, "grad_bias": 3}
+    for name, g in zip(names, got):
+        r, s = ref[idx[name]], S[idx[name]]
+        d = (g.detach().cpu().double() - r).abs()
+        assert torch.isfinite(d).all(), "%s %s %s: non-finite values" % (case, mode, name)
+        if mode == "fp32":
+            bound = 1e-4 * max(1.0, float(r.abs().max()))
+            print("%s %s %-11s max|d| %.3e  bound %.3e" % (case, mode, name, float(d.max()), bound))
+            assert float(d.max()) <= bound, (case, mode, name, float(d.max()), bound)
+        else:
+            ratio = float((d / s.clamp_min(1e-300)).max())
+            print("%s %s %-11s max|d|/S %.3e  c %.1e" % (case, mode, name, ratio, C_ACC[mode]))
+            assert bool((d <= C_ACC[mode] * s).all()), (case, mode, name, ratio, C_ACC[mode])
+
+
+class Abi(object):
+    """the four C entries on plain device buffers"""
+
+    def __init__(self, case, mode):
+        self.lib, self.dims, self.dt = _lib.lib(), _dims(case), _lib.DTYPES[mode]
+        self.nb = self.lib.tdrn_conv2d_workspace_bytes(*self.dims, self.dt)
+        assert self.nb > 0
+        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=DEV)
+        self.x, self.w, self.b, self.go = (t.to(DEV) for t in _inputs(case))
+        self.st = _lib.current_stream(DEV)
+
+    def forward(self, out, bias=True):
+        _lib.check(self.lib.tdrn_conv2d_forward(_lib.ptr(self.x), _lib.ptr(self.w), _lib.ptr(self.b if bias else None), _lib.ptr(out),
+                                                *self.dims, self.dt, _lib.ptr(self.ws), self.nb, self.st))
+        return out
+
+    def backward_input(self, gi):
+        _lib.check(self.lib.tdrn_conv2d_backward_input(_lib.ptr(self.go), _lib.ptr(self.w), _lib.ptr(gi), *self.dims, self.dt,
+                                                       _lib.ptr(self.ws), self.nb, self.st))
+        return gi
+
+    def backward_parameters(self, gw, gb, scale=1.0):
+        _lib.check(self.lib.tdrn_conv2d_backward_parameters(_lib.ptr(self.x), _lib.ptr(self.go), _lib.ptr(gw), _lib.ptr(gb), *self.dims,
+                                                            scale, self.dt, _lib.ptr(self.ws), self.nb, self.st))
+        return gw, gb
+
+    def all(self):
+        out = self.forward(torch.full_like(self.go, float("nan")))
+        gi = self.backward_input(torch.full_like(self.x, float("nan")))
+        gw, gb = self.backward_parameters(torch.zeros_like(self.w), torch.zeros_like(self.b))
+        torch.cuda.synchronize()
+        return out, gi, gw, gb
+
+
+@pytest.mark.parametrize("mode", list(DT))
+@pytest.mark.parametrize("case", list(CASES))
+def test_conv2d_abi_matches_float64_autograd(case, mode):
+    _check(case, mode, ("output", "grad_input", "grad_weight", "grad_bias"), Abi(case, mode).all())
+
+
+@pytest.mark.parametrize("mode", list(DT))
+@pytest.mark.parametrize("case", list(CASES))
+def test_conv2d_autograd_matches_float64_autograd(case, mode):
+    N, Cin, H, W, Cout, k, pad, dil = CASES[case]
+    x, w, b, go = (t.to(DEV) for t in _inputs(case))
+    x, w, b = (t.requires_grad_(True) for t in (x, w, b))
+    y = networks.conv2d(x, w, b, padding=pad, dilation=dil, compute=mode)
+    y.backward(go)
+    _check(case, mode, ("output", "grad_input", "grad_weight", "grad_bias"), (y, x.grad, w.grad, b.grad))
+
+
+def test_conv2d_parameter_gradients_accumulate_and_the_rest_is_overwritten():
+    a = Abi("k800", "fp32")
+    gw, gb = a.backward_parameters(torch.zeros_like(a.w), torch.zeros_like(a.b))
+    gw1, gb1 = gw.clone(), gb.clone()
+    a.backward_parameters(gw, gb, scale=0.5)
+    # fl(g + fl(0.5 s)) against 1.5 g with g = fl(s): two roundings of fp32
+    for got, one in ((gw, gw1), (gb, gb1)):
+        assert float((got - 1.5 * one).abs().max()) <= 4 * 2.0 ** -24 * float(one.abs().max())
+    out = a.forward(torch.full_like(a.go, float("nan")))
+    out2 = a.forward(torch.full_like(a.go, float("nan")))
+    gi = a.backward_input(torch.full_like(a.x, float("nan")))
+    gi2 = a.backward_input(torch.full_like(a.x, float("nan")))
+    assert torch.equal(out, out2) and torch.equal(gi, gi2)
+    assert bool(torch.isfinite(out2).all()) and bool(torch.isfinite(gi2).all())
+    _check("k800", "fp32", ("grad_weight", "grad_bias"), (gw1, gb1))
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp32"])
+def test_conv2d_is_bitwise_reproducible(mode):
+    a = Abi("k6400_split", mode)
+    first = [t.clone() for t in a.all()]
+    # other work on the device in between must not change the arithmetic
+    Abi("ragged_tiles", mode).all()
+    second = a.all()
+    for name, p, q in zip(("output", "grad_input", "grad_weight", "grad_bias"), first, second):
+        assert torch.equal(p.view(torch.int32), q.view(torch.int32)), name
+
+
+SENTINEL = 0x7FBADBAD
+GUARD = 4096
+
+
+class Guarded(object):
+    """`nbytes` of device memory that start `offset` bytes behind a 256-byte boundary, between two guard bands of a NaN pattern no
+    kernel computes (the pattern of test_gpu_caller_memory.py)"""
+
+    def __init__(self, shape=None, offset=0, nbytes=None, init=None):
+        n = int(nbytes) if nbytes is not None else 4 * int(torch.Size(shape).numel())
+        total = 2 * GUARD + 256 + offset + n
+        self.raw = torch.full(((total + 3) // 4,), SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)
+        base = (-self.raw.data_ptr()) % 256 + GUARD
+        self.lo, self.hi = base + offset, base + offset + n
+        body = self.raw[self.lo:self.hi]
+        self.t = body if shape is None else body.view(torch.float32).view(shape)
+        if init is not None:
+            self.t.copy_(init)
+
+    def check(self, what, full=True):
+        torch.cuda.synchronize()
+        words = self.raw.view(torch.int32)
+        assert self.lo % 4 == 0 and self.hi % 4 == 0
+        assert bool((words[:self.lo // 4] == SENTINEL).all()), "%s: bytes in front of the buffer were written" % what
+        assert bool((words[self.hi // 4:] == SENTINEL).all()), "%s: bytes behind the end of the buffer were written" % what
+        if full:
+            assert int((words[self.lo // 4:self.hi // 4] == SENTINEL).sum()) == 0, "%s: elements never written" % what
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp32"])
+@pytest.mark.parametrize("case", ["ragged_tiles", "odd_two_images", "1x1", "full_pad2"])
+def test_conv2d_writes_only_the_callers_buffers(case, mode):
+    a = Abi(case, mode)
+    want = [t.clone() for t in a.all()]
+    ws = Guarded(nbytes=a.nb)                      # exactly the queried size
+    a.ws = ws.t
+    assert ws.t.data_ptr() % 256 == 0
+    out = Guarded(a.go.shape, offset=4)            # 4 bytes behind a 256-byte boundary
+    gi = Guarded(a.x.shape, offset=4)
+    gw = Guarded(a.w.shape, offset=4, init=torch.zeros_like(a.w))
+    gb = Guarded(a.b.shape, offset=4, init=torch.zeros_like(a.b))
+    assert out.t.data_ptr() % 256 == 4
+    a.forward(out.t)
+    a.backward_input(gi.t)
+    a.backward_parameters(gw.t, gb.t)
+    for name, g, w in zip(("output", "grad_input", "grad_weight", "grad_bias"), (out, gi, gw, gb), want):
+        g.check("%s %s %s" % (case, mode, name))
+        assert torch.equal(g.t.contiguous().view(torch.int32), w.view(torch.int32)), name
+    ws.check("%s %s workspace" % (case, mode), full=False)
+
+
+def test_conv2d_autograd_plumbing():
+    case, mode = "odd_two_images", "fp32"
+    N, Cin, H, W, Cout, k, pad, dil = CASES[case]
+    x0, w0, b0, _ = (t.to(DEV) for t in _inputs(case))
+    for need in ((True, True, True), (True, False, False), (False, True, False), (False, False, True), (False, True, True)):
+        x, w, b = (t.clone().requires_grad_(n) for t, n in zip((x0, w0, b0), need))
+        y = networks.conv2d(x, w, b, padding=pad, dilation=dil, compute=mode)
+        assert y.requires_grad
+        y.sum().backward()                           # a stride-0 grad_output
+        for t, n in zip((x, w, b), need):
+            assert (t.grad is not None) == n
+    with torch.no_grad():
+        assert networks.conv2d(x0.clone().requires_grad_(True), w0, b0, padding=pad).grad_fn is None
+    assert networks.conv2d(x0, w0, b0, padding=pad).grad_fn is None
+    # the gradient of sum(y), and bias=None
+    x, w = x0.clone().requires_grad_(True), w0.clone().requires_grad_(True)
+    y = networks.conv2d(x, w, None, padding=pad, dilation=dil, compute=mode)
+    y.sum().backward()
+    xr, wr = x0.cpu().double().requires_grad_(True), w0.cpu().double().requires_grad_(True)
+    yr = F.conv2d(xr, wr, None, 1, pad, dil)
+    yr.sum().backward()
+    for got, ref in ((y, yr), (x.grad, xr.grad), (w.grad, wr.grad)):
+        assert float((got.detach().cpu().double() - ref.detach()).abs().max()) <= 1e-4 * max(1.0, float(ref.abs().max()))
+    # geometry the ABI rejects raises (no fallback): stride is not even an argument, k = 5 is refused
+    with pytest.raises(RuntimeError):
+        networks.conv2d(x0, torch.zeros(Cout, Cin, 5, 5, device=DEV), None, padding=2)
+    # a module left on the CPU: its parameters must not reach the library as host pointers
+    with pytest.raises(NotImplementedError):
+        networks.Conv2d(Cin, Cout, 3, padding=1)(x0)
+    m = networks.Conv2d(Cin, Cout, 3, padding=1).to(DEV)
+    m(x0).mean().backward()
+    assert m.weight.grad is not None and m.bias.grad is not None
+
+
+def test_conv2d_short_training_run_follows_float64():
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 16, 10, 10, generator=gen)
+    target = torch.randn(2, 8, 10, 10, generator=gen)
+    w1 = torch.randn(32, 16, 3, 3, generator=gen) * (16 * 9) ** -0.5
+    b1 = torch.randn(32, generator=gen) * 0.1
+    w2 = torch.randn(8, 32, 1, 1, generator=gen) * 32 ** -0.5
+    b2 = torch.randn(8, generator=gen) * 0.1
+
+    def loop(params, x, target, conv):
+        losses = []
+        for _ in range(3):
+            h = torch.relu(conv(x, params[0], params[1], 1))
+            loss = ((conv(h, params[2], params[3], 0) - target) ** 2).mean()
+            grads = torch.autograd.grad(loss, params)
+            with torch.no_grad():
+                for p, g in zip(params, grads):
+                    p -= 0.5 * g
+            losses.append(float(loss))
+        return losses
+
+    ours = [t.clone().to(DEV).requires_grad_(True) for t in (w1, b1, w2, b2)]
+    ref = [t.clone().double().requires_grad_(True) for t in (w1, b1, w2, b2)]
+    l_ours = loop(ours, x.to(DEV), target.to(DEV), lambda i, w, b, p: networks.conv2d(i, w, b, padding=p, compute="fp32"))
+    l_ref = loop(ref, x.double(), target.double(), lambda i, w, b, p: F.conv2d(i, w, b, 1, p))
+    assert l_ours[0] > l_ours[1] > l_ours[2], l_ours
+    assert l_ref[0] > l_ref[1] > l_ref[2], l_ref
+    for p, r in zip(ours, ref):
+        d = float((p.detach().cpu().double() - r.detach()).abs().max())
+        assert d <= 1e-4 * max(1.0, float(r.abs().max())), d
