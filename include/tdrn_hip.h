@@ -148,6 +148,39 @@ TDRN_API int tdrn_conv2d_backward_parameters(const float *input, const float *gr
                                              tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-d) BatchNorm2d with an optional fused ReLU, forward and backward -- what nn.BatchNorm2d + nn.ReLU + autograd give the
+ *     reference's training loop (the fifteen pairs of model/dualrefinedet_vggbn.py; vgg(), model/networks.py:136-163).
+ *   input / output / grad_output / grad_input (N, C, H, W); weight, bias, running_mean, running_var, save_mean, save_invstd,
+ *   grad_weight, grad_bias (C): all fp32, contiguous, device, on any 4-byte boundary.  M = N*H*W values per channel.
+ *   forward, training = 1: mean and biased variance of the batch (chunked Welford records merged with Chan's formula, never
+ *                        E[x^2] - E[x]^2) -> save_mean, save_invstd = 1 / sqrt(var + eps); running_mean = (1 - momentum) running_mean +
+ *                        momentum mean and running_var likewise with the UNBIASED variance M2 / (M - 1), once per call
+ *                        (nn.BatchNorm2d's semantics; both NULL: nothing is updated).
+ *            training = 0: save_mean = running_mean, save_invstd = 1 / sqrt(running_var + eps); the running buffers are only read.
+ *            z = (input - save_mean) (weight save_invstd) + bias; output = relu ? max(z, 0) : z, OVERWRITTEN.
+ *   backward: dy' = grad_output [z > 0] with z recomputed from input (relu = 0: dy' = grad_output), xhat = (input - save_mean) save_invstd;
+ *            grad_weight += scale sum dy' xhat, grad_bias += scale sum dy' (both or neither; NULL: not computed);
+ *            grad_input (NULL: not computed) is OVERWRITTEN with weight save_invstd (dy' - (sum dy' + xhat sum dy' xhat) / M) for
+ *            training = 1 and with weight save_invstd dy' for training = 0.  One of grad_input and the pair is required.
+ *   A channel's reduction is cut into splits that depend on (N, C, H*W) alone and merged in split order: no float atomics, every
+ *   output of both entries is bitwise reproducible, and the same for a buffer on any 4-byte boundary.
+ *   The query returns 12 C splits + 8 C bytes and serves both entries.
+ *   Errors, all decided before any launch: a null required pointer, a pointer off a 4-byte boundary, grad_weight without grad_bias,
+ *   training = 0 without running buffers -> TDRN_E_ARG; N / C / H / W <= 0 -> query 0 and TDRN_E_SHAPE; training = 1 with M = 1 ->
+ *   TDRN_E_SHAPE (M = 2 is legal); N*C*H*W >= 2^31 -> query 0 and TDRN_E_UNSUPPORTED; eps <= 0 or momentum outside [0, 1] -> TDRN_E_ARG;
+ *   a workspace below the query -> TDRN_E_WORKSPACE.  No allocation and no host synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W);
+TDRN_API int tdrn_batch_norm_forward(const float *input, const float *weight, const float *bias, float *running_mean,
+                                     float *running_var, float *output, float *save_mean, float *save_invstd, int N, int C, int H,
+                                     int W, int training, float momentum, float eps, int relu, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_batch_norm_backward(const float *input, const float *grad_output, const float *weight, const float *bias,
+                                      const float *save_mean, const float *save_invstd, float *grad_input, float *grad_weight,
+                                      float *grad_bias, int N, int C, int H, int W, int training, int relu, float scale,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -1,4 +1,4 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c) and (ii) (section (iii) is in net.hip).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d) and (ii) (section (iii) is in net.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -152,6 +152,19 @@ int conv2d_run(const Conv2dPlan &p, char *ws, bool dgrad, int dtype, float *out,
     TDRN_TRY(launch_conv(a, s));
     return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.o_cs, out, p.g.N, a.Cout, a.Ho * a.Wo, s);
 }
+
+// BatchNorm2d (section i-d): the geometry checks of the query and of both entries
+int batch_norm_plan(int N, int C, int H, int W, size_t &bytes)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
+    // 32-bit element offsets of the kernels
+    const long long HW = (long long)H * W, NC = (long long)N * C;
+    if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    bytes = batch_norm_workspace_bytes(N, C, H * W);
+    return TDRN_OK;
+}
+
+bool off_dword(const void *p) { return ((uintptr_t)p & 3) != 0; }
 
 }  // namespace
 
@@ -321,6 +334,47 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
     TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
     TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
     return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+}
+
+size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W)
+{
+    size_t bytes;
+    return batch_norm_plan(N, C, H, W, bytes) == TDRN_OK ? bytes : 0;
+}
+
+int tdrn_batch_norm_forward(const float *input, const float *weight, const float *bias, float *running_mean, float *running_var,
+                            float *output, float *save_mean, float *save_invstd, int N, int C, int H, int W, int training, float momentum,
+                            float eps, int relu, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !bias || !output || !save_mean || !save_invstd) return TDRN_E_ARG;
+    if (!running_mean != !running_var || (!training && !running_mean)) return TDRN_E_ARG;
+    if (off_dword(input) || off_dword(weight) || off_dword(bias) || off_dword(running_mean) || off_dword(running_var) || off_dword(output) ||
+        off_dword(save_mean) || off_dword(save_invstd) || off_dword(workspace))
+        return TDRN_E_ARG;
+    size_t bytes;
+    TDRN_TRY(batch_norm_plan(N, C, H, W, bytes));
+    if (training && (long long)N * H * W == 1) return TDRN_E_SHAPE;     // one value per channel has no variance
+    if (!(eps > 0.f) || !(momentum >= 0.f && momentum <= 1.f)) return TDRN_E_ARG;
+    if (!workspace || workspace_bytes < bytes) return TDRN_E_WORKSPACE;
+    return launch_batch_norm_forward(input, weight, bias, running_mean, running_var, output, save_mean, save_invstd, N, C, H * W,
+                                     training != 0, momentum, eps, relu != 0, workspace, (hipStream_t)stream);
+}
+
+int tdrn_batch_norm_backward(const float *input, const float *grad_output, const float *weight, const float *bias, const float *save_mean,
+                             const float *save_invstd, float *grad_input, float *grad_weight, float *grad_bias, int N, int C, int H, int W,
+                             int training, int relu, float scale, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !grad_output || !weight || !bias || !save_mean || !save_invstd) return TDRN_E_ARG;
+    if (!grad_weight != !grad_bias || (!grad_input && !grad_weight)) return TDRN_E_ARG;
+    if (off_dword(input) || off_dword(grad_output) || off_dword(weight) || off_dword(bias) || off_dword(save_mean) || off_dword(save_invstd) ||
+        off_dword(grad_input) || off_dword(grad_weight) || off_dword(grad_bias) || off_dword(workspace))
+        return TDRN_E_ARG;
+    size_t bytes;
+    TDRN_TRY(batch_norm_plan(N, C, H, W, bytes));
+    if (training && (long long)N * H * W == 1) return TDRN_E_SHAPE;
+    if (!workspace || workspace_bytes < bytes) return TDRN_E_WORKSPACE;
+    return launch_batch_norm_backward(input, grad_output, weight, bias, save_mean, save_invstd, grad_input, grad_weight, grad_bias, N, C,
+                                      H * W, training != 0, relu != 0, scale, workspace, (hipStream_t)stream);
 }
 
 size_t tdrn_nms_workspace_bytes(int n) { return nms_workspace_bytes(n); }

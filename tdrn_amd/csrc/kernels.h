@@ -258,6 +258,19 @@ int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_n
                       float *grad_bias, float scale, int dtype, hipStream_t s);
 // OIHW fp32 -> launch_conv's packing of the input-gradient conv: out[ci][taps-1-tap][co] = w[co][ci][tap] ([Npad][taps][conv_bwd_cpad(Cout)])
 int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int Npad, int taps, int dtype, hipStream_t s);
+// BatchNorm2d with an optional fused ReLU, fp32 NCHW (batch_norm.hip; tdrn_hip.h section i-d).  Every pass cuts a channel's N*HW values
+// into `splits` pieces of per_split elements, from (N, C, HW) alone; the workspace holds the per-(channel, split) records of the reducing
+// passes and the backward's per-channel sums: 12 C splits + 8 C bytes
+void batch_norm_splits(int N, int C, int HW, int &splits, int &per_split);
+size_t batch_norm_workspace_bytes(int N, int C, int HW);
+// training: batch statistics -> save_mean / save_invstd, the running buffers (or null) updated once; else they are read.  output is overwritten
+int launch_batch_norm_forward(const float *input, const float *weight, const float *bias, float *running_mean, float *running_var,
+                              float *output, float *save_mean, float *save_invstd, int N, int C, int HW, int training, float momentum,
+                              float eps, int relu, void *ws, hipStream_t s);
+// grad_input (or null) is overwritten; grad_weight / grad_bias (both or neither) += scale * their sums, merged in split order
+int launch_batch_norm_backward(const float *input, const float *grad_output, const float *weight, const float *bias, const float *save_mean,
+                               const float *save_invstd, float *grad_input, float *grad_weight, float *grad_bias, int N, int C, int HW,
+                               int training, int relu, float scale, void *ws, hipStream_t s);
 // transform-then-sample path of the 16-bit one-group heads (deform.hip): the caller computes Y = 1x1 GEMM of the input with the
 // per-tap weight slabs ([taps][80 columns] per pixel, deform_sample_cols(taps) channels), this launch blends the corners
 int deform_sample_supported(const DeformArgs &a);      // 0 = no, else the number of taps of all branches

@@ -1,7 +1,8 @@
 """Parameter-holder builders mirroring model/networks.py of the reference (vgg :136-163,
 conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615,
 ConvOffset2dFunction :617-697, ConvOffset2d :699-733), plus the trainable dense conv (Conv2dFunction / conv2d / Conv2d: what
-nn.Conv2d and autograd give the reference's training loop).  The modules only own parameters with the reference's names and
+nn.Conv2d and autograd give the reference's training loop) and the trainable batch norm with a fused ReLU (BatchNormFunction /
+batch_norm / BatchNorm2d).  The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import ctypes as C
 import math
@@ -302,3 +303,147 @@ class Conv2d(nn.Module):
 
     def forward(self, input):
         return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute)
+
+
+def _batch_norm_check(input, running_mean, running_var, weight, bias, training):
+    if input.dim() != 4:
+        raise ValueError("expected 4D input (got {}D input)".format(input.dim()))
+    _lib.require_cuda(input, "input")
+    for name, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is None:
+            if name in ("weight", "bias") or not training:
+                raise ValueError("batch_norm: %s is required%s" % (name, "" if training else " when training is False"))
+            continue
+        _lib.require_cuda(t, name)          # a module left on the CPU must not reach the library as host pointers
+        if tuple(t.shape) != (input.shape[1],):
+            raise RuntimeError("batch_norm: %s has shape %r, expected (%d,)" % (name, tuple(t.shape), input.shape[1]))
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("batch_norm: running_mean and running_var come as a pair")
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        # they are updated in place through their address: a copy would take the update with it
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("batch_norm: %s must be a contiguous float32 tensor" % name)
+    if training and input.numel() == input.shape[1]:
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(input.size()))
+
+
+def _batch_norm_workspace(lib, dims, device):
+    nb = lib.tdrn_batch_norm_workspace_bytes(*dims)
+    if nb == 0:
+        raise RuntimeError("batch_norm: shape outside what libtdrn_hip covers (positive sizes, fewer than 2^31 elements): "
+                           "N, C, H, W = %r" % (dims,))
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+def _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu):
+    lib = _lib.lib()
+    dims = tuple(x.shape)
+    ws, nb = _batch_norm_workspace(lib, dims, x.device)
+    out = torch.empty_like(x)
+    save_mean = torch.empty(dims[1], dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty_like(save_mean)
+    _lib.check(lib.tdrn_batch_norm_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                           _lib.ptr(out), _lib.ptr(save_mean), _lib.ptr(save_invstd), *dims, int(bool(training)),
+                                           float(momentum), float(eps), int(bool(relu)), _lib.ptr(ws), nb,
+                                           _lib.current_stream(x.device)), "tdrn_batch_norm_forward")
+    return out, save_mean, save_invstd
+
+
+class BatchNormFunction(torch.autograd.Function):
+    """BatchNorm2d with an optional fused ReLU and gradients: forward through tdrn_batch_norm_forward, backward through
+    tdrn_batch_norm_backward (scale 1 into zeroed parameter gradients; only what needs_input_grad asks for is computed).  Saves
+    the input and the statistics, no ReLU output and no mask: the backward recomputes the mask from the input.  The running
+    buffers (or None, in training) are updated in place.
+
+        y = BatchNormFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+    """
+
+    @staticmethod
+    def forward(ctx, input, running_mean, running_var, weight, bias, training=True, momentum=0.1, eps=1e-5, relu=False):
+        _batch_norm_check(input, running_mean, running_var, weight, bias, training)
+        x, w, b = input.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
+        out, save_mean, save_invstd = _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)
+        ctx.conf = (bool(training), bool(relu))
+        ctx.save_for_backward(x, w, b, save_mean, save_invstd)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, w, b, save_mean, save_invstd = ctx.saved_tensors
+        if not grad_output.is_cuda:
+            raise NotImplementedError("batch_norm backward: grad_output must be a CUDA tensor")
+        training, relu = ctx.conf
+        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
+        if go.shape != x.shape:
+            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(x.shape)))
+        need_in, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        grad_input = gw = gb = None
+        if need_in or need_w or need_b:
+            lib = _lib.lib()
+            dims = tuple(x.shape)
+            ws, nb = _batch_norm_workspace(lib, dims, x.device)
+            if need_in:
+                grad_input = torch.empty_like(x)
+            if need_w or need_b:
+                gw, gb = torch.zeros_like(w), torch.zeros_like(b)
+            _lib.check(lib.tdrn_batch_norm_backward(_lib.ptr(x), _lib.ptr(go), _lib.ptr(w), _lib.ptr(b), _lib.ptr(save_mean),
+                                                    _lib.ptr(save_invstd), _lib.ptr(grad_input), _lib.ptr(gw), _lib.ptr(gb), *dims,
+                                                    int(training), int(relu), 1.0, _lib.ptr(ws), nb, _lib.current_stream(x.device)),
+                       "tdrn_batch_norm_backward")
+        return grad_input, None, None, gw if need_w else None, gb if need_b else None, None, None, None, None
+
+
+def batch_norm(input, running_mean, running_var, weight, bias, training, momentum=0.1, eps=1e-5, relu=False):
+    """F.batch_norm for NCHW fp32 CUDA tensors on libtdrn_hip, with `relu=True` fusing the ReLU behind it; differentiable in input,
+    weight and bias.  In training the running buffers (float32, contiguous; or both None) are updated in place with `momentum`,
+    nn.BatchNorm2d's semantics.  With grad mode off, or when nothing requires grad, only the forward runs and the output has no
+    grad_fn."""
+    _batch_norm_check(input, running_mean, running_var, weight, bias, training)
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or bias.requires_grad):
+        return BatchNormFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+    x, w, b = input.detach().contiguous().float(), weight.detach().contiguous().float(), bias.detach().contiguous().float()
+    return _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)[0]
+
+
+class BatchNorm2d(nn.Module):
+    """nn.BatchNorm2d's parameters, buffers, state_dict keys and default init on batch_norm above, with `relu=True` fusing the
+    nn.ReLU that follows it in the reference's nets.  Always affine, always tracking running statistics.  `momentum=None` is the
+    cumulative average; its factor 1 / num_batches_tracked comes from a host-side count, never from a device read."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, relu=False):
+        super(BatchNorm2d, self).__init__()
+        self.num_features, self.eps, self.momentum, self.relu = num_features, eps, momentum, relu
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        self._batches = 0        # num_batches_tracked as the host knows it
+
+    def reset_running_stats(self):
+        self.running_mean.zero_()
+        self.running_var.fill_(1)
+        self.num_batches_tracked.zero_()
+        self._batches = 0
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super(BatchNorm2d, self)._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        key = prefix + "num_batches_tracked"
+        if key in state_dict:
+            self._batches = int(state_dict[key])        # at load time, off the training path
+
+    def forward(self, input):
+        factor = 0.0 if self.momentum is None else self.momentum
+        if self.training:
+            # checked before the count moves: a refused call is no tracked batch
+            _batch_norm_check(input, self.running_mean, self.running_var, self.weight, self.bias, True)
+            self.num_batches_tracked.add_(1)
+            self._batches += 1
+            if self.momentum is None:
+                factor = 1.0 / self._batches
+        return batch_norm(input, self.running_mean, self.running_var, self.weight, self.bias, self.training, factor, self.eps,
+                          self.relu)
+
+    def extra_repr(self):
+        return "{num_features}, eps={eps}, momentum={momentum}, relu={relu}".format(**self.__dict__)
