@@ -181,6 +181,45 @@ TDRN_API int tdrn_batch_norm_backward(const float *input, const float *grad_outp
                                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-e) MaxPool2d and L2Norm, forward and backward -- what nn.MaxPool2d, layers/modules/l2norm.py and autograd give the reference's
+ *     training loop (the five pools of vgg(), model/networks.py:136-163, and the two L2Norm layers of the source maps).
+ *   All tensors fp32, contiguous NCHW, device, on any 4-byte boundary (the code tensor on any byte), fewer than 2^31 elements.
+ *   MaxPool2d.  Geometries: kernel 2 / stride 2 / pad 0 with ceil_mode 0 or 1, and kernel 3 / stride 1 / pad 1.  Output size per axis:
+ *            floor or ceil of (in + 2 pad - kernel) / stride, plus 1; in ceil mode the last window must start inside the input
+ *            (torch's rule).  tdrn_max_pool_output_size returns it, 0 for another geometry or when no window fits.
+ *   forward: a window's in-bounds elements are scanned row-major; a value replaces the running maximum when it is strictly greater or
+ *            is NaN (torch's rule: the first of equal maxima wins, a NaN wins, the last NaN is the selected element).  output
+ *            (N, C, Ho, Wo) is OVERWRITTEN; code (N, C, Ho, Wo) uint8, or NULL for an inference-only forward, gets the selected
+ *            element's slot dy * kernel + dx in the unclipped window.
+ *   backward: grad_input (N, C, H, W) is OVERWRITTEN, every element exactly once, from grad_output and code alone (the input is not
+ *            read): the sum, in window row-major order and starting from +0.0, of grad_output over the windows whose code names the
+ *            element.  An element of no window, or selected by none, gets +0.0.
+ *   L2Norm.   output = weight[c] input / norm with norm[n, h, w] = sqrt(sum_c input^2) + eps (eps outside the root, the reference's
+ *            module), OVERWRITTEN; norm (N, H, W), or NULL, is all the backward needs besides the input.
+ *   backward: with r = norm - eps and s = sum_c weight go input per pixel, grad_input (NULL: not computed) is OVERWRITTEN with
+ *            weight go / norm - input s / (norm^2 r); at an all-zero pixel (r = 0) the second term is taken as 0 (the function is
+ *            weight input / eps there; torch's autograd returns NaN).  grad_weight (NULL: not computed) += scale sum_pixels go input / norm,
+ *            summed per 64-pixel tile and over the tiles in tile order.  One of the two is required.  The workspace is needed for
+ *            grad_weight only; the query returns 4 C ceil(N H W / 64) bytes, a pure function of (N, C, H W).
+ *   No float atomics: every output of the four entries is bitwise reproducible, and the same for a buffer on any 4-byte boundary.
+ *   Errors, all decided before any launch, in this order: a null required pointer, a float pointer off a 4-byte boundary, eps <= 0
+ *   or NaN -> TDRN_E_ARG; N / C / H / W <= 0 or an empty output -> TDRN_E_SHAPE (queries: 0); 2^31 or more elements or a pool
+ *   geometry outside the list -> TDRN_E_UNSUPPORTED (queries: 0); grad_weight with a workspace below the query -> TDRN_E_WORKSPACE.
+ *   No allocation and no host synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API int tdrn_max_pool_output_size(int in, int kernel, int stride, int pad, int ceil_mode);
+TDRN_API int tdrn_max_pool_forward(const float *input, float *output, unsigned char *code, int N, int C, int H, int W, int kernel,
+                                   int stride, int pad, int ceil_mode, void *stream);
+TDRN_API int tdrn_max_pool_backward(const float *grad_output, const unsigned char *code, float *grad_input, int N, int C, int H, int W,
+                                    int kernel, int stride, int pad, int ceil_mode, void *stream);
+TDRN_API size_t tdrn_l2norm_workspace_bytes(int N, int C, int H, int W);
+TDRN_API int tdrn_l2norm_forward(const float *input, const float *weight, float *output, float *norm, int N, int C, int H, int W,
+                                 float eps, void *stream);
+TDRN_API int tdrn_l2norm_backward(const float *input, const float *grad_output, const float *weight, const float *norm,
+                                  float *grad_input, float *grad_weight, int N, int C, int H, int W, float eps, float scale,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -105,6 +105,12 @@ _SIGS = {
     "tdrn_batch_norm_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t,
                                                                              C.c_void_p]),
     "tdrn_batch_norm_backward": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_max_pool_output_size": (C.c_int, [C.c_int] * 5),
+    "tdrn_max_pool_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
+    "tdrn_max_pool_backward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
+    "tdrn_l2norm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "tdrn_l2norm_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+    "tdrn_l2norm_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tdrn_nms_workspace_bytes": (C.c_size_t, [C.c_int]),
     "tdrn_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_size_t, C.c_void_p]),

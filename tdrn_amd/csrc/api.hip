@@ -1,4 +1,4 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d) and (ii) (section (iii) is in net.hip).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e) and (ii) (section (iii) is in net.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -165,6 +165,44 @@ int batch_norm_plan(int N, int C, int H, int W, size_t &bytes)
 }
 
 bool off_dword(const void *p) { return ((uintptr_t)p & 3) != 0; }
+
+// MaxPool2d (section i-e).  The output size of any well-formed window (torch's rule: in ceil mode the last window starts inside the
+// input or its left padding); 0 when nothing fits
+int pool_out(int in, int k, int s, int p, int ceil_mode)
+{
+    if (in <= 0 || k <= 0 || s <= 0 || p < 0) return 0;
+    const long long num = (long long)in + 2ll * p - k;
+    if (num < 0) return ceil_mode && num + s - 1 >= 0 && in + p > 0 ? 1 : 0;
+    long long o = (ceil_mode ? (num + s - 1) / s : num / s) + 1;
+    if (ceil_mode && (o - 1) * s >= (long long)in + p) --o;
+    return (int)o;
+}
+
+bool pool_geometry_supported(int k, int s, int p) { return (k == 2 && s == 2 && p == 0) || (k == 3 && s == 1 && p == 1); }
+
+// the checks both pool entries share, after their pointers
+int max_pool_plan(int N, int C, int H, int W, int k, int s, int p, int ceil_mode, int &Ho, int &Wo)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
+    const bool formed = k > 0 && s > 0 && p >= 0;
+    Ho = pool_out(H, k, s, p, ceil_mode);
+    Wo = pool_out(W, k, s, p, ceil_mode);
+    if (formed && (Ho == 0 || Wo == 0)) return TDRN_E_SHAPE;
+    if (!pool_geometry_supported(k, s, p)) return TDRN_E_UNSUPPORTED;
+    if ((long long)N * C * H * W >= (1ll << 31) || (long long)N * C >= (1ll << 31) || (long long)H * W >= (1ll << 31))
+        return TDRN_E_UNSUPPORTED;
+    return TDRN_OK;
+}
+
+// L2Norm (section i-e): the geometry checks of the query and of both entries
+int l2norm_plan(int N, int C, int H, int W, size_t &bytes)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
+    const long long HW = (long long)H * W, NC = (long long)N * C;
+    if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    bytes = l2norm_workspace_bytes(N, C, H * W);
+    return TDRN_OK;
+}
 
 }  // namespace
 
@@ -375,6 +413,61 @@ int tdrn_batch_norm_backward(const float *input, const float *grad_output, const
     if (!workspace || workspace_bytes < bytes) return TDRN_E_WORKSPACE;
     return launch_batch_norm_backward(input, grad_output, weight, bias, save_mean, save_invstd, grad_input, grad_weight, grad_bias, N, C,
                                       H * W, training != 0, relu != 0, scale, workspace, (hipStream_t)stream);
+}
+
+int tdrn_max_pool_output_size(int in, int kernel, int stride, int pad, int ceil_mode)
+{
+    return pool_geometry_supported(kernel, stride, pad) ? pool_out(in, kernel, stride, pad, ceil_mode) : 0;
+}
+
+int tdrn_max_pool_forward(const float *input, float *output, unsigned char *code, int N, int C, int H, int W, int kernel, int stride, int pad,
+                          int ceil_mode, void *stream)
+{
+    if (!input || !output || off_dword(input) || off_dword(output)) return TDRN_E_ARG;
+    int Ho, Wo;
+    TDRN_TRY(max_pool_plan(N, C, H, W, kernel, stride, pad, ceil_mode, Ho, Wo));
+    return launch_max_pool_forward(input, output, code, N * C, H, W, Ho, Wo, kernel, (hipStream_t)stream);
+}
+
+int tdrn_max_pool_backward(const float *grad_output, const unsigned char *code, float *grad_input, int N, int C, int H, int W, int kernel,
+                           int stride, int pad, int ceil_mode, void *stream)
+{
+    if (!grad_output || !code || !grad_input || off_dword(grad_output) || off_dword(grad_input)) return TDRN_E_ARG;
+    int Ho, Wo;
+    TDRN_TRY(max_pool_plan(N, C, H, W, kernel, stride, pad, ceil_mode, Ho, Wo));
+    return launch_max_pool_backward(grad_output, code, grad_input, N * C, H, W, Ho, Wo, kernel, (hipStream_t)stream);
+}
+
+size_t tdrn_l2norm_workspace_bytes(int N, int C, int H, int W)
+{
+    size_t bytes;
+    return l2norm_plan(N, C, H, W, bytes) == TDRN_OK ? bytes : 0;
+}
+
+int tdrn_l2norm_forward(const float *input, const float *weight, float *output, float *norm, int N, int C, int H, int W, float eps,
+                        void *stream)
+{
+    if (!input || !weight || !output || !(eps > 0.f)) return TDRN_E_ARG;
+    if (off_dword(input) || off_dword(weight) || off_dword(output) || off_dword(norm)) return TDRN_E_ARG;
+    size_t bytes;
+    TDRN_TRY(l2norm_plan(N, C, H, W, bytes));
+    return launch_l2norm_forward(input, weight, output, norm, N, C, H * W, eps, (hipStream_t)stream);
+}
+
+int tdrn_l2norm_backward(const float *input, const float *grad_output, const float *weight, const float *norm, float *grad_input,
+                         float *grad_weight, int N, int C, int H, int W, float eps, float scale, void *workspace, size_t workspace_bytes,
+                         void *stream)
+{
+    if (!input || !grad_output || !weight || !norm || (!grad_input && !grad_weight) || !(eps > 0.f)) return TDRN_E_ARG;
+    if (off_dword(input) || off_dword(grad_output) || off_dword(weight) || off_dword(norm) || off_dword(grad_input) || off_dword(grad_weight) ||
+        off_dword(workspace))
+        return TDRN_E_ARG;
+    size_t bytes;
+    TDRN_TRY(l2norm_plan(N, C, H, W, bytes));
+    // the workspace holds grad_weight's partial sums and nothing else
+    if (grad_weight && (!workspace || workspace_bytes < bytes)) return TDRN_E_WORKSPACE;
+    return launch_l2norm_backward(input, grad_output, weight, norm, grad_input, grad_weight, N, C, H * W, eps, scale, workspace,
+                                  (hipStream_t)stream);
 }
 
 size_t tdrn_nms_workspace_bytes(int n) { return nms_workspace_bytes(n); }

@@ -271,6 +271,20 @@ int launch_batch_norm_forward(const float *input, const float *weight, const flo
 int launch_batch_norm_backward(const float *input, const float *grad_output, const float *weight, const float *bias, const float *save_mean,
                                const float *save_invstd, float *grad_input, float *grad_weight, float *grad_bias, int N, int C, int HW,
                                int training, int relu, float scale, void *ws, hipStream_t s);
+// Trainable MaxPool2d and L2Norm, fp32 NCHW (pool_l2norm.hip; tdrn_hip.h section i-e).  kernel = 2: 2x2 / 2 / 0 with a floor or ceil
+// Ho x Wo; kernel = 3: 3x3 / 1 / 1 (Ho x Wo = H x W).  code (or null) gets one byte per output element, the selected slot dy * k + dx
+int launch_max_pool_forward(const float *input, float *output, unsigned char *code, int planes, int H, int W, int Ho, int Wo, int kernel,
+                            hipStream_t s);
+// grad_input is written exactly once per element from grad_output and the codes; the input is not read
+int launch_max_pool_backward(const float *grad_output, const unsigned char *code, float *grad_input, int planes, int H, int W, int Ho, int Wo,
+                             int kernel, hipStream_t s);
+// the [ceil(N HW / 64)][C] fp32 partial sums of grad_weight
+size_t l2norm_workspace_bytes(int N, int C, int HW);
+// norm (or null) = sqrt(sum_c x^2) + eps per pixel
+int launch_l2norm_forward(const float *input, const float *weight, float *output, float *norm, int N, int C, int HW, float eps, hipStream_t s);
+// grad_input (or null) is overwritten; grad_weight (or null; needs ws) += scale * its sum, merged in tile order
+int launch_l2norm_backward(const float *input, const float *grad_output, const float *weight, const float *norm, float *grad_input,
+                           float *grad_weight, int N, int C, int HW, float eps, float scale, void *ws, hipStream_t s);
 // transform-then-sample path of the 16-bit one-group heads (deform.hip): the caller computes Y = 1x1 GEMM of the input with the
 // per-tap weight slabs ([taps][80 columns] per pixel, deform_sample_cols(taps) channels), this launch blends the corners
 int deform_sample_supported(const DeformArgs &a);      // 0 = no, else the number of taps of all branches

@@ -2,7 +2,8 @@
 conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615,
 ConvOffset2dFunction :617-697, ConvOffset2d :699-733), plus the trainable dense conv (Conv2dFunction / conv2d / Conv2d: what
 nn.Conv2d and autograd give the reference's training loop) and the trainable batch norm with a fused ReLU (BatchNormFunction /
-batch_norm / BatchNorm2d).  The modules only own parameters with the reference's names and
+batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d) and L2Norm (L2NormFunction / l2norm / L2Norm).
+The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import ctypes as C
 import math
@@ -447,3 +448,192 @@ class BatchNorm2d(nn.Module):
 
     def extra_repr(self):
         return "{num_features}, eps={eps}, momentum={momentum}, relu={relu}".format(**self.__dict__)
+
+
+_POOL_GEOMETRIES = "kernel_size 2, stride 2, padding 0 (ceil_mode False or True) and kernel_size 3, stride 1, padding 1"
+
+
+def _square(v, name):
+    a, b = _pair(v)
+    if a != b:
+        raise NotImplementedError("max_pool2d: %s %r is not square; libtdrn_hip covers %s" % (name, v, _POOL_GEOMETRIES))
+    return int(a)
+
+
+def _max_pool_check(input, kernel_size, stride, padding, ceil_mode):
+    """-> (kernel, stride, pad, ceil, Ho, Wo) of a call the library covers"""
+    if input.dim() != 4:
+        raise ValueError("expected 4D input (got {}D input)".format(input.dim()))
+    if input.dtype != torch.float32:
+        raise ValueError("max_pool2d: input must be float32 (got %s)" % input.dtype)
+    _lib.require_cuda(input, "input")
+    k = _square(kernel_size, "kernel_size")
+    geo = (k, k if stride is None else _square(stride, "stride"), _square(padding, "padding"), int(bool(ceil_mode)))
+    lib = _lib.lib()
+    Ho, Wo = (lib.tdrn_max_pool_output_size(int(n), *geo) for n in input.shape[2:])
+    if geo[:3] not in ((2, 2, 0), (3, 1, 1)):
+        raise NotImplementedError("max_pool2d: kernel_size %d, stride %d, padding %d is not covered; libtdrn_hip covers %s"
+                                  % (geo[0], geo[1], geo[2], _POOL_GEOMETRIES))
+    if Ho == 0 or Wo == 0 or input.numel() == 0:
+        raise RuntimeError("max_pool2d: input %r gives an empty output" % (tuple(input.shape),))
+    return geo + (Ho, Wo)
+
+
+def _max_pool_forward(x, conf, with_code):
+    k, s, p, ceil, Ho, Wo = conf
+    N, Ch, H, W = x.shape
+    out = torch.empty((N, Ch, Ho, Wo), dtype=torch.float32, device=x.device)
+    code = torch.empty((N, Ch, Ho, Wo), dtype=torch.uint8, device=x.device) if with_code else None
+    _lib.check(_lib.lib().tdrn_max_pool_forward(_lib.ptr(x), _lib.ptr(out), _lib.ptr(code), N, Ch, H, W, k, s, p, ceil,
+                                                _lib.current_stream(x.device)), "tdrn_max_pool_forward")
+    return out, code
+
+
+class MaxPool2dFunction(torch.autograd.Function):
+    """MaxPool2d with a gradient: forward through tdrn_max_pool_forward, backward through tdrn_max_pool_backward.  Saves one uint8
+    code per output element (the selected slot of the window), not the input and no int64 indices.
+
+        y = MaxPool2dFunction.apply(input, kernel_size, stride, padding, ceil_mode)
+    """
+
+    @staticmethod
+    def forward(ctx, input, kernel_size, stride=None, padding=0, ceil_mode=False):
+        conf = _max_pool_check(input, kernel_size, stride, padding, ceil_mode)
+        x = input.contiguous()
+        out, code = _max_pool_forward(x, conf, True)
+        ctx.conf, ctx.in_shape = conf, tuple(x.shape)
+        ctx.save_for_backward(code)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        code, = ctx.saved_tensors
+        if not grad_output.is_cuda:
+            raise NotImplementedError("max_pool2d backward: grad_output must be a CUDA tensor")
+        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
+        if go.shape != code.shape:
+            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(code.shape)))
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            k, s, p, ceil, _, _ = ctx.conf
+            grad_input = torch.empty(ctx.in_shape, dtype=torch.float32, device=go.device)
+            _lib.check(_lib.lib().tdrn_max_pool_backward(_lib.ptr(go), _lib.ptr(code), _lib.ptr(grad_input), *ctx.in_shape, k, s, p, ceil,
+                                                         _lib.current_stream(go.device)), "tdrn_max_pool_backward")
+        return grad_input, None, None, None, None
+
+
+def max_pool2d(input, kernel_size, stride=None, padding=0, ceil_mode=False):
+    """F.max_pool2d for NCHW fp32 CUDA tensors on libtdrn_hip, differentiable in input, for the geometries of vgg(): 2 / 2 / 0 with
+    either ceil_mode, and 3 / 1 / 1.  With grad mode off, or an input that does not require grad, only the forward runs, no code
+    tensor is made and the output has no grad_fn."""
+    conf = _max_pool_check(input, kernel_size, stride, padding, ceil_mode)
+    if torch.is_grad_enabled() and input.requires_grad:
+        return MaxPool2dFunction.apply(input, kernel_size, stride, padding, ceil_mode)
+    return _max_pool_forward(input.detach().contiguous(), conf, False)[0]
+
+
+class MaxPool2d(nn.Module):
+    """nn.MaxPool2d's constructor arguments (without dilation and return_indices) on max_pool2d above; no state."""
+
+    def __init__(self, kernel_size, stride=None, padding=0, ceil_mode=False):
+        super(MaxPool2d, self).__init__()
+        self.kernel_size, self.stride, self.padding, self.ceil_mode = kernel_size, kernel_size if stride is None else stride, padding, ceil_mode
+
+    def forward(self, input):
+        return max_pool2d(input, self.kernel_size, self.stride, self.padding, self.ceil_mode)
+
+    def extra_repr(self):
+        return "kernel_size={kernel_size}, stride={stride}, padding={padding}, ceil_mode={ceil_mode}".format(**self.__dict__)
+
+
+def _l2norm_check(input, weight, eps):
+    if input.dim() != 4:
+        raise ValueError("expected 4D input (got {}D input)".format(input.dim()))
+    if input.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise ValueError("l2norm: input and weight must be float32 (got %s, %s)" % (input.dtype, weight.dtype))
+    _lib.require_cuda(input, "input")
+    _lib.require_cuda(weight, "weight")         # a module left on the CPU must not reach the library as host pointers
+    if tuple(weight.shape) != (input.shape[1],):
+        raise RuntimeError("l2norm: weight has shape %r, expected (%d,)" % (tuple(weight.shape), input.shape[1]))
+    if not eps > 0:
+        raise ValueError("l2norm: eps must be positive")
+    if input.numel() == 0 or input.numel() >= 2 ** 31:
+        raise RuntimeError("l2norm: shape outside what libtdrn_hip covers (positive sizes, fewer than 2^31 elements): %r"
+                           % (tuple(input.shape),))
+
+
+def _l2norm_forward(x, w, eps, with_norm):
+    N, Ch, H, W = x.shape
+    out = torch.empty_like(x)
+    norm = torch.empty((N, H, W), dtype=torch.float32, device=x.device) if with_norm else None
+    _lib.check(_lib.lib().tdrn_l2norm_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(out), _lib.ptr(norm), N, Ch, H, W, float(eps),
+                                              _lib.current_stream(x.device)), "tdrn_l2norm_forward")
+    return out, norm
+
+
+class L2NormFunction(torch.autograd.Function):
+    """weight x / (sqrt(sum_c x^2) + eps) with gradients: forward through tdrn_l2norm_forward, backward through tdrn_l2norm_backward
+    (scale 1 into a zeroed grad_weight; only what needs_input_grad asks for is computed).  Saves the input, the weight and the
+    per-pixel norm.  At an all-zero pixel the input gradient is weight grad_output / eps, where torch's autograd gives NaN.
+
+        y = L2NormFunction.apply(input, weight, eps)
+    """
+
+    @staticmethod
+    def forward(ctx, input, weight, eps=1e-10):
+        _l2norm_check(input, weight, eps)
+        x, w = input.contiguous(), weight.contiguous()
+        out, norm = _l2norm_forward(x, w, eps, True)
+        ctx.eps = float(eps)
+        ctx.save_for_backward(x, w, norm)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, w, norm = ctx.saved_tensors
+        if not grad_output.is_cuda:
+            raise NotImplementedError("l2norm backward: grad_output must be a CUDA tensor")
+        go = grad_output.float().contiguous()
+        if go.shape != x.shape:
+            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(x.shape)))
+        need_in, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        grad_input = gw = None
+        if need_in or need_w:
+            lib = _lib.lib()
+            dims = tuple(x.shape)
+            ws, nb = None, 0
+            if need_in:
+                grad_input = torch.empty_like(x)
+            if need_w:
+                gw = torch.zeros_like(w)
+                nb = lib.tdrn_l2norm_workspace_bytes(*dims)
+                ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+            _lib.check(lib.tdrn_l2norm_backward(_lib.ptr(x), _lib.ptr(go), _lib.ptr(w), _lib.ptr(norm), _lib.ptr(grad_input), _lib.ptr(gw),
+                                                *dims, ctx.eps, 1.0, _lib.ptr(ws), nb, _lib.current_stream(x.device)),
+                       "tdrn_l2norm_backward")
+        return grad_input, gw, None
+
+
+def l2norm(input, weight, eps=1e-10):
+    """The reference's L2Norm (layers/modules/l2norm.py) for NCHW fp32 CUDA tensors on libtdrn_hip, differentiable in input and
+    weight.  With grad mode off, or when nothing requires grad, only the forward runs, no norm tensor is made and the output has
+    no grad_fn."""
+    _l2norm_check(input, weight, eps)
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad):
+        return L2NormFunction.apply(input, weight, eps)
+    return _l2norm_forward(input.detach().contiguous(), weight.detach().contiguous(), eps, False)[0]
+
+
+class L2Norm(nn.Module):
+    """The reference module's single `weight` key and init (layers/modules/l2norm.py: every channel starts at `scale`) on l2norm
+    above."""
+
+    def __init__(self, n_channels, scale):
+        super(L2Norm, self).__init__()
+        self.n_channels, self.gamma, self.eps = n_channels, scale or None, 1e-10
+        self.weight = nn.Parameter(torch.full((n_channels,), float(scale)))
+
+    def forward(self, x):
+        return l2norm(x, self.weight, self.eps)
