@@ -247,7 +247,7 @@ int tdrn_deform_conv_forward(const float *input, const float *weight, const floa
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
     const int G = deformable_group, es = dtype_bytes(compute);
-    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
     TDRN_TRY(launch_nchw_to_nhwc_grouped(input, ws + p.o_in, N, Cin, H * W, G, p.cpg_pad, compute, s));
     TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.Npad_total, Cin, p.taps, G, p.cpg_pad, compute, s));
     const int offC = G * 2 * p.taps;
@@ -291,7 +291,7 @@ int tdrn_deform_conv_backward_input(const float *input, const float *offset, con
     float *in_nhwc = (float *)(ws + b.o_in), *gin = (float *)(ws + b.o_gin), *wr = (float *)(ws + b.o_w);
     TDRN_TRY(launch_nchw_to_nhwc_grouped(input, in_nhwc, N, Cin, H * W, G, cpg64, TDRN_F32, s));
     TDRN_TRY(launch_repack_oihw(weight, wr, Cout, Cout, Cin, taps, G, cpg64, TDRN_F32, s));
-    TDRN_HIP_TRY(hipMemsetAsync(gin, 0, (size_t)N * H * W * cpg64 * G * 4, s));
+    TDRN_TRY(launch_fill_zero(gin, (size_t)N * H * W * cpg64 * G * 4, s));
     TDRN_TRY(launch_deform_bwd_data(b.g, in_nhwc, offset, grad_output, wr, gin, grad_offset, s));
     return launch_deform_bwd_input_add(b.g, gin, grad_input, s);
 }
@@ -332,10 +332,10 @@ int tdrn_conv2d_forward(const float *input, const float *weight, const float *bi
     if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
     TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
     TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.NpadF, Cin, p.taps, 1, p.CiPad, compute, s));
-    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_bias, 0, (size_t)p.NpadF * 4, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadF * 4, s));
     if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
     return conv2d_run(p, ws, false, compute, output, s);
 }
@@ -350,10 +350,10 @@ int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, fl
     if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
     TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
     TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.NpadD, p.taps, compute, s));
-    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_bias, 0, (size_t)p.NpadD * 4, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadD * 4, s));
     // a stride-1 conv over grad_output: kernel rotated and transposed (the packing above), pad' = dil (k - 1) - pad, same dilation
     return conv2d_run(p, ws, true, compute, grad_input, s);
 }
@@ -368,7 +368,7 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
     if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_HIP_TRY(hipMemsetAsync(ws + p.o_zero, 0, kZeroPageBytes, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
     TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
     TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
     return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);

@@ -195,7 +195,7 @@ int launch_preprocess(const unsigned char *in, int B, int H0, int W0, int S, con
                       hipStream_t s);
 int launch_preprocess_u8(const unsigned char *in, int B, int H0, int W0, int S, int to_rgb, unsigned char *out, hipStream_t s);   // resized uint8 planes
 int launch_u8_planes_to_f32(const unsigned char *in, int B, int S, const float *mean, float *out, hipStream_t s);                // (B,3,S,S) u8 -> fp32 - mean[c]
-int launch_fill_zero(void *p, size_t bytes, hipStream_t s);
+int launch_fill_zero(void *p, size_t bytes, hipStream_t s);       // a kernel, not a memset node: keeps its place in a replayed hipGraph
 
 // ---------------------------------------------------------------------------------------------
 // Deformable-conv GEMM (deform.hip): up to two branches (3x3 + 5x5) sharing the input and summed.

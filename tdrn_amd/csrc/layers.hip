@@ -1065,9 +1065,26 @@ int launch_u8_planes_to_f32(const unsigned char *in, int B, int S, const float *
     return hip_status(hipGetLastError());
 }
 
+// Zeroes `bytes` bytes at p (both multiples of 4) with a kernel; 16-byte stores where p and bytes allow.  The capturable entries
+// (tdrn_hip.h sections i, i-b, i-c) zero through this and not through hipMemsetAsync: captured into a hipGraph, a memset node
+// took effect on the first launch of the graph only -- from the second replay on, the kernels behind it read what the kernels in
+// front of it had left in the zero page (tests/test_gpu_train_graph.py).  A kernel node keeps its place.
+template <typename V>
+__global__ __launch_bounds__(256) void fill_zero_kernel(V *__restrict__ p, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = V{};
+}
+
 int launch_fill_zero(void *p, size_t bytes, hipStream_t s)
 {
-    return hip_status(hipMemsetAsync(p, 0, bytes, s));
+    if (bytes == 0) return TDRN_OK;
+    if (!p || (((uintptr_t)p | bytes) & 3)) return TDRN_E_ARG;
+    const bool vec = (((uintptr_t)p | bytes) & 15) == 0;
+    const size_t n = vec ? bytes / 16 : bytes / 4;
+    dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256));
+    if (vec) hipLaunchKernelGGL((fill_zero_kernel<uint4>), grid, dim3(256), 0, s, (uint4 *)p, n);
+    else hipLaunchKernelGGL((fill_zero_kernel<unsigned>), grid, dim3(256), 0, s, (unsigned *)p, n);
+    return hip_status(hipGetLastError());
 }
 
 int allow_big_lds(const void *kernel)
