@@ -220,6 +220,45 @@ TDRN_API int tdrn_l2norm_backward(const float *input, const float *grad_output, 
                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-f) ConvTranspose2d with kernel 2, stride 2 and gradients -- what nn.ConvTranspose2d(256, 256, 2, 2, 0) + autograd give the
+ *     reference's training loop (the up_layers of add_refine_head: the TCB pyramid of dualrefinedet_vggbn, dualrefinedet_mobilenet
+ *     and refinedet_vgg): forward, input gradient, weight / bias gradient.
+ *   input (N, Cin, H, W), weight (Cin, Cout, 2, 2) (torch's layout), bias (Cout) or NULL, output / grad_output (N, Cout, 2H, 2W),
+ *   grad_input like input, grad_weight like weight, grad_bias (Cout) or NULL: all fp32, contiguous, device, on any 4-byte boundary.
+ *   `compute` as in (i-c): TDRN_BF16 / TDRN_F16 round input, weight and grad_output ONCE, to nearest even (bias is not rounded);
+ *   accumulation and every output are fp32.  With kernel 2 at stride 2 every output pixel has exactly one tap:
+ *   forward:             output[n][co][2h+i][2w+j] = bias[co] + sum_ci input[n][ci][h][w] weight[ci][co][i][j], OVERWRITTEN.
+ *   backward_input:      grad_input[n][ci][h][w] = sum_{i,j,co} grad_output[n][co][2h+i][2w+j] weight[ci][co][i][j], OVERWRITTEN.
+ *   backward_parameters: grad_weight[ci][co][i][j] += scale * sum_{n,h,w} input[n][ci][h][w] grad_output[n][co][2h+i][2w+j],
+ *                        grad_bias[co] += scale * sum grad_output[.][co][.][.]; split over K = N*H*W and summed in a fixed order.
+ *   All outputs are bitwise reproducible run to run, and the same for caller buffers on any 4-byte boundary: nothing on this path
+ *   uses float atomics, and the split counts depend on the geometry alone.
+ *   Geometry (the argument order is the query's in all four functions): kH = kW = 2, dH = dW = 2, pad 0, output_padding 0,
+ *   dilation 1; any N, Cin, Cout, H, W >= 1 with N*H*W*Cin_pad, N*H*W*4*Cout_pad and N*4*H*W*Cout below 2^31 (channels padded
+ *   to 64).
+ *   Errors, all decided before any launch: a null tensor pointer -> TDRN_E_ARG (first); k <= 0, stride / dilation <= 0, a negative
+ *   pad or output_padding, N / Cin / Cout / H / W <= 0 -> query 0 and TDRN_E_SHAPE; any other well-formed geometry -> query 0 and
+ *   TDRN_E_UNSUPPORTED; a null workspace or one below the query -> TDRN_E_WORKSPACE.  One query serves all three entries.  No
+ *   allocation and no host synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_conv_transpose2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW,
+                                                      int padH, int padW, int output_padH, int output_padW, int dilationH,
+                                                      int dilationW, tdrn_dtype compute);
+TDRN_API int tdrn_conv_transpose2d_forward(const float *input, const float *weight, const float *bias, float *output, int N,
+                                           int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                           int output_padH, int output_padW, int dilationH, int dilationW, tdrn_dtype compute,
+                                           void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv_transpose2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N,
+                                                  int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH,
+                                                  int padW, int output_padH, int output_padW, int dilationH, int dilationW,
+                                                  tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv_transpose2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight,
+                                                       float *grad_bias, int N, int Cin, int H, int W, int Cout, int kH, int kW,
+                                                       int dH, int dW, int padH, int padW, int output_padH, int output_padW,
+                                                       int dilationH, int dilationW, float scale, tdrn_dtype compute,
+                                                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

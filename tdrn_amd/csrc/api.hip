@@ -1,4 +1,4 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e) and (ii) (section (iii) is in net.hip).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f) and (ii) (section (iii) is in net.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -151,6 +151,84 @@ int conv2d_run(const Conv2dPlan &p, char *ws, bool dgrad, int dtype, float *out,
     if (a.splitk > 1) a.partial = ws + p.o_partial;
     TDRN_TRY(launch_conv(a, s));
     return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.o_cs, out, p.g.N, a.Cout, a.Ho * a.Wo, s);
+}
+
+// ConvTranspose2d(k = 2, s = 2) with gradients (section i-f).  Workspace, in conv2d_plan's shape: zero page | input NHWC | the
+// space-to-depth image of grad_output | the rest, which is either {packed weight (the larger packing), padded bias, NHWC fp32 result
+// (the larger of output and grad_input), split-K partials of launch_conv} or the wgrad slabs.
+struct ConvT2dPlan {
+    int N, Cin, H, W, Cout, CiPad, CoPad, C4, NpadF, NpadD;
+    ConvBwdGeom wg;         // the one-tap weight-gradient GEMM over the space-to-depth image: 4 CoPad "output channels"
+    size_t o_zero, o_x, o_go, o_w, o_bias, o_out, o_partial, o_slab, total;
+};
+
+// the launch_conv arguments, without their pointers, of the forward (four phase GEMMs, each a 1x1 conv that writes every second
+// pixel of every second row) or of the input gradient (one 1x1 conv over the space-to-depth image): fp32 NHWC result, no ReLU
+ConvArgs convt2d_args(const ConvT2dPlan &p, bool dgrad, int dtype)
+{
+    ConvArgs a;
+    a.B = p.N; a.H = a.Ho = p.H; a.W = a.Wo = p.W;
+    a.kh = a.kw = 1; a.stride = 1; a.pad = 0; a.dil = 1;
+    a.relu = 0; a.out_f32 = 1;
+    if (!dgrad) {
+        a.Cin = p.CiPad; a.Cout = p.Cout; a.Npad = p.NpadF; a.phases = 4;
+        a.o_cs = 2ll * p.Cout; a.o_rs = 4ll * p.W * p.Cout; a.o_bs = 4ll * p.H * p.W * p.Cout;
+        a.o_pr = 2ll * p.W * p.Cout; a.o_pc = p.Cout;
+    } else {
+        a.Cin = p.C4; a.Cout = p.Cin; a.Npad = p.NpadD;
+        a.o_cs = p.Cin; a.o_rs = (long long)p.W * p.Cin; a.o_bs = (long long)p.H * p.W * p.Cin;
+    }
+    a.dtype = dtype;
+    a.kdisable = KOFF_HEAD3X3;             // (conv2d_args: every shape on conv_igemm.hip)
+    a.splitk = conv_splitk_choice(a);      // the 5 x 5 and 10 x 10 levels fill the chip by K slices, as in the engine
+    return a;
+}
+
+int convt2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int opadH, int opadW, int dilH,
+                 int dilW, int dtype, ConvT2dPlan &p)
+{
+    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0 || opadH < 0 || opadW < 0) return TDRN_E_SHAPE;
+    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    // what the kernels cover: the four taps of a 2x2 kernel at stride 2 write four disjoint phases of the output
+    if (kH != 2 || kW != 2 || dH != 2 || dW != 2 || padH || padW || opadH || opadW || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
+    const long long CiPad = ((long long)Cin + kChanPad - 1) / kChanPad * kChanPad, CoPad = ((long long)Cout + kChanPad - 1) / kChanPad * kChanPad;
+    // 32-bit offsets of the kernels (conv_igemm.hip: elements of its input; conv_bwd.hip: pixels; the NCHW <-> NHWC conversions)
+    if ((long long)H * W >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    const long long px = (long long)N * ((long long)H * W);
+    if (px >= (1ll << 31) || px * CiPad >= (1ll << 31) || px * 4 * CoPad >= (1ll << 31) || px * 4 * Cout >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
+    p.CiPad = (int)CiPad; p.CoPad = (int)CoPad; p.C4 = 4 * p.CoPad;
+    p.NpadF = conv_n_pad(Cout); p.NpadD = conv_n_pad(Cin);
+    p.wg = ConvBwdGeom{N, Cin, H, W, p.C4, 1, 0, 1, H, W};
+    const int es = dtype_bytes(dtype);
+    const size_t wf = (size_t)4 * p.NpadF * p.CiPad * es, wd = (size_t)p.NpadD * p.C4 * es;
+    const size_t of = (size_t)px * 4 * Cout * 4, od = (size_t)px * Cin * 4;
+    size_t o = 0;
+    p.o_zero = o; o += kZeroPageBytes;
+    p.o_x = o;    o += align_up((size_t)px * p.CiPad * es, 256);
+    p.o_go = o;   o += align_up((size_t)px * p.C4 * es, 256);
+    p.o_slab = o;
+    const size_t slab_end = o + conv_wgrad_slab_bytes(p.wg);
+    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
+    p.o_bias = o; o += align_up((size_t)(p.NpadF > p.NpadD ? p.NpadF : p.NpadD) * 4, 256);
+    p.o_out = o;  o += align_up(of > od ? of : od, 256);
+    const ConvArgs af = convt2d_args(p, false, dtype), ad = convt2d_args(p, true, dtype);
+    const size_t pf = conv_splitk_bytes(af, af.splitk), pd = conv_splitk_bytes(ad, ad.splitk);
+    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
+    p.total = o > slab_end ? o : slab_end;
+    return TDRN_OK;
+}
+
+// launch_conv with an fp32 NHWC result in the workspace ([N][2H][2W][Cout] or [N][H][W][Cin]), then NCHW into `out`
+int convt2d_run(const ConvT2dPlan &p, char *ws, bool dgrad, int dtype, float *out, hipStream_t s)
+{
+    ConvArgs a = convt2d_args(p, dgrad, dtype);
+    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
+    a.out = ws + p.o_out;
+    if (a.splitk > 1) a.partial = ws + p.o_partial;
+    TDRN_TRY(launch_conv(a, s));
+    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.Cout, out, p.N, a.Cout, (dgrad ? 1 : 4) * p.H * p.W, s);
 }
 
 // BatchNorm2d (section i-d): the geometry checks of the query and of both entries
@@ -372,6 +450,72 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
     TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
     TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
     return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+}
+
+size_t tdrn_conv_transpose2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                             int output_padH, int output_padW, int dilationH, int dilationW, tdrn_dtype compute)
+{
+    ConvT2dPlan p;
+    if (convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p) != TDRN_OK)
+        return 0;
+    return p.total;
+}
+
+int tdrn_conv_transpose2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W,
+                                  int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int output_padH, int output_padW,
+                                  int dilationH, int dilationW, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !output) return TDRN_E_ARG;
+    ConvT2dPlan p;
+    TDRN_TRY(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(launch_repack_iohw_phases(weight, ws + p.o_w, Cin, Cout, p.NpadF, compute, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadF * 4, s));
+    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+    return convt2d_run(p, ws, false, compute, output, s);
+}
+
+int tdrn_conv_transpose2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W,
+                                         int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int output_padH, int output_padW,
+                                         int dilationH, int dilationW, tdrn_dtype compute, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
+    ConvT2dPlan p;
+    TDRN_TRY(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc_s2d(grad_output, ws + p.o_go, N, Cout, H, W, compute, s));
+    TDRN_TRY(launch_repack_iohw_dgrad(weight, ws + p.o_w, Cin, Cout, p.NpadD, compute, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadD * 4, s));
+    // one 1x1 conv over the space-to-depth image: its 4 CoPad channels are the (tap, cout) pairs of the sum
+    return convt2d_run(p, ws, true, compute, grad_input, s);
+}
+
+int tdrn_conv_transpose2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N,
+                                              int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                              int output_padH, int output_padW, int dilationH, int dilationW, float scale,
+                                              tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
+    ConvT2dPlan p;
+    TDRN_TRY(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(launch_nchw_to_nhwc_s2d(grad_output, ws + p.o_go, N, Cout, H, W, compute, s));
+    int splits;
+    const float *bslab;
+    TDRN_TRY(launch_conv_wgrad_slabs(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, compute, s, splits, bslab));
+    return launch_convt_wgrad_reduce((const float *)(ws + p.o_slab), bslab, grad_weight, grad_bias, Cin, Cout, splits, scale, s);
 }
 
 size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W)

@@ -299,10 +299,10 @@ int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int N
     return hip_status(hipGetLastError());
 }
 
-int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, float *grad_weight,
-                      float *grad_bias, float scale, int dtype, hipStream_t s)
+int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, int dtype,
+                            hipStream_t s, int &splits, const float *&bias_slab)
 {
-    if ((g.k != 1 && g.k != 3) || !x_nhwc || !go_nhwc || !zero_page || !slab || !grad_weight) return TDRN_E_UNSUPPORTED;
+    if ((g.k != 1 && g.k != 3) || !x_nhwc || !go_nhwc || !zero_page || !slab) return TDRN_E_UNSUPPORTED;
     int S, per_split;
     conv_wgrad_splits(g, S, per_split);
     const int taps = g.k * g.k;
@@ -320,11 +320,23 @@ int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_n
         case TDRN_BF16: rc = launch_wgrad_dt<bf16_t>(p, taps, grid, s); break;
         case TDRN_F16: rc = launch_wgrad_dt<f16_t>(p, taps, grid, s); break;
     }
-    TDRN_TRY(rc);
+    splits = S;
+    bias_slab = p.bslab;
+    return rc;
+}
+
+int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, float *grad_weight,
+                      float *grad_bias, float scale, int dtype, hipStream_t s)
+{
+    if (!grad_weight) return TDRN_E_UNSUPPORTED;
+    int S;
+    const float *bslab;
+    TDRN_TRY(launch_conv_wgrad_slabs(g, x_nhwc, go_nhwc, zero_page, slab, dtype, s, S, bslab));
+    const int taps = g.k * g.k, CoPad = conv_bwd_cpad(g.Cout), CiPad = conv_bwd_cpad(g.Cin);
     const long long total = (long long)taps * g.Cout * g.Cin + (grad_bias ? g.Cout : 0);
     const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p.slab, p.bslab, grad_weight, grad_bias, g.Cout,
-                       g.Cin, taps, p.CoPad, p.CiPad, S, scale);
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float *)slab, bslab, grad_weight, grad_bias,
+                       g.Cout, g.Cin, taps, CoPad, CiPad, S, scale);
     return hip_status(hipGetLastError());
 }
 

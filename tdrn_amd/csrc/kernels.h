@@ -256,8 +256,24 @@ size_t conv_wgrad_slab_bytes(const ConvBwdGeom &g);     // the fp32 slabs [split
 // grad_weight (OIHW) += scale * sum_p go[p][co] x[p (+) tap][ci], grad_bias (or null) += scale * sum_p go[p][co]; fixed order, no atomics
 int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, float *grad_weight,
                       float *grad_bias, float scale, int dtype, hipStream_t s);
+// ... its MFMA pass alone: the per-split sums land in `slab`; `splits` and the bias part of the slab ([splits][CoutPad]) are returned
+// for the caller's own reduce (conv_transpose.hip)
+int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, int dtype,
+                            hipStream_t s, int &splits, const float *&bias_slab);
 // OIHW fp32 -> launch_conv's packing of the input-gradient conv: out[ci][taps-1-tap][co] = w[co][ci][tap] ([Npad][taps][conv_bwd_cpad(Cout)])
 int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int Npad, int taps, int dtype, hipStream_t s);
+// ConvTranspose2d(k = 2, s = 2) with gradients (conv_transpose.hip; tdrn_hip.h section i-f).  z = 2i + j names the kernel tap (i, j) = the
+// output phase; CoPad = conv_bwd_cpad(Cout).
+// grad_output fp32 NCHW (N, Cout, 2H, 2W) -> its space-to-depth image, DT NHWC [N][H][W][z * CoPad + co], padded channels zero
+int launch_nchw_to_nhwc_s2d(const float *in, void *out, int N, int Cout, int H, int W, int dtype, hipStream_t s);
+// weight (Cin, Cout, 2, 2) fp32 -> launch_conv's phases = 4 packing out[z][co][ci] ([4][Npad][conv_bwd_cpad(Cin)]) ...
+int launch_repack_iohw_phases(const float *w, void *out, int Cin, int Cout, int Npad, int dtype, hipStream_t s);
+// ... and the packing of the input gradient, a 1x1 conv over the space-to-depth image: out[ci][z * CoPad + co] ([Npad][4 CoPad])
+int launch_repack_iohw_dgrad(const float *w, void *out, int Cin, int Cout, int Npad, int dtype, hipStream_t s);
+// grad_weight (Cin, Cout, 2, 2) += scale * sum_split slab[split][z * CoPad + co][ci], grad_bias (or null) += scale * sum_split sum_z
+// bias_slab[split][z * CoPad + co]: the slabs of launch_conv_wgrad_slabs on ConvBwdGeom{N, Cin, H, W, 4 CoPad, 1, 0, 1, H, W}
+int launch_convt_wgrad_reduce(const float *slab, const float *bias_slab, float *grad_weight, float *grad_bias, int Cin, int Cout, int splits,
+                              float scale, hipStream_t s);
 // BatchNorm2d with an optional fused ReLU, fp32 NCHW (batch_norm.hip; tdrn_hip.h section i-d).  Every pass cuts a channel's N*HW values
 // into `splits` pieces of per_split elements, from (N, C, HW) alone; the workspace holds the per-(channel, split) records of the reducing
 // passes and the backward's per-channel sums: 12 C splits + 8 C bytes

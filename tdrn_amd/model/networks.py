@@ -2,7 +2,8 @@
 conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615,
 ConvOffset2dFunction :617-697, ConvOffset2d :699-733), plus the trainable dense conv (Conv2dFunction / conv2d / Conv2d: what
 nn.Conv2d and autograd give the reference's training loop) and the trainable batch norm with a fused ReLU (BatchNormFunction /
-batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d) and L2Norm (L2NormFunction / l2norm / L2Norm).
+batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d) and L2Norm (L2NormFunction / l2norm / L2Norm),
+and the trainable 2x2 stride-2 transposed conv of the TCB up_layers (ConvTranspose2dFunction / conv_transpose2d / ConvTranspose2d).
 The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import ctypes as C
@@ -304,6 +305,144 @@ class Conv2d(nn.Module):
 
     def forward(self, input):
         return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute)
+
+
+def _conv_transpose2d_geometry(x, w, stride, padding=0, output_padding=0):
+    (sh, sw), (ph, pw), (oh, ow) = _pair(stride), _pair(padding), _pair(output_padding)
+    N, Cin, H, W = x.shape
+    Cw, Cout, kh, kw = w.shape
+    if Cw != Cin:
+        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (Cw, Cin))
+    Ho = (H - 1) * sh - 2 * ph + (kh - 1) + oh + 1
+    Wo = (W - 1) * sw - 2 * pw + (kw - 1) + ow + 1
+    # the C ABI's argument order: N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW
+    return (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, oh, ow, 1, 1), (N, Cout, Ho, Wo)
+
+
+def _conv_transpose2d_workspace(lib, dims, dt, device):
+    nb = lib.tdrn_conv_transpose2d_workspace_bytes(*dims, dt)
+    if nb == 0:
+        raise RuntimeError("conv_transpose2d: geometry outside what libtdrn_hip covers (kernel 2 x 2, stride 2, padding 0, "
+                           "output_padding 0, dilation 1): N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, opadH, opadW, dilH, dilW = %r"
+                           % (dims,))
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+def _conv_transpose2d_forward(x, w, b, stride, padding, output_padding, compute):
+    lib = _lib.lib()
+    dims, out_shape = _conv_transpose2d_geometry(x, w, stride, padding, output_padding)
+    if b is not None and tuple(b.shape) != (out_shape[1],):
+        raise RuntimeError("conv_transpose2d: bias has shape %r, expected (%d,)" % (tuple(b.shape), out_shape[1]))
+    dt = _lib.DTYPES[compute]
+    ws, nb = _conv_transpose2d_workspace(lib, dims, dt, x.device)
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    _lib.check(lib.tdrn_conv_transpose2d_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
+                                                 _lib.current_stream(x.device)), "tdrn_conv_transpose2d_forward")
+    return out
+
+
+def _conv_transpose2d_check(input, weight, bias):
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    if weight.dim() != 4:
+        raise ValueError("Expected a 4D weight (in_channels, out_channels, kH, kW), got {}D.".format(weight.dim()))
+    _conv2d_require_cuda(input, weight, bias)
+
+
+class ConvTranspose2dFunction(torch.autograd.Function):
+    """ConvTranspose2d(kernel 2, stride 2) with gradients: forward through tdrn_conv_transpose2d_forward, backward through
+    tdrn_conv_transpose2d_backward_input (when the input needs a gradient) and tdrn_conv_transpose2d_backward_parameters (weight
+    and bias gradients, scale 1 into zeroed buffers).  `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the forward
+    and of both gradients.  The weight is (in_channels, out_channels, 2, 2), torch's layout.  Geometry the library rejects raises;
+    nothing falls back to torch.
+
+        y = ConvTranspose2dFunction.apply(input, weight, bias_or_None, stride[, padding, output_padding, compute])
+    """
+
+    @staticmethod
+    def forward(ctx, input, weight, bias=None, stride=2, padding=0, output_padding=0, compute="fp32"):
+        _conv_transpose2d_check(input, weight, bias)
+        x, w = input.contiguous().float(), weight.contiguous().float()
+        b = None if bias is None else bias.contiguous().float()
+        out = _conv_transpose2d_forward(x, w, b, stride, padding, output_padding, compute)
+        ctx.conf = (stride, padding, output_padding, compute, bias is not None)
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, w = ctx.saved_tensors
+        if not grad_output.is_cuda:
+            raise NotImplementedError("conv_transpose2d backward: grad_output must be a CUDA tensor")
+        stride, padding, output_padding, compute, has_bias = ctx.conf
+        lib = _lib.lib()
+        dims, out_shape = _conv_transpose2d_geometry(x, w, stride, padding, output_padding)
+        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
+        if tuple(go.shape) != out_shape:
+            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
+        need_in, need_w = ctx.needs_input_grad[:2]
+        need_b = has_bias and ctx.needs_input_grad[2]
+        grad_input = grad_weight = grad_bias = None
+        if need_in or need_w or need_b:
+            dt = _lib.DTYPES[compute]
+            ws, nb = _conv_transpose2d_workspace(lib, dims, dt, x.device)
+            stream = _lib.current_stream(x.device)
+        if need_in:
+            grad_input = torch.empty_like(x)
+            _lib.check(lib.tdrn_conv_transpose2d_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws),
+                                                                nb, stream), "tdrn_conv_transpose2d_backward_input")
+        if need_w or need_b:
+            gw = torch.zeros_like(w)
+            gb = torch.zeros(w.shape[1], dtype=torch.float32, device=x.device) if need_b else None
+            _lib.check(lib.tdrn_conv_transpose2d_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
+                                                                     _lib.ptr(ws), nb, stream),
+                       "tdrn_conv_transpose2d_backward_parameters")
+            grad_weight = gw if need_w else None
+            grad_bias = gb
+        return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
+def _conv_transpose2d(input, weight, bias, stride, padding, output_padding, compute):
+    _conv_transpose2d_check(input, weight, bias)
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return ConvTranspose2dFunction.apply(input, weight, bias, stride, padding, output_padding, compute)
+    x, w = input.contiguous().float(), weight.detach().contiguous().float()
+    b = None if bias is None else bias.detach().contiguous().float()
+    return _conv_transpose2d_forward(x, w, b, stride, padding, output_padding, compute)
+
+
+def conv_transpose2d(input, weight, bias=None, stride=2, compute="fp32"):
+    """ConvTranspose2d with a 2 x 2 kernel at stride 2 on libtdrn_hip (NCHW fp32 CUDA tensors in, (N, Cout, 2H, 2W) fp32 out; weight
+    (Cin, Cout, 2, 2)), differentiable in input, weight and bias.  With grad mode off, or when nothing requires grad, only the
+    forward runs and the output has no grad_fn."""
+    return _conv_transpose2d(input, weight, bias, stride, 0, 0, compute)
+
+
+class ConvTranspose2d(nn.Module):
+    """nn.ConvTranspose2d's parameters and default init (weight (in, out, kH, kW), bias) on conv_transpose2d above: groups 1,
+    dilation 1.  Every geometry can be constructed (a checkpoint loads); one the library does not cover raises in forward."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, padding=0, output_padding=0, bias=True, compute="fp32"):
+        super(ConvTranspose2d, self).__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride = _pair(kernel_size), _pair(stride)
+        self.padding, self.output_padding = _pair(padding), _pair(output_padding)
+        self.compute = compute
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels, *self.kernel_size))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        # nn.ConvTranspose2d's: fan_in is taken from dimension 1 of the weight, the output channels
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            fan_in = self.out_channels * self.kernel_size[0] * self.kernel_size[1]
+            bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, input):
+        return _conv_transpose2d(input, self.weight, self.bias, self.stride, self.padding, self.output_padding, self.compute)
 
 
 def _batch_norm_check(input, running_mean, running_var, weight, bias, training):
