@@ -259,6 +259,46 @@ TDRN_API int tdrn_conv_transpose2d_backward_parameters(const float *input, const
                                                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-g) Dense 3x3 conv2d at stride 2 with gradients -- what nn.Conv2d(256, 512, 3, 2, 1) + autograd give the reference's training
+ *     loop (`extras` of dualrefinedet_vggbn, ssd4scale_vgg and refinedet_vgg; nn.Conv2d(3, 32, 3, 2, 1) at the head of the MobileNet
+ *     trunk): forward, input gradient, weight / bias gradient.  A family of its own: (i-c) keeps refusing stride 2, and this one
+ *     refuses stride 1.
+ *   Tensors, `compute`, OVERWRITTEN / += scale semantics and the argument lists are (i-c)'s, with
+ *   Ho = (H + 2 pad - 3) / 2 + 1 (floor) and Wo likewise; all fp32, contiguous, device, on any 4-byte boundary.
+ *   forward:             output[n][co][ho][wo] = bias[co] + sum_{ci,i,j} input[n][ci][2ho - pad + i][2wo - pad + j] weight[co][ci][i][j].
+ *   backward_input:      grad_input is OVERWRITTEN: a stride-1 conv, kernel rotated and transposed, pad' = 2 - pad, over the
+ *                        zero-inserted image of grad_output (H + 2 pad - 2 rows, W + 2 pad - 2 columns, grad_output[ho][wo] at
+ *                        [2ho][2wo]).  An input row or column that no output pixel touches gets exactly 0.
+ *   backward_parameters: grad_weight += scale * sum_p grad_output[p] input[2p - pad (+) tap], grad_bias += scale * sum_p grad_output[p],
+ *                        split over K = N*Ho*Wo and summed in a fixed order.
+ *   All outputs are bitwise reproducible run to run, and the same for caller buffers on any 4-byte boundary: nothing on this path
+ *   uses float atomics, and the split counts depend on the geometry alone.
+ *   Geometry (the argument order is the query's in all four functions): kH = kW = 3, dH = dW = 2, dilation 1,
+ *   0 <= padH = padW <= 2, Ho, Wo >= 1, groups = 1.
+ *   Errors, all decided before any launch: a null tensor pointer -> TDRN_E_ARG (first); k <= 0, stride / dilation <= 0, negative
+ *   pad, N / Cin / Cout / H / W <= 0, an output smaller than 1 x 1 -> query 0 and TDRN_E_SHAPE; any other well-formed geometry
+ *   (stride 1, per-axis stride, other kernel sizes, dilation > 1, pad > 2, per-axis pad; N*H*W*Cin_pad, N*Ho*Wo*Cout_pad or
+ *   N*(H + 2 pad - 2)*(W + 2 pad - 2)*Cout_pad of 2^31 elements or more, channels padded to 64) -> query 0 and TDRN_E_UNSUPPORTED;
+ *   a null workspace or one below the query -> TDRN_E_WORKSPACE.  One query serves all three entries.  No allocation and no host
+ *   synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_conv2d_strided_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW,
+                                                    int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute);
+TDRN_API int tdrn_conv2d_strided_forward(const float *input, const float *weight, const float *bias, float *output, int N,
+                                         int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                         int dilationH, int dilationW, tdrn_dtype compute, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv2d_strided_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin,
+                                                int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                                int dilationH, int dilationW, tdrn_dtype compute, void *workspace,
+                                                size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv2d_strided_backward_parameters(const float *input, const float *grad_output, float *grad_weight,
+                                                     float *grad_bias, int N, int Cin, int H, int W, int Cout, int kH, int kW,
+                                                     int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                                     float scale, tdrn_dtype compute, void *workspace, size_t workspace_bytes,
+                                                     void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

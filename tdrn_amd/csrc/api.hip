@@ -1,4 +1,4 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f) and (ii) (section (iii) is in net.hip).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g) and (ii) (section (iii) is in net.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -229,6 +229,83 @@ int convt2d_run(const ConvT2dPlan &p, char *ws, bool dgrad, int dtype, float *ou
     if (a.splitk > 1) a.partial = ws + p.o_partial;
     TDRN_TRY(launch_conv(a, s));
     return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.Cout, out, p.N, a.Cout, (dgrad ? 1 : 4) * p.H * p.W, s);
+}
+
+// dense 3x3 stride-2 conv with gradients (section i-g).  Workspace, in conv2d_plan's shape: zero page | input NHWC | grad_output NHWC
+// (backward_parameters) or its zero-inserted image D (backward_input; the larger of the two) | the rest, which is either {packed
+// weight, padded bias, NHWC fp32 result, split-K partials of launch_conv} or the wgrad slabs.
+struct ConvS2Plan {
+    ConvBwdGeom g;          // stride = 2: the weight gradient's geometry
+    int CiPad, CoPad, NpadF, NpadD, Hd, Wd;
+    size_t o_zero, o_x, o_go, o_w, o_bias, o_out, o_partial, o_slab, total;
+};
+
+// the launch_conv arguments, without their pointers, of the forward (stride 2) or of the input gradient: a stride-1 conv with
+// pad' = 2 - pad over the zero-inserted image (N, CoPad, Hd, Wd) -> (Cin, H, W).  fp32 NHWC result, no ReLU
+ConvArgs convs2_args(const ConvS2Plan &p, bool dgrad, int dtype)
+{
+    const ConvBwdGeom &g = p.g;
+    ConvArgs a;
+    a.B = g.N;
+    if (!dgrad) { a.H = g.H; a.W = g.W; a.Cin = p.CiPad; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Cout; a.Npad = p.NpadF; a.pad = g.pad; a.stride = 2; }
+    else { a.H = p.Hd; a.W = p.Wd; a.Cin = p.CoPad; a.Ho = g.H; a.Wo = g.W; a.Cout = g.Cin; a.Npad = p.NpadD; a.pad = 2 - g.pad; a.stride = 1; }
+    a.kh = a.kw = 3; a.dil = 1;
+    a.relu = 0; a.out_f32 = 1;
+    a.o_cs = a.Cout; a.o_rs = (long long)a.Wo * a.Cout; a.o_bs = (long long)a.Ho * a.Wo * a.Cout;
+    a.dtype = dtype;
+    a.kdisable = KOFF_HEAD3X3;             // (conv2d_args: every shape on conv_igemm.hip)
+    a.splitk = conv_splitk_choice(a);      // the extras layer (10 x 10 -> 5 x 5) fills the chip by K slices, as in the engine
+    return a;
+}
+
+int convs2_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
+                ConvS2Plan &p)
+{
+    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
+    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
+    // what the kernels cover: k = 3 at stride 2, dilation 1, one pad <= 2 for both axes (the input gradient is then a conv with
+    // pad' = 2 - pad >= 0).  Stride 1 is section i-c's: the two families are disjoint.
+    if (kH != 3 || kW != 3 || dH != 2 || dW != 2 || dilH != 1 || dilW != 1 || padH != padW || padH > 2) return TDRN_E_UNSUPPORTED;
+    const long long Ho = ((long long)H + 2 * padH - 3) / 2 + 1, Wo = ((long long)W + 2 * padW - 3) / 2 + 1;
+    const long long Hd = (long long)H + 2 * padH - 2, Wd = (long long)W + 2 * padW - 2;
+    p.CiPad = conv_bwd_cpad(Cin); p.CoPad = conv_bwd_cpad(Cout);
+    // 32-bit offsets of the kernels (conv_igemm.hip: elements of its input; conv_bwd.hip: pixels): every padded tensor below 2^31
+    if ((long long)N * H * W * p.CiPad >= (1ll << 31) || (long long)N * Ho * Wo * p.CoPad >= (1ll << 31) ||
+        (long long)N * Hd * Wd * p.CoPad >= (1ll << 31))
+        return TDRN_E_UNSUPPORTED;
+    p.g = ConvBwdGeom{N, Cin, H, W, Cout, 3, padH, 1, (int)Ho, (int)Wo, 2};
+    p.Hd = (int)Hd; p.Wd = (int)Wd;
+    p.NpadF = conv_n_pad(Cout); p.NpadD = conv_n_pad(Cin);
+    const int es = dtype_bytes(dtype);
+    const size_t wf = (size_t)p.NpadF * 9 * p.CiPad * es, wd = (size_t)p.NpadD * 9 * p.CoPad * es;
+    const size_t of = (size_t)N * Ho * Wo * Cout * 4, od = (size_t)N * H * W * Cin * 4;
+    size_t o = 0;
+    p.o_zero = o; o += kZeroPageBytes;
+    p.o_x = o;    o += align_up((size_t)N * H * W * p.CiPad * es, 256);
+    p.o_go = o;   o += align_up((size_t)N * Hd * Wd * p.CoPad * es, 256);     // (Hd >= Ho, Wd >= Wo: the plain image fits as well)
+    p.o_slab = o;
+    const size_t slab_end = o + conv_wgrad_slab_bytes(p.g);
+    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
+    p.o_bias = o; o += align_up((size_t)(p.NpadF > p.NpadD ? p.NpadF : p.NpadD) * 4, 256);
+    p.o_out = o;  o += align_up(of > od ? of : od, 256);
+    const ConvArgs af = convs2_args(p, false, dtype), ad = convs2_args(p, true, dtype);
+    const size_t pf = conv_splitk_bytes(af, af.splitk), pd = conv_splitk_bytes(ad, ad.splitk);
+    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
+    p.total = o > slab_end ? o : slab_end;
+    return TDRN_OK;
+}
+
+// launch_conv with an fp32 NHWC result [pixels][Cout] in the workspace, then NCHW into `out`
+int convs2_run(const ConvS2Plan &p, char *ws, bool dgrad, int dtype, float *out, hipStream_t s)
+{
+    ConvArgs a = convs2_args(p, dgrad, dtype);
+    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
+    a.out = ws + p.o_out;
+    if (a.splitk > 1) a.partial = ws + p.o_partial;
+    TDRN_TRY(launch_conv(a, s));
+    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.o_cs, out, p.g.N, a.Cout, a.Ho * a.Wo, s);
 }
 
 // BatchNorm2d (section i-d): the geometry checks of the query and of both entries
@@ -516,6 +593,68 @@ int tdrn_conv_transpose2d_backward_parameters(const float *input, const float *g
     const float *bslab;
     TDRN_TRY(launch_conv_wgrad_slabs(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, compute, s, splits, bslab));
     return launch_convt_wgrad_reduce((const float *)(ws + p.o_slab), bslab, grad_weight, grad_bias, Cin, Cout, splits, scale, s);
+}
+
+size_t tdrn_conv2d_strided_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                           int dilationH, int dilationW, tdrn_dtype compute)
+{
+    ConvS2Plan p;
+    if (convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) != TDRN_OK) return 0;
+    return p.total;
+}
+
+int tdrn_conv2d_strided_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W,
+                                int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !output) return TDRN_E_ARG;
+    ConvS2Plan p;
+    TDRN_TRY(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.NpadF, Cin, 9, 1, p.CiPad, compute, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadF * 4, s));
+    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+    return convs2_run(p, ws, false, compute, output, s);
+}
+
+int tdrn_conv2d_strided_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W,
+                                       int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                       tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
+    ConvS2Plan p;
+    TDRN_TRY(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    // the zero-inserted image: the kernel stores every element of it, zeros included
+    TDRN_TRY(launch_nchw_to_nhwc_dilate2(grad_output, ws + p.o_go, N, Cout, p.g.Ho, p.g.Wo, p.Hd, p.Wd, compute, s));
+    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.NpadD, 9, compute, s));
+    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadD * 4, s));
+    // a stride-1 conv over it: kernel rotated and transposed (the packing above), pad' = 2 - pad
+    return convs2_run(p, ws, true, compute, grad_input, s);
+}
+
+int tdrn_conv2d_strided_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N,
+                                            int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                            int dilationH, int dilationW, float scale, tdrn_dtype compute, void *workspace,
+                                            size_t workspace_bytes, void *stream)
+{
+    if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
+    ConvS2Plan p;
+    TDRN_TRY(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
+    return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
 }
 
 size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W)

@@ -1,4 +1,5 @@
-// conv_bwd.hip -- the gradients of the dense stride-1 convolution (tdrn_hip.h section i-c) that no inference kernel computes:
+// conv_bwd.hip -- the gradients of the dense convolution (tdrn_hip.h section i-c; with the output pixel stepped by ConvBwdGeom::stride
+// also section i-g's weight gradient) that no inference kernel computes:
 //   grad_weight[co][ci][i][j] += scale * sum_p GO[p][co] * X[p (+) tap][ci]      (wgrad: conv_wgrad_kernel + conv_wgrad_reduce_kernel)
 //   grad_bias[co]             += scale * sum_p GO[p][co]                         (the same two kernels)
 // and the weight packing of the input gradient, which is launch_conv over grad_output with the kernel rotated by 180 degrees
@@ -43,6 +44,7 @@ struct WgradParams {
     const char *x, *go, *zero;
     float *slab, *bslab;
     int M, H, W, Ho, Wo, HoWo, CiPad, CoPad, pad, dil, per_split;
+    int stride = 1;        // input rows / columns per output pixel (2: tdrn_hip.h section i-g)
 };
 
 template <typename DT> struct WgLds {
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams g)
         for (int v = 0; v < V16; ++v) rgo[v] = *(const u32x4 *)(src + 16 * v);
     };
     auto load_x = [&](int tap) {
-        const int hi = pho - g.pad + (tap / KK) * g.dil, wi = pwo - g.pad + (tap % KK) * g.dil;
+        const int hi = pho * g.stride - g.pad + (tap / KK) * g.dil, wi = pwo * g.stride - g.pad + (tap % KK) * g.dil;
         const bool ok = pvalid && hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
         const char *src = ok ? g.x + ((((size_t)pn * g.H + hi) * g.W + wi) * g.CiPad + ci0 + sq * 16) * ES : zsrc;
 #pragma unroll
@@ -302,7 +304,7 @@ int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int N
 int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, int dtype,
                             hipStream_t s, int &splits, const float *&bias_slab)
 {
-    if ((g.k != 1 && g.k != 3) || !x_nhwc || !go_nhwc || !zero_page || !slab) return TDRN_E_UNSUPPORTED;
+    if ((g.k != 1 && g.k != 3) || g.stride < 1 || !x_nhwc || !go_nhwc || !zero_page || !slab) return TDRN_E_UNSUPPORTED;
     int S, per_split;
     conv_wgrad_splits(g, S, per_split);
     const int taps = g.k * g.k;
@@ -312,7 +314,7 @@ int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void
     p.slab = (float *)slab;
     p.bslab = (float *)((char *)slab + align_up((size_t)S * taps * p.CoPad * p.CiPad * 4, 256));
     p.M = g.N * g.Ho * g.Wo; p.H = g.H; p.W = g.W; p.Ho = g.Ho; p.Wo = g.Wo; p.HoWo = g.Ho * g.Wo;
-    p.pad = g.pad; p.dil = g.dil; p.per_split = per_split;
+    p.pad = g.pad; p.dil = g.dil; p.per_split = per_split; p.stride = g.stride;
     const dim3 grid((unsigned)S, (unsigned)(p.CiPad / kWgTile), (unsigned)(p.CoPad / kWgTile));
     int rc = TDRN_E_ARG;
     switch (dtype) {

@@ -248,7 +248,9 @@ int launch_deform_bwd_weight(const DeformBwdGeom &g, const float *in_nhwc, const
                              float scale, hipStream_t s);
 // Dense stride-1 conv backward (conv_bwd.hip; tdrn_hip.h section i-c).  x_nhwc / go_nhwc: the input and grad_output as NHWC in the compute
 // type, channels padded to conv_bwd_cpad (launch_nchw_to_nhwc).  Square kernels k = 1 | 3, one pad / dilation for both axes.
-struct ConvBwdGeom { int N, Cin, H, W, Cout, k, pad, dil, Ho, Wo; };
+// stride (trailing, default 1: every positional initialiser keeps its meaning) steps the output pixel of the weight gradient: 2 for
+// the strided family (conv_strided.hip; tdrn_hip.h section i-g), whose K = N*Ho*Wo is that of the strided output.
+struct ConvBwdGeom { int N, Cin, H, W, Cout, k, pad, dil, Ho, Wo; int stride = 1; };
 int conv_bwd_cpad(int c);
 // K splits of the weight gradient, from the geometry alone (the result does not depend on the device's state)
 void conv_wgrad_splits(const ConvBwdGeom &g, int &splits, int &per_split);
@@ -274,6 +276,11 @@ int launch_repack_iohw_dgrad(const float *w, void *out, int Cin, int Cout, int N
 // bias_slab[split][z * CoPad + co]: the slabs of launch_conv_wgrad_slabs on ConvBwdGeom{N, Cin, H, W, 4 CoPad, 1, 0, 1, H, W}
 int launch_convt_wgrad_reduce(const float *slab, const float *bias_slab, float *grad_weight, float *grad_bias, int Cin, int Cout, int splits,
                               float scale, hipStream_t s);
+// Dense 3x3 stride-2 conv with gradients (conv_strided.hip; tdrn_hip.h section i-g).  The input gradient is a stride-1 conv over the
+// zero-inserted image of grad_output: fp32 NCHW (N, Cout, Ho, Wo) -> DT NHWC D[n][r][c][CoPad] with Hd x Wd rows and columns
+// (Hd = 2 Ho - 1 or 2 Ho, the caller's H + 2 pad - 2; Wd likewise), D[2 ho][2 wo] = go[ho][wo], every other element zero (odd rows and
+// columns, padded channels).  The kernel writes EVERY element of D itself.
+int launch_nchw_to_nhwc_dilate2(const float *in, void *out, int N, int Cout, int Ho, int Wo, int Hd, int Wd, int dtype, hipStream_t s);
 // BatchNorm2d with an optional fused ReLU, fp32 NCHW (batch_norm.hip; tdrn_hip.h section i-d).  Every pass cuts a channel's N*HW values
 // into `splits` pieces of per_split elements, from (N, C, HW) alone; the workspace holds the per-(channel, split) records of the reducing
 // passes and the backward's per-channel sums: 12 C splits + 8 C bytes

@@ -1,7 +1,7 @@
 """Parameter-holder builders mirroring model/networks.py of the reference (vgg :136-163,
 conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615,
 ConvOffset2dFunction :617-697, ConvOffset2d :699-733), plus the trainable dense conv (Conv2dFunction / conv2d / Conv2d: what
-nn.Conv2d and autograd give the reference's training loop) and the trainable batch norm with a fused ReLU (BatchNormFunction /
+nn.Conv2d and autograd give the reference's training loop; stride 1, and 3x3 at stride 2) and the trainable batch norm with a fused ReLU (BatchNormFunction /
 batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d) and L2Norm (L2NormFunction / l2norm / L2Norm),
 and the trainable 2x2 stride-2 transposed conv of the TCB up_layers (ConvTranspose2dFunction / conv_transpose2d / ConvTranspose2d).
 The modules only own parameters with the reference's names and
@@ -178,34 +178,49 @@ class ConvOffset2d(nn.Module):
                              self.num_deformable_groups)
 
 
-def _conv2d_geometry(x, w, padding, dilation):
-    (ph, pw), (dh, dw) = _pair(padding), _pair(dilation)
+_CONV2D_COVERED = ("square k in {1, 3} at stride 1 with 0 <= pad <= dilation * (k - 1); k = 3 at stride 2 with dilation 1 and "
+                   "0 <= pad <= 2")
+
+
+def _conv2d_family(stride):
+    """the C ABI family of a stride: "tdrn_conv2d" (stride 1, section i-c) or "tdrn_conv2d_strided" (stride 2, section i-g)"""
+    sh, sw = (int(v) for v in _pair(stride))
+    if (sh, sw) == (1, 1):
+        return "tdrn_conv2d"
+    if (sh, sw) == (2, 2):
+        return "tdrn_conv2d_strided"
+    raise RuntimeError("conv2d: stride %r is outside what libtdrn_hip covers (%s)" % (stride, _CONV2D_COVERED))
+
+
+def _conv2d_geometry(x, w, padding, dilation, stride=1):
+    (ph, pw), (dh, dw), (sh, sw) = _pair(padding), _pair(dilation), _pair(stride)
     N, Cin, H, W = x.shape
     Cout, Cw, kh, kw = w.shape
     if Cw != Cin:
         raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (Cw, Cin))
-    Ho = H + 2 * ph - (dh * (kh - 1) + 1) + 1
-    Wo = W + 2 * pw - (dw * (kw - 1) + 1) + 1
+    Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+    Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
     # the C ABI's argument order: N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW
-    return (N, Cin, H, W, Cout, kh, kw, 1, 1, ph, pw, dh, dw), (N, Cout, Ho, Wo)
+    return (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw), (N, Cout, Ho, Wo)
 
 
-def _conv2d_workspace(lib, dims, dt, device):
-    nb = lib.tdrn_conv2d_workspace_bytes(*dims, dt)
+def _conv2d_workspace(lib, dims, dt, device, family="tdrn_conv2d"):
+    nb = getattr(lib, family + "_workspace_bytes")(*dims, dt)
     if nb == 0:
-        raise RuntimeError("conv2d: geometry outside what libtdrn_hip covers (square k in {1, 3}, stride 1, "
-                           "0 <= pad <= dilation * (k - 1)): N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW = %r" % (dims,))
+        raise RuntimeError("conv2d: geometry outside what libtdrn_hip covers (%s): "
+                           "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW = %r" % (_CONV2D_COVERED, dims))
     return torch.empty(nb, dtype=torch.uint8, device=device), nb
 
 
-def _conv2d_forward(x, w, b, padding, dilation, compute):
+def _conv2d_forward(x, w, b, padding, dilation, compute, stride=1):
     lib = _lib.lib()
-    dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
+    family = _conv2d_family(stride)
+    dims, out_shape = _conv2d_geometry(x, w, padding, dilation, stride)
     dt = _lib.DTYPES[compute]
-    ws, nb = _conv2d_workspace(lib, dims, dt, x.device)
+    ws, nb = _conv2d_workspace(lib, dims, dt, x.device, family)
     out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-    _lib.check(lib.tdrn_conv2d_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
-                                       _lib.current_stream(x.device)), "tdrn_conv2d_forward")
+    _lib.check(getattr(lib, family + "_forward")(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
+                                                 _lib.current_stream(x.device)), family + "_forward")
     return out
 
 
@@ -218,23 +233,24 @@ def _conv2d_require_cuda(input, weight, bias):
 
 
 class Conv2dFunction(torch.autograd.Function):
-    """Dense stride-1 conv2d with gradients: forward through tdrn_conv2d_forward, backward through
+    """Dense conv2d with gradients: forward through tdrn_conv2d_forward, backward through
     tdrn_conv2d_backward_input (when the input needs a gradient) and tdrn_conv2d_backward_parameters (weight and bias
     gradients, scale 1 into zeroed buffers).  `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the forward and
-    of both gradients.  Geometry the library rejects raises; nothing falls back to torch.
+    of both gradients.  `stride` (an int or a pair) 1 is that family; 2 is the 3x3 family tdrn_conv2d_strided_* with the same three
+    entries.  Geometry the library rejects raises; nothing falls back to torch.
 
-        y = Conv2dFunction.apply(input, weight, bias_or_None, padding, dilation[, compute])
+        y = Conv2dFunction.apply(input, weight, bias_or_None, padding, dilation[, compute, stride])
     """
 
     @staticmethod
-    def forward(ctx, input, weight, bias=None, padding=0, dilation=1, compute="fp32"):
+    def forward(ctx, input, weight, bias=None, padding=0, dilation=1, compute="fp32", stride=1):
         if input.dim() != 4:
             raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
         _conv2d_require_cuda(input, weight, bias)
         x, w = input.contiguous().float(), weight.contiguous().float()
         b = None if bias is None else bias.contiguous().float()
-        out = _conv2d_forward(x, w, b, padding, dilation, compute)
-        ctx.conf = (padding, dilation, compute, bias is not None)
+        out = _conv2d_forward(x, w, b, padding, dilation, compute, stride)
+        ctx.conf = (padding, dilation, compute, bias is not None, stride)
         ctx.save_for_backward(x, w)
         return out
 
@@ -244,9 +260,10 @@ class Conv2dFunction(torch.autograd.Function):
         x, w = ctx.saved_tensors
         if not grad_output.is_cuda:
             raise NotImplementedError("conv2d backward: grad_output must be a CUDA tensor")
-        padding, dilation, compute, has_bias = ctx.conf
+        padding, dilation, compute, has_bias, stride = ctx.conf
         lib = _lib.lib()
-        dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
+        family = _conv2d_family(stride)
+        dims, out_shape = _conv2d_geometry(x, w, padding, dilation, stride)
         go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
         if tuple(go.shape) != out_shape:
             raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
@@ -255,42 +272,45 @@ class Conv2dFunction(torch.autograd.Function):
         grad_input = grad_weight = grad_bias = None
         if need_in or need_w or need_b:
             dt = _lib.DTYPES[compute]
-            ws, nb = _conv2d_workspace(lib, dims, dt, x.device)
+            ws, nb = _conv2d_workspace(lib, dims, dt, x.device, family)
             stream = _lib.current_stream(x.device)
         if need_in:
             grad_input = torch.empty_like(x)
-            _lib.check(lib.tdrn_conv2d_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws), nb,
-                                                      stream), "tdrn_conv2d_backward_input")
+            _lib.check(getattr(lib, family + "_backward_input")(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws),
+                                                                nb, stream), family + "_backward_input")
         if need_w or need_b:
             gw = torch.zeros_like(w)
             gb = torch.zeros(w.shape[0], dtype=torch.float32, device=x.device) if need_b else None
-            _lib.check(lib.tdrn_conv2d_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
-                                                           _lib.ptr(ws), nb, stream), "tdrn_conv2d_backward_parameters")
+            _lib.check(getattr(lib, family + "_backward_parameters")(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
+                                                                     _lib.ptr(ws), nb, stream), family + "_backward_parameters")
             grad_weight = gw if need_w else None
             grad_bias = gb
-        return grad_input, grad_weight, grad_bias, None, None, None
+        return grad_input, grad_weight, grad_bias, None, None, None, None
 
 
-def conv2d(input, weight, bias=None, padding=0, dilation=1, compute="fp32"):
-    """Dense stride-1 conv2d on libtdrn_hip (NCHW fp32 CUDA tensors in, NCHW fp32 out), differentiable in input, weight and
-    bias.  With grad mode off, or when nothing requires grad, only the forward runs and the output has no grad_fn."""
+def conv2d(input, weight, bias=None, padding=0, dilation=1, compute="fp32", stride=1):
+    """Dense conv2d on libtdrn_hip (NCHW fp32 CUDA tensors in, NCHW fp32 out), differentiable in input, weight and
+    bias.  `stride` is an int or a pair: 1, or 2 for a 3x3 kernel at dilation 1 (the `extras` layer of the VGG detectors, the first
+    conv of the MobileNet trunk); another stride raises.  With grad mode off, or when nothing requires grad, only the forward runs
+    and the output has no grad_fn."""
+    _conv2d_family(stride)                  # a stride the library does not cover raises before anything else
     if input is not None and input.dim() != 4:
         raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
     _conv2d_require_cuda(input, weight, bias)
     if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return Conv2dFunction.apply(input, weight, bias, padding, dilation, compute)
+        return Conv2dFunction.apply(input, weight, bias, padding, dilation, compute, stride)
     x, w = input.contiguous().float(), weight.detach().contiguous().float()
     b = None if bias is None else bias.detach().contiguous().float()
-    return _conv2d_forward(x, w, b, padding, dilation, compute)
+    return _conv2d_forward(x, w, b, padding, dilation, compute, stride)
 
 
 class Conv2d(nn.Module):
-    """nn.Conv2d's parameters and default init (weight, bias) on conv2d above: stride 1, groups 1."""
+    """nn.Conv2d's parameters and default init (weight, bias) on conv2d above: stride 1 or 2 (the last argument), groups 1."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, padding=0, dilation=1, bias=True, compute="fp32"):
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, dilation=1, bias=True, compute="fp32", stride=1):
         super(Conv2d, self).__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.padding, self.dilation = _pair(kernel_size), _pair(padding), _pair(dilation)
+        self.kernel_size, self.padding, self.dilation, self.stride = _pair(kernel_size), _pair(padding), _pair(dilation), _pair(stride)
         self.compute = compute
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
@@ -304,7 +324,7 @@ class Conv2d(nn.Module):
             nn.init.uniform_(self.bias, -bound, bound)
 
     def forward(self, input):
-        return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute)
+        return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute, self.stride)
 
 
 def _conv_transpose2d_geometry(x, w, stride, padding=0, output_padding=0):
