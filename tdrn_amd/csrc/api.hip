@@ -1,4 +1,5 @@
 // api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g) and (ii) (section (iii) is in net.hip).
+// Sections (i-c), (i-f) and (i-g), the trainable conv families, share one plan, one workspace layout and one runner (ConvTrainPlan).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -74,36 +75,92 @@ int deform_bwd_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int 
     return TDRN_OK;
 }
 
-// dense conv2d with gradients (section i-c).  Workspace: zero page | input NHWC | grad_output NHWC | the rest, which is either
-// {packed weight, padded bias, NHWC fp32 result, split-K partials of launch_conv} (forward, backward_input) or the split-K slabs (backward_parameters).
-struct Conv2dPlan {
-    ConvBwdGeom g;
-    int taps, CiPad, CoPad, NpadF, NpadD;
+// The three trainable conv families: dense conv2d at stride 1 (section i-c), ConvTranspose2d(k = 2, s = 2) (section i-f) and the 3x3
+// conv at stride 2 (section i-g).  In each the forward and the input gradient are one launch_conv with an fp32 NHWC result, and the
+// weight gradient is one conv_bwd.hip GEMM: a family is its geometry checks and these three descriptions (conv2d_plan, convt2d_plan,
+// convs2_plan); layout, bias staging and the run are shared.
+// Workspace: zero page | x NHWC | the grad_output image NHWC (what the input gradient convolves) | the rest, which is either {packed
+// weight, padded bias, NHWC fp32 result, split-K partials of launch_conv} (forward, backward_input; each the larger of the two) or the
+// split-K slabs of the weight gradient (backward_parameters).
+struct ConvTrainPlan {
+    ConvArgs fwd, dgrad;    // launch_conv's arguments without their pointers; fwd.Cin = CiPad, dgrad.Cin = the image's padded channels
+    ConvBwdGeom wg;         // the weight gradient's geometry
     size_t o_zero, o_x, o_go, o_w, o_bias, o_out, o_partial, o_slab, total;
 };
 
-// the launch_conv arguments of the forward (dgrad = false) or of the input gradient -- a stride-1 conv over grad_output with
-// pad' = dil (k - 1) - pad -- without their pointers: fp32 NHWC result [pixels][Cout], no ReLU
-ConvArgs conv2d_args(const Conv2dPlan &p, bool dgrad, int dtype)
+// an fp32 NHWC result without gaps: [B][Ho][Wo][Cout]
+void conv_train_dense_out(ConvArgs &a)
 {
-    const ConvBwdGeom &g = p.g;
-    ConvArgs a;
-    a.B = g.N;
-    if (!dgrad) { a.H = g.H; a.W = g.W; a.Cin = p.CiPad; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Cout; a.Npad = p.NpadF; a.pad = g.pad; }
-    else { a.H = g.Ho; a.W = g.Wo; a.Cin = p.CoPad; a.Ho = g.H; a.Wo = g.W; a.Cout = g.Cin; a.Npad = p.NpadD; a.pad = g.dil * (g.k - 1) - g.pad; }
-    a.kh = a.kw = g.k; a.stride = 1; a.dil = g.dil;
-    a.relu = 0; a.out_f32 = 1;
     a.o_cs = a.Cout; a.o_rs = (long long)a.Wo * a.Cout; a.o_bs = (long long)a.Ho * a.Wo * a.Cout;
+}
+
+// what the families' launches share, set once their geometry and output strides are: fp32 result, no ReLU
+void conv_train_args(ConvArgs &a, int dtype)
+{
+    a.relu = 0; a.out_f32 = 1;
     a.dtype = dtype;
     // every shape on conv_igemm.hip: head3x3.hip would take the narrow 16-bit layers with another fp32 K order, and a layer's
     // gradient should not change its rounding with its channel count
     a.kdisable = KOFF_HEAD3X3;
-    a.splitk = conv_splitk_choice(a);      // the small-M layers (10 x 10, 5 x 5 maps) fill the chip by K slices, as in the engine
-    return a;
+    // the small-M layers (the 10 x 10 and 5 x 5 maps, the extras layer between them) fill the chip by K slices, as in the engine
+    a.splitk = conv_splitk_choice(a);
 }
 
+// offsets and total from the two launches (each one's input image, packed weight [phases][Npad][taps][Cin] and result) and the slabs
+void conv_train_layout(ConvTrainPlan &p, int dtype)
+{
+    conv_train_args(p.fwd, dtype);
+    conv_train_args(p.dgrad, dtype);
+    const ConvArgs &f = p.fwd, &d = p.dgrad;
+    const size_t es = dtype_bytes(dtype);
+    const size_t wf = (size_t)f.phases * f.Npad * f.kh * f.kw * f.Cin * es, wd = (size_t)d.phases * d.Npad * d.kh * d.kw * d.Cin * es;
+    const size_t of = (size_t)f.B * f.o_bs * 4, od = (size_t)d.B * d.o_bs * 4;
+    const size_t pf = conv_splitk_bytes(f, f.splitk), pd = conv_splitk_bytes(d, d.splitk);
+    size_t o = 0;
+    p.o_zero = o; o += kZeroPageBytes;
+    p.o_x = o;    o += align_up((size_t)f.B * f.H * f.W * f.Cin * es, 256);
+    p.o_go = o;   o += align_up((size_t)d.B * d.H * d.W * d.Cin * es, 256);
+    p.o_slab = o;
+    const size_t slab_end = o + conv_wgrad_slab_bytes(p.wg);
+    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
+    p.o_bias = o; o += align_up((size_t)(f.Npad > d.Npad ? f.Npad : d.Npad) * 4, 256);
+    p.o_out = o;  o += align_up(of > od ? of : od, 256);
+    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
+    p.total = o > slab_end ? o : slab_end;
+}
+
+// what every entry does after its pointer check: the plan's verdict, the workspace, the zero page
+int conv_train_begin(int plan_rc, const ConvTrainPlan &p, void *workspace, size_t workspace_bytes, hipStream_t s)
+{
+    TDRN_TRY(plan_rc);
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    return launch_fill_zero((char *)workspace + p.o_zero, kZeroPageBytes, s);
+}
+
+// launch_conv's bias: Npad zeros, under the caller's Cout values when there are any
+int conv_train_bias(const ConvArgs &a, char *ws_bias, const float *bias, hipStream_t s)
+{
+    TDRN_TRY(launch_fill_zero(ws_bias, (size_t)a.Npad * 4, s));
+    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws_bias, bias, (size_t)a.Cout * 4, hipMemcpyDeviceToDevice, s));
+    return TDRN_OK;
+}
+
+// launch_conv with its fp32 NHWC result in the workspace ([pixels][Cout], pixels = Ho Wo or, through four phases, 4 H W), then NCHW
+// into `out`
+int conv_train_run(const ConvTrainPlan &p, char *ws, bool dgrad, float *out, hipStream_t s)
+{
+    ConvArgs a = dgrad ? p.dgrad : p.fwd;
+    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
+    a.out = ws + p.o_out;
+    if (a.splitk > 1) a.partial = ws + p.o_partial;
+    TDRN_TRY(launch_conv(a, s));
+    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.Cout, out, a.B, a.Cout, a.phases * a.Ho * a.Wo, s);
+}
+
+// dense conv2d (section i-c).  The input gradient is a stride-1 conv over grad_output, kernel rotated and transposed
+// (launch_repack_oihw_dgrad), with pad' = dil (k - 1) - pad and the same dilation.
 int conv2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
-                Conv2dPlan &p)
+                ConvTrainPlan &p)
 {
     if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
@@ -112,80 +169,31 @@ int conv2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, 
     const long long Wo = ((long long)W + 2ll * padW - ((long long)dilW * (kW - 1) + 1)) / dW + 1;
     if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
     if (Ho < 1 || Wo < 1) return TDRN_E_SHAPE;
-    // what the kernels cover: square k = 1 | 3, stride 1, one pad / dilation for both axes, pad <= dil (k - 1) (the input gradient
-    // is then a conv with pad' = dil (k - 1) - pad >= 0)
+    // what the kernels cover: square k = 1 | 3, stride 1, one pad / dilation for both axes, pad <= dil (k - 1) (pad' >= 0)
     if (kH != kW || (kH != 1 && kH != 3) || dH != 1 || dW != 1 || padH != padW || dilH != dilW) return TDRN_E_UNSUPPORTED;
     if ((long long)padH > (long long)dilH * (kH - 1)) return TDRN_E_UNSUPPORTED;
-    const int es = dtype_bytes(dtype);
-    p.taps = kH * kW;
-    p.CiPad = conv_bwd_cpad(Cin); p.CoPad = conv_bwd_cpad(Cout);
+    const int CiPad = conv_bwd_cpad(Cin), CoPad = conv_bwd_cpad(Cout);
     // 32-bit offsets of the kernels (conv_igemm.hip: elements; conv_bwd.hip: pixels)
-    if ((long long)N * H * W * p.CiPad >= (1ll << 31) || (long long)N * Ho * Wo * p.CoPad >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * Ho * Wo * CoPad >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
     if ((long long)dilH * (kH - 1) >= (1 << 20)) return TDRN_E_UNSUPPORTED;
-    p.g = ConvBwdGeom{N, Cin, H, W, Cout, kH, padH, dilH, (int)Ho, (int)Wo};
-    p.NpadF = conv_n_pad(Cout); p.NpadD = conv_n_pad(Cin);
-    const size_t wf = (size_t)p.NpadF * p.taps * p.CiPad * es, wd = (size_t)p.NpadD * p.taps * p.CoPad * es;
-    const size_t of = (size_t)N * Ho * Wo * Cout * 4, od = (size_t)N * H * W * Cin * 4;
-    size_t o = 0;
-    p.o_zero = o; o += kZeroPageBytes;
-    p.o_x = o;    o += align_up((size_t)N * H * W * p.CiPad * es, 256);
-    p.o_go = o;   o += align_up((size_t)N * Ho * Wo * p.CoPad * es, 256);
-    p.o_slab = o;
-    const size_t slab_end = o + conv_wgrad_slab_bytes(p.g);
-    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
-    p.o_bias = o; o += align_up((size_t)(p.NpadF > p.NpadD ? p.NpadF : p.NpadD) * 4, 256);
-    p.o_out = o;  o += align_up(of > od ? of : od, 256);
-    const ConvArgs af = conv2d_args(p, false, dtype), ad = conv2d_args(p, true, dtype);
-    const size_t pf = conv_splitk_bytes(af, af.splitk), pd = conv_splitk_bytes(ad, ad.splitk);
-    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
-    p.total = o > slab_end ? o : slab_end;
+    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, kH, padH, dilH, (int)Ho, (int)Wo};
+    ConvArgs &f = p.fwd, &d = p.dgrad;
+    f.B = d.B = N;
+    f.H = d.Ho = H; f.W = d.Wo = W; f.Ho = d.H = (int)Ho; f.Wo = d.W = (int)Wo;
+    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.pad = padH;
+    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin); d.pad = dilH * (kH - 1) - padH;
+    f.kh = f.kw = d.kh = d.kw = kH; f.dil = d.dil = dilH;
+    conv_train_dense_out(f);
+    conv_train_dense_out(d);
+    conv_train_layout(p, dtype);
     return TDRN_OK;
 }
 
-// launch_conv with an fp32 NHWC result [pixels][Cout] in the workspace, then NCHW into `out`
-int conv2d_run(const Conv2dPlan &p, char *ws, bool dgrad, int dtype, float *out, hipStream_t s)
-{
-    ConvArgs a = conv2d_args(p, dgrad, dtype);
-    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
-    a.out = ws + p.o_out;
-    if (a.splitk > 1) a.partial = ws + p.o_partial;
-    TDRN_TRY(launch_conv(a, s));
-    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.o_cs, out, p.g.N, a.Cout, a.Ho * a.Wo, s);
-}
-
-// ConvTranspose2d(k = 2, s = 2) with gradients (section i-f).  Workspace, in conv2d_plan's shape: zero page | input NHWC | the
-// space-to-depth image of grad_output | the rest, which is either {packed weight (the larger packing), padded bias, NHWC fp32 result
-// (the larger of output and grad_input), split-K partials of launch_conv} or the wgrad slabs.
-struct ConvT2dPlan {
-    int N, Cin, H, W, Cout, CiPad, CoPad, C4, NpadF, NpadD;
-    ConvBwdGeom wg;         // the one-tap weight-gradient GEMM over the space-to-depth image: 4 CoPad "output channels"
-    size_t o_zero, o_x, o_go, o_w, o_bias, o_out, o_partial, o_slab, total;
-};
-
-// the launch_conv arguments, without their pointers, of the forward (four phase GEMMs, each a 1x1 conv that writes every second
-// pixel of every second row) or of the input gradient (one 1x1 conv over the space-to-depth image): fp32 NHWC result, no ReLU
-ConvArgs convt2d_args(const ConvT2dPlan &p, bool dgrad, int dtype)
-{
-    ConvArgs a;
-    a.B = p.N; a.H = a.Ho = p.H; a.W = a.Wo = p.W;
-    a.kh = a.kw = 1; a.stride = 1; a.pad = 0; a.dil = 1;
-    a.relu = 0; a.out_f32 = 1;
-    if (!dgrad) {
-        a.Cin = p.CiPad; a.Cout = p.Cout; a.Npad = p.NpadF; a.phases = 4;
-        a.o_cs = 2ll * p.Cout; a.o_rs = 4ll * p.W * p.Cout; a.o_bs = 4ll * p.H * p.W * p.Cout;
-        a.o_pr = 2ll * p.W * p.Cout; a.o_pc = p.Cout;
-    } else {
-        a.Cin = p.C4; a.Cout = p.Cin; a.Npad = p.NpadD;
-        a.o_cs = p.Cin; a.o_rs = (long long)p.W * p.Cin; a.o_bs = (long long)p.H * p.W * p.Cin;
-    }
-    a.dtype = dtype;
-    a.kdisable = KOFF_HEAD3X3;             // (conv2d_args: every shape on conv_igemm.hip)
-    a.splitk = conv_splitk_choice(a);      // the 5 x 5 and 10 x 10 levels fill the chip by K slices, as in the engine
-    return a;
-}
-
+// ConvTranspose2d(k = 2, s = 2) (section i-f).  The forward is four phase GEMMs, each a 1x1 conv that writes every second pixel of
+// every second row; the input gradient is one 1x1 conv over the space-to-depth image of grad_output, whose C4 = 4 CoPad channels are
+// the (tap, cout) pairs of the sum; the weight gradient is the one-tap GEMM over that image with C4 "output channels".
 int convt2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int opadH, int opadW, int dilH,
-                 int dilW, int dtype, ConvT2dPlan &p)
+                 int dilW, int dtype, ConvTrainPlan &p)
 {
     if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0 || opadH < 0 || opadW < 0) return TDRN_E_SHAPE;
@@ -197,115 +205,51 @@ int convt2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH,
     if ((long long)H * W >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
     const long long px = (long long)N * ((long long)H * W);
     if (px >= (1ll << 31) || px * CiPad >= (1ll << 31) || px * 4 * CoPad >= (1ll << 31) || px * 4 * Cout >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-    p.CiPad = (int)CiPad; p.CoPad = (int)CoPad; p.C4 = 4 * p.CoPad;
-    p.NpadF = conv_n_pad(Cout); p.NpadD = conv_n_pad(Cin);
-    p.wg = ConvBwdGeom{N, Cin, H, W, p.C4, 1, 0, 1, H, W};
-    const int es = dtype_bytes(dtype);
-    const size_t wf = (size_t)4 * p.NpadF * p.CiPad * es, wd = (size_t)p.NpadD * p.C4 * es;
-    const size_t of = (size_t)px * 4 * Cout * 4, od = (size_t)px * Cin * 4;
-    size_t o = 0;
-    p.o_zero = o; o += kZeroPageBytes;
-    p.o_x = o;    o += align_up((size_t)px * p.CiPad * es, 256);
-    p.o_go = o;   o += align_up((size_t)px * p.C4 * es, 256);
-    p.o_slab = o;
-    const size_t slab_end = o + conv_wgrad_slab_bytes(p.wg);
-    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
-    p.o_bias = o; o += align_up((size_t)(p.NpadF > p.NpadD ? p.NpadF : p.NpadD) * 4, 256);
-    p.o_out = o;  o += align_up(of > od ? of : od, 256);
-    const ConvArgs af = convt2d_args(p, false, dtype), ad = convt2d_args(p, true, dtype);
-    const size_t pf = conv_splitk_bytes(af, af.splitk), pd = conv_splitk_bytes(ad, ad.splitk);
-    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
-    p.total = o > slab_end ? o : slab_end;
+    const int C4 = 4 * (int)CoPad;
+    p.wg = ConvBwdGeom{N, Cin, H, W, C4, 1, 0, 1, H, W};
+    ConvArgs &f = p.fwd, &d = p.dgrad;      // both 1x1 at stride 1 over H x W pixels: ConvArgs' defaults
+    f.B = d.B = N;
+    f.H = f.Ho = d.H = d.Ho = H; f.W = f.Wo = d.W = d.Wo = W;
+    f.Cin = (int)CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.phases = 4;
+    f.o_cs = 2ll * Cout; f.o_rs = 4ll * W * Cout; f.o_bs = 4ll * H * W * Cout;
+    f.o_pr = 2ll * W * Cout; f.o_pc = Cout;
+    d.Cin = C4; d.Cout = Cin; d.Npad = conv_n_pad(Cin);
+    conv_train_dense_out(d);
+    conv_train_layout(p, dtype);
     return TDRN_OK;
 }
 
-// launch_conv with an fp32 NHWC result in the workspace ([N][2H][2W][Cout] or [N][H][W][Cin]), then NCHW into `out`
-int convt2d_run(const ConvT2dPlan &p, char *ws, bool dgrad, int dtype, float *out, hipStream_t s)
-{
-    ConvArgs a = convt2d_args(p, dgrad, dtype);
-    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
-    a.out = ws + p.o_out;
-    if (a.splitk > 1) a.partial = ws + p.o_partial;
-    TDRN_TRY(launch_conv(a, s));
-    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.Cout, out, p.N, a.Cout, (dgrad ? 1 : 4) * p.H * p.W, s);
-}
-
-// dense 3x3 stride-2 conv with gradients (section i-g).  Workspace, in conv2d_plan's shape: zero page | input NHWC | grad_output NHWC
-// (backward_parameters) or its zero-inserted image D (backward_input; the larger of the two) | the rest, which is either {packed
-// weight, padded bias, NHWC fp32 result, split-K partials of launch_conv} or the wgrad slabs.
-struct ConvS2Plan {
-    ConvBwdGeom g;          // stride = 2: the weight gradient's geometry
-    int CiPad, CoPad, NpadF, NpadD, Hd, Wd;
-    size_t o_zero, o_x, o_go, o_w, o_bias, o_out, o_partial, o_slab, total;
-};
-
-// the launch_conv arguments, without their pointers, of the forward (stride 2) or of the input gradient: a stride-1 conv with
-// pad' = 2 - pad over the zero-inserted image (N, CoPad, Hd, Wd) -> (Cin, H, W).  fp32 NHWC result, no ReLU
-ConvArgs convs2_args(const ConvS2Plan &p, bool dgrad, int dtype)
-{
-    const ConvBwdGeom &g = p.g;
-    ConvArgs a;
-    a.B = g.N;
-    if (!dgrad) { a.H = g.H; a.W = g.W; a.Cin = p.CiPad; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Cout; a.Npad = p.NpadF; a.pad = g.pad; a.stride = 2; }
-    else { a.H = p.Hd; a.W = p.Wd; a.Cin = p.CoPad; a.Ho = g.H; a.Wo = g.W; a.Cout = g.Cin; a.Npad = p.NpadD; a.pad = 2 - g.pad; a.stride = 1; }
-    a.kh = a.kw = 3; a.dil = 1;
-    a.relu = 0; a.out_f32 = 1;
-    a.o_cs = a.Cout; a.o_rs = (long long)a.Wo * a.Cout; a.o_bs = (long long)a.Ho * a.Wo * a.Cout;
-    a.dtype = dtype;
-    a.kdisable = KOFF_HEAD3X3;             // (conv2d_args: every shape on conv_igemm.hip)
-    a.splitk = conv_splitk_choice(a);      // the extras layer (10 x 10 -> 5 x 5) fills the chip by K slices, as in the engine
-    return a;
-}
-
+// dense 3x3 stride-2 conv (section i-g).  The input gradient is a stride-1 conv with pad' = 2 - pad over the zero-inserted image D of
+// grad_output, (N, CoPad, Hd, Wd) -> (Cin, H, W), kernel rotated and transposed; backward_parameters keeps the plain grad_output image
+// in D's place (Hd >= Ho, Wd >= Wo: it fits).
 int convs2_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
-                ConvS2Plan &p)
+                ConvTrainPlan &p)
 {
     if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
     if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
     if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
-    // what the kernels cover: k = 3 at stride 2, dilation 1, one pad <= 2 for both axes (the input gradient is then a conv with
-    // pad' = 2 - pad >= 0).  Stride 1 is section i-c's: the two families are disjoint.
+    // what the kernels cover: k = 3 at stride 2, dilation 1, one pad <= 2 for both axes (pad' >= 0).  Stride 1 is section i-c's: the
+    // two families are disjoint.
     if (kH != 3 || kW != 3 || dH != 2 || dW != 2 || dilH != 1 || dilW != 1 || padH != padW || padH > 2) return TDRN_E_UNSUPPORTED;
     const long long Ho = ((long long)H + 2 * padH - 3) / 2 + 1, Wo = ((long long)W + 2 * padW - 3) / 2 + 1;
     const long long Hd = (long long)H + 2 * padH - 2, Wd = (long long)W + 2 * padW - 2;
-    p.CiPad = conv_bwd_cpad(Cin); p.CoPad = conv_bwd_cpad(Cout);
+    const int CiPad = conv_bwd_cpad(Cin), CoPad = conv_bwd_cpad(Cout);
     // 32-bit offsets of the kernels (conv_igemm.hip: elements of its input; conv_bwd.hip: pixels): every padded tensor below 2^31
-    if ((long long)N * H * W * p.CiPad >= (1ll << 31) || (long long)N * Ho * Wo * p.CoPad >= (1ll << 31) ||
-        (long long)N * Hd * Wd * p.CoPad >= (1ll << 31))
+    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * Ho * Wo * CoPad >= (1ll << 31) ||
+        (long long)N * Hd * Wd * CoPad >= (1ll << 31))
         return TDRN_E_UNSUPPORTED;
-    p.g = ConvBwdGeom{N, Cin, H, W, Cout, 3, padH, 1, (int)Ho, (int)Wo, 2};
-    p.Hd = (int)Hd; p.Wd = (int)Wd;
-    p.NpadF = conv_n_pad(Cout); p.NpadD = conv_n_pad(Cin);
-    const int es = dtype_bytes(dtype);
-    const size_t wf = (size_t)p.NpadF * 9 * p.CiPad * es, wd = (size_t)p.NpadD * 9 * p.CoPad * es;
-    const size_t of = (size_t)N * Ho * Wo * Cout * 4, od = (size_t)N * H * W * Cin * 4;
-    size_t o = 0;
-    p.o_zero = o; o += kZeroPageBytes;
-    p.o_x = o;    o += align_up((size_t)N * H * W * p.CiPad * es, 256);
-    p.o_go = o;   o += align_up((size_t)N * Hd * Wd * p.CoPad * es, 256);     // (Hd >= Ho, Wd >= Wo: the plain image fits as well)
-    p.o_slab = o;
-    const size_t slab_end = o + conv_wgrad_slab_bytes(p.g);
-    p.o_w = o;    o += align_up(wf > wd ? wf : wd, 256);
-    p.o_bias = o; o += align_up((size_t)(p.NpadF > p.NpadD ? p.NpadF : p.NpadD) * 4, 256);
-    p.o_out = o;  o += align_up(of > od ? of : od, 256);
-    const ConvArgs af = convs2_args(p, false, dtype), ad = convs2_args(p, true, dtype);
-    const size_t pf = conv_splitk_bytes(af, af.splitk), pd = conv_splitk_bytes(ad, ad.splitk);
-    p.o_partial = o; o += align_up(pf > pd ? pf : pd, 256);
-    p.total = o > slab_end ? o : slab_end;
+    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, 3, padH, 1, (int)Ho, (int)Wo, 2};
+    ConvArgs &f = p.fwd, &d = p.dgrad;
+    f.B = d.B = N;
+    f.H = d.Ho = H; f.W = d.Wo = W; f.Ho = (int)Ho; f.Wo = (int)Wo; d.H = (int)Hd; d.W = (int)Wd;
+    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.pad = padH; f.stride = 2;
+    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin); d.pad = 2 - padH;
+    f.kh = f.kw = d.kh = d.kw = 3;
+    conv_train_dense_out(f);
+    conv_train_dense_out(d);
+    conv_train_layout(p, dtype);
     return TDRN_OK;
-}
-
-// launch_conv with an fp32 NHWC result [pixels][Cout] in the workspace, then NCHW into `out`
-int convs2_run(const ConvS2Plan &p, char *ws, bool dgrad, int dtype, float *out, hipStream_t s)
-{
-    ConvArgs a = convs2_args(p, dgrad, dtype);
-    a.in = ws + (dgrad ? p.o_go : p.o_x); a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
-    a.out = ws + p.o_out;
-    if (a.splitk > 1) a.partial = ws + p.o_partial;
-    TDRN_TRY(launch_conv(a, s));
-    return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.o_cs, out, p.g.N, a.Cout, a.Ho * a.Wo, s);
 }
 
 // BatchNorm2d (section i-d): the geometry checks of the query and of both entries
@@ -469,12 +413,13 @@ int tdrn_deform_conv_backward_parameters(const float *input, const float *offset
     return launch_deform_bwd_weight(b.g, in_nhwc, offset, grad_output, (float *)(ws + b.o_slab), grad_weight, scale, s);
 }
 
+// The nine entries of the trainable conv families (ConvTrainPlan above): pointer check, plan, conv_train_begin, then each one's own
+// layout conversion(s), weight packing and tail.
 size_t tdrn_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
                                    int dilationH, int dilationW, tdrn_dtype compute)
 {
-    Conv2dPlan p;
-    if (conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) != TDRN_OK) return 0;
-    return p.total;
+    ConvTrainPlan p;
+    return conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
 }
 
 int tdrn_conv2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W, int Cout,
@@ -482,17 +427,15 @@ int tdrn_conv2d_forward(const float *input, const float *weight, const float *bi
                         void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
-    Conv2dPlan p;
-    TDRN_TRY(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
-    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.NpadF, Cin, p.taps, 1, p.CiPad, compute, s));
-    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadF * 4, s));
-    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    return conv2d_run(p, ws, false, compute, output, s);
+    TDRN_TRY(conv_train_begin(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
+                              workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
+    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.fwd.Npad, Cin, kH * kW, 1, p.fwd.Cin, compute, s));
+    TDRN_TRY(conv_train_bias(p.fwd, ws + p.o_bias, bias, s));
+    return conv_train_run(p, ws, false, output, s);
 }
 
 int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W, int Cout,
@@ -500,17 +443,15 @@ int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, fl
                                void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
-    Conv2dPlan p;
-    TDRN_TRY(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
-    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.NpadD, p.taps, compute, s));
-    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadD * 4, s));
-    // a stride-1 conv over grad_output: kernel rotated and transposed (the packing above), pad' = dil (k - 1) - pad, same dilation
-    return conv2d_run(p, ws, true, compute, grad_input, s);
+    TDRN_TRY(conv_train_begin(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
+                              workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
+    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.dgrad.Npad, kH * kW, compute, s));
+    TDRN_TRY(conv_train_bias(p.dgrad, ws + p.o_bias, nullptr, s));
+    return conv_train_run(p, ws, true, grad_input, s);
 }
 
 int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N, int Cin,
@@ -518,24 +459,21 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
                                     int dilationW, float scale, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
-    Conv2dPlan p;
-    TDRN_TRY(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
-    return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+    TDRN_TRY(conv_train_begin(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
+                              workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
+    return launch_conv_wgrad(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
 }
 
 size_t tdrn_conv_transpose2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
                                              int output_padH, int output_padW, int dilationH, int dilationW, tdrn_dtype compute)
 {
-    ConvT2dPlan p;
-    if (convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p) != TDRN_OK)
-        return 0;
-    return p.total;
+    ConvTrainPlan p;
+    return convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
 }
 
 int tdrn_conv_transpose2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W,
@@ -543,17 +481,15 @@ int tdrn_conv_transpose2d_forward(const float *input, const float *weight, const
                                   int dilationH, int dilationW, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
-    ConvT2dPlan p;
-    TDRN_TRY(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
-    TDRN_TRY(launch_repack_iohw_phases(weight, ws + p.o_w, Cin, Cout, p.NpadF, compute, s));
-    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadF * 4, s));
-    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    return convt2d_run(p, ws, false, compute, output, s);
+    TDRN_TRY(conv_train_begin(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW,
+                                           compute, p), p, workspace, workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
+    TDRN_TRY(launch_repack_iohw_phases(weight, ws + p.o_w, Cin, Cout, p.fwd.Npad, compute, s));
+    TDRN_TRY(conv_train_bias(p.fwd, ws + p.o_bias, bias, s));
+    return conv_train_run(p, ws, false, output, s);
 }
 
 int tdrn_conv_transpose2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W,
@@ -562,17 +498,15 @@ int tdrn_conv_transpose2d_backward_input(const float *grad_output, const float *
                                          void *stream)
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
-    ConvT2dPlan p;
-    TDRN_TRY(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(conv_train_begin(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW,
+                                           compute, p), p, workspace, workspace_bytes, s));
     TDRN_TRY(launch_nchw_to_nhwc_s2d(grad_output, ws + p.o_go, N, Cout, H, W, compute, s));
-    TDRN_TRY(launch_repack_iohw_dgrad(weight, ws + p.o_w, Cin, Cout, p.NpadD, compute, s));
-    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadD * 4, s));
-    // one 1x1 conv over the space-to-depth image: its 4 CoPad channels are the (tap, cout) pairs of the sum
-    return convt2d_run(p, ws, true, compute, grad_input, s);
+    TDRN_TRY(launch_repack_iohw_dgrad(weight, ws + p.o_w, Cin, Cout, p.dgrad.Npad, compute, s));
+    TDRN_TRY(conv_train_bias(p.dgrad, ws + p.o_bias, nullptr, s));
+    return conv_train_run(p, ws, true, grad_input, s);
 }
 
 int tdrn_conv_transpose2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N,
@@ -581,14 +515,14 @@ int tdrn_conv_transpose2d_backward_parameters(const float *input, const float *g
                                               tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
-    ConvT2dPlan p;
-    TDRN_TRY(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
+    TDRN_TRY(conv_train_begin(convt2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW,
+                                           compute, p), p, workspace, workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
     TDRN_TRY(launch_nchw_to_nhwc_s2d(grad_output, ws + p.o_go, N, Cout, H, W, compute, s));
+    // the slabs hold (tap, cout) rows: this family reduces them into (Cin, Cout, 2, 2) itself
     int splits;
     const float *bslab;
     TDRN_TRY(launch_conv_wgrad_slabs(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, compute, s, splits, bslab));
@@ -598,9 +532,8 @@ int tdrn_conv_transpose2d_backward_parameters(const float *input, const float *g
 size_t tdrn_conv2d_strided_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
                                            int dilationH, int dilationW, tdrn_dtype compute)
 {
-    ConvS2Plan p;
-    if (convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) != TDRN_OK) return 0;
-    return p.total;
+    ConvTrainPlan p;
+    return convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
 }
 
 int tdrn_conv2d_strided_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W,
@@ -608,17 +541,15 @@ int tdrn_conv2d_strided_forward(const float *input, const float *weight, const f
                                 tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
-    ConvS2Plan p;
-    TDRN_TRY(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
-    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.NpadF, Cin, 9, 1, p.CiPad, compute, s));
-    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadF * 4, s));
-    if (bias) TDRN_HIP_TRY(hipMemcpyAsync(ws + p.o_bias, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
-    return convs2_run(p, ws, false, compute, output, s);
+    TDRN_TRY(conv_train_begin(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
+                              workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
+    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.fwd.Npad, Cin, 9, 1, p.fwd.Cin, compute, s));
+    TDRN_TRY(conv_train_bias(p.fwd, ws + p.o_bias, bias, s));
+    return conv_train_run(p, ws, false, output, s);
 }
 
 int tdrn_conv2d_strided_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W,
@@ -626,18 +557,16 @@ int tdrn_conv2d_strided_backward_input(const float *grad_output, const float *we
                                        tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
-    ConvS2Plan p;
-    TDRN_TRY(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(conv_train_begin(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
+                              workspace_bytes, s));
     // the zero-inserted image: the kernel stores every element of it, zeros included
-    TDRN_TRY(launch_nchw_to_nhwc_dilate2(grad_output, ws + p.o_go, N, Cout, p.g.Ho, p.g.Wo, p.Hd, p.Wd, compute, s));
-    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.NpadD, 9, compute, s));
-    TDRN_TRY(launch_fill_zero(ws + p.o_bias, (size_t)p.NpadD * 4, s));
-    // a stride-1 conv over it: kernel rotated and transposed (the packing above), pad' = 2 - pad
-    return convs2_run(p, ws, true, compute, grad_input, s);
+    TDRN_TRY(launch_nchw_to_nhwc_dilate2(grad_output, ws + p.o_go, N, Cout, p.wg.Ho, p.wg.Wo, p.dgrad.H, p.dgrad.W, compute, s));
+    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.dgrad.Npad, 9, compute, s));
+    TDRN_TRY(conv_train_bias(p.dgrad, ws + p.o_bias, nullptr, s));
+    return conv_train_run(p, ws, true, grad_input, s);
 }
 
 int tdrn_conv2d_strided_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N,
@@ -646,15 +575,14 @@ int tdrn_conv2d_strided_backward_parameters(const float *input, const float *gra
                                             size_t workspace_bytes, void *stream)
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
-    ConvS2Plan p;
-    TDRN_TRY(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
-    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    ConvTrainPlan p;
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    TDRN_TRY(launch_fill_zero(ws + p.o_zero, kZeroPageBytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.CiPad, compute, s));
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.g.Ho * p.g.Wo, p.CoPad, compute, s));
-    return launch_conv_wgrad(p.g, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+    TDRN_TRY(conv_train_begin(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
+                              workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
+    return launch_conv_wgrad(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
 }
 
 size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W)

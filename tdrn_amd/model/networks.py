@@ -6,6 +6,7 @@ batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d)
 and the trainable 2x2 stride-2 transposed conv of the TCB up_layers (ConvTranspose2dFunction / conv_transpose2d / ConvTranspose2d).
 The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
+import collections
 import ctypes as C
 import math
 
@@ -53,6 +54,24 @@ def mobilenet_backbone(c_last=1024):
     return nn.ModuleList([first] + [conv_dw(a, b, s) for a, b, s in plan])
 
 
+def _grad_output(grad_output, shape, op):
+    """what every backward does first: a CUDA grad_output, as contiguous fp32, of the output's shape"""
+    if not grad_output.is_cuda:
+        raise NotImplementedError("%s backward: grad_output must be a CUDA tensor" % op)
+    go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
+    if tuple(go.shape) != tuple(shape):
+        raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(shape)))
+    return go
+
+
+def _workspace(query, args, device, message, *what):
+    """-> (a uint8 workspace of query(*args) bytes, its size); a query of 0 raises `message % what`"""
+    nb = query(*args)
+    if nb == 0:
+        raise RuntimeError(message % what)
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
 def _deform_geometry(x, off, w, stride, padding, dilation, deform_groups):
     (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
     N, Cin, H, W = x.shape
@@ -75,10 +94,8 @@ def _deform_forward(x, off, w, stride, padding, dilation, deform_groups, compute
     dims, out_shape = _deform_geometry(x, off, w, stride, padding, dilation, deform_groups)
     N, Cin, H, W, Cout, kw, kh, sw, sh, pw, ph, dh, dw, G = dims
     dt = _lib.DTYPES[compute]
-    nb = lib.tdrn_deform_conv_workspace_bytes(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G, dt)
-    if nb == 0:
-        raise RuntimeError("deform_conv: shape check failed")
-    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    ws, nb = _workspace(lib.tdrn_deform_conv_workspace_bytes, (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G, dt), x.device,
+                        "deform_conv: shape check failed")
     out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
     _lib.check(lib.tdrn_deform_conv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
                                             _lib.current_stream(x.device)), "tdrn_deform_conv_forward")
@@ -109,21 +126,15 @@ class ConvOffset2dFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_output):
         x, off, w = ctx.saved_tensors
-        if not grad_output.is_cuda:
-            raise NotImplementedError("conv_offset2d backward: grad_output must be a CUDA tensor")
-        lib = _lib.lib()
         dims, out_shape = _deform_geometry(x, off, w, *ctx.conf)
-        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
-        if tuple(go.shape) != out_shape:
-            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
+        go = _grad_output(grad_output, out_shape, "conv_offset2d")
+        lib = _lib.lib()
         need_in, need_off, need_w = ctx.needs_input_grad[:3]
         grad_input = grad_offset = grad_weight = None
         if need_in or need_off or need_w:
             N, Cin, H, W, Cout, kw, kh, sw, sh, pw, ph, dh, dw, G = dims
-            nb = lib.tdrn_deform_conv_backward_workspace_bytes(N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G)
-            if nb == 0:
-                raise RuntimeError("deform_conv backward: shape check failed")
-            ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+            ws, nb = _workspace(lib.tdrn_deform_conv_backward_workspace_bytes, (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, G),
+                                x.device, "deform_conv backward: shape check failed")
             stream = _lib.current_stream(x.device)
         if need_in or need_off:
             gi = torch.zeros_like(x)
@@ -178,8 +189,10 @@ class ConvOffset2d(nn.Module):
                              self.num_deformable_groups)
 
 
-_CONV2D_COVERED = ("square k in {1, 3} at stride 1 with 0 <= pad <= dilation * (k - 1); k = 3 at stride 2 with dilation 1 and "
-                   "0 <= pad <= 2")
+# One trainable conv family of the C ABI (tdrn_hip.h sections i-c, i-f, i-g): `prefix`_workspace_bytes / _forward / _backward_input /
+# _backward_parameters.  geometry(x, w, *geo) -> (the ABI's dims, the output's shape); cout_axis: the weight axis that is Cout;
+# covered / dim_names: the error message of a geometry the library refuses.  `name` is the op's name in messages.
+_ConvFamily = collections.namedtuple("_ConvFamily", "name prefix geometry cout_axis covered dim_names")
 
 
 def _conv2d_family(stride):
@@ -204,24 +217,26 @@ def _conv2d_geometry(x, w, padding, dilation, stride=1):
     return (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw), (N, Cout, Ho, Wo)
 
 
-def _conv2d_workspace(lib, dims, dt, device, family="tdrn_conv2d"):
-    nb = getattr(lib, family + "_workspace_bytes")(*dims, dt)
-    if nb == 0:
-        raise RuntimeError("conv2d: geometry outside what libtdrn_hip covers (%s): "
-                           "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW = %r" % (_CONV2D_COVERED, dims))
-    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+def _conv_transpose2d_geometry(x, w, stride, padding=0, output_padding=0):
+    (sh, sw), (ph, pw), (oh, ow) = _pair(stride), _pair(padding), _pair(output_padding)
+    N, Cin, H, W = x.shape
+    Cw, Cout, kh, kw = w.shape
+    if Cw != Cin:
+        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (Cw, Cin))
+    Ho = (H - 1) * sh - 2 * ph + (kh - 1) + oh + 1
+    Wo = (W - 1) * sw - 2 * pw + (kw - 1) + ow + 1
+    # the C ABI's argument order: N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW
+    return (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, oh, ow, 1, 1), (N, Cout, Ho, Wo)
 
 
-def _conv2d_forward(x, w, b, padding, dilation, compute, stride=1):
-    lib = _lib.lib()
-    family = _conv2d_family(stride)
-    dims, out_shape = _conv2d_geometry(x, w, padding, dilation, stride)
-    dt = _lib.DTYPES[compute]
-    ws, nb = _conv2d_workspace(lib, dims, dt, x.device, family)
-    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-    _lib.check(getattr(lib, family + "_forward")(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
-                                                 _lib.current_stream(x.device)), family + "_forward")
-    return out
+_CONV2D_COVERED = ("square k in {1, 3} at stride 1 with 0 <= pad <= dilation * (k - 1); k = 3 at stride 2 with dilation 1 and "
+                   "0 <= pad <= 2")
+_CONV2D = {prefix: _ConvFamily("conv2d", prefix, _conv2d_geometry, 0, _CONV2D_COVERED,
+                               "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW")
+           for prefix in ("tdrn_conv2d", "tdrn_conv2d_strided")}
+_CONV_TRANSPOSE2D = _ConvFamily("conv_transpose2d", "tdrn_conv_transpose2d", _conv_transpose2d_geometry, 1,
+                                "kernel 2 x 2, stride 2, padding 0, output_padding 0, dilation 1",
+                                "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, opadH, opadW, dilH, dilW")
 
 
 def _conv2d_require_cuda(input, weight, bias):
@@ -230,6 +245,71 @@ def _conv2d_require_cuda(input, weight, bias):
     _lib.require_cuda(weight, "weight")
     if bias is not None:
         _lib.require_cuda(bias, "bias")
+
+
+def _conv_workspace(lib, fam, dims, dt, device):
+    return _workspace(getattr(lib, fam.prefix + "_workspace_bytes"), dims + (dt,), device,
+                      "%s: geometry outside what libtdrn_hip covers (%s): %s = %r", fam.name, fam.covered, fam.dim_names, dims)
+
+
+def _conv_forward(fam, x, w, b, geo, compute):
+    lib = _lib.lib()
+    dims, out_shape = fam.geometry(x, w, *geo)
+    if b is not None and tuple(b.shape) != (out_shape[1],):
+        raise RuntimeError("%s: bias has shape %r, expected (%d,)" % (fam.name, tuple(b.shape), out_shape[1]))
+    dt = _lib.DTYPES[compute]
+    ws, nb = _conv_workspace(lib, fam, dims, dt, x.device)
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    _lib.check(getattr(lib, fam.prefix + "_forward")(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
+                                                     _lib.current_stream(x.device)), fam.prefix + "_forward")
+    return out
+
+
+def _conv_function_forward(ctx, fam, input, weight, bias, geo, compute):
+    """the forward of both conv Functions, after their checks"""
+    x, w = input.contiguous().float(), weight.contiguous().float()
+    b = None if bias is None else bias.contiguous().float()
+    out = _conv_forward(fam, x, w, b, geo, compute)
+    ctx.conf = (fam, geo, compute, bias is not None)
+    ctx.save_for_backward(x, w)
+    return out
+
+
+def _conv_function_backward(ctx, grad_output):
+    """the backward of both conv Functions -> (grad_input, grad_weight, grad_bias), each None where it is not needed"""
+    x, w = ctx.saved_tensors
+    fam, geo, compute, has_bias = ctx.conf
+    dims, out_shape = fam.geometry(x, w, *geo)
+    go = _grad_output(grad_output, out_shape, fam.name)
+    lib = _lib.lib()
+    need_in, need_w = ctx.needs_input_grad[:2]
+    need_b = has_bias and ctx.needs_input_grad[2]
+    grad_input = grad_weight = grad_bias = None
+    if need_in or need_w or need_b:
+        dt = _lib.DTYPES[compute]
+        ws, nb = _conv_workspace(lib, fam, dims, dt, x.device)
+        stream = _lib.current_stream(x.device)
+    if need_in:
+        grad_input = torch.empty_like(x)
+        _lib.check(getattr(lib, fam.prefix + "_backward_input")(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws),
+                                                                nb, stream), fam.prefix + "_backward_input")
+    if need_w or need_b:
+        gw = torch.zeros_like(w)
+        gb = torch.zeros(w.shape[fam.cout_axis], dtype=torch.float32, device=x.device) if need_b else None
+        _lib.check(getattr(lib, fam.prefix + "_backward_parameters")(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
+                                                                     _lib.ptr(ws), nb, stream), fam.prefix + "_backward_parameters")
+        grad_weight = gw if need_w else None
+        grad_bias = gb
+    return grad_input, grad_weight, grad_bias
+
+
+def _conv_dispatch(function, fam, input, weight, bias, geo, compute, *apply_args):
+    """through `function` when something requires grad and grad mode is on; else the forward alone, no grad_fn"""
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return function.apply(input, weight, bias, *apply_args)
+    x, w = input.contiguous().float(), weight.detach().contiguous().float()
+    b = None if bias is None else bias.detach().contiguous().float()
+    return _conv_forward(fam, x, w, b, geo, compute)
 
 
 class Conv2dFunction(torch.autograd.Function):
@@ -247,45 +327,12 @@ class Conv2dFunction(torch.autograd.Function):
         if input.dim() != 4:
             raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
         _conv2d_require_cuda(input, weight, bias)
-        x, w = input.contiguous().float(), weight.contiguous().float()
-        b = None if bias is None else bias.contiguous().float()
-        out = _conv2d_forward(x, w, b, padding, dilation, compute, stride)
-        ctx.conf = (padding, dilation, compute, bias is not None, stride)
-        ctx.save_for_backward(x, w)
-        return out
+        return _conv_function_forward(ctx, _CONV2D[_conv2d_family(stride)], input, weight, bias, (padding, dilation, stride), compute)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        x, w = ctx.saved_tensors
-        if not grad_output.is_cuda:
-            raise NotImplementedError("conv2d backward: grad_output must be a CUDA tensor")
-        padding, dilation, compute, has_bias, stride = ctx.conf
-        lib = _lib.lib()
-        family = _conv2d_family(stride)
-        dims, out_shape = _conv2d_geometry(x, w, padding, dilation, stride)
-        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
-        if tuple(go.shape) != out_shape:
-            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
-        need_in, need_w = ctx.needs_input_grad[:2]
-        need_b = has_bias and ctx.needs_input_grad[2]
-        grad_input = grad_weight = grad_bias = None
-        if need_in or need_w or need_b:
-            dt = _lib.DTYPES[compute]
-            ws, nb = _conv2d_workspace(lib, dims, dt, x.device, family)
-            stream = _lib.current_stream(x.device)
-        if need_in:
-            grad_input = torch.empty_like(x)
-            _lib.check(getattr(lib, family + "_backward_input")(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws),
-                                                                nb, stream), family + "_backward_input")
-        if need_w or need_b:
-            gw = torch.zeros_like(w)
-            gb = torch.zeros(w.shape[0], dtype=torch.float32, device=x.device) if need_b else None
-            _lib.check(getattr(lib, family + "_backward_parameters")(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
-                                                                     _lib.ptr(ws), nb, stream), family + "_backward_parameters")
-            grad_weight = gw if need_w else None
-            grad_bias = gb
-        return grad_input, grad_weight, grad_bias, None, None, None, None
+        return _conv_function_backward(ctx, grad_output) + (None, None, None, None)
 
 
 def conv2d(input, weight, bias=None, padding=0, dilation=1, compute="fp32", stride=1):
@@ -293,15 +340,11 @@ def conv2d(input, weight, bias=None, padding=0, dilation=1, compute="fp32", stri
     bias.  `stride` is an int or a pair: 1, or 2 for a 3x3 kernel at dilation 1 (the `extras` layer of the VGG detectors, the first
     conv of the MobileNet trunk); another stride raises.  With grad mode off, or when nothing requires grad, only the forward runs
     and the output has no grad_fn."""
-    _conv2d_family(stride)                  # a stride the library does not cover raises before anything else
+    fam = _CONV2D[_conv2d_family(stride)]   # a stride the library does not cover raises before anything else
     if input is not None and input.dim() != 4:
         raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
     _conv2d_require_cuda(input, weight, bias)
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return Conv2dFunction.apply(input, weight, bias, padding, dilation, compute, stride)
-    x, w = input.contiguous().float(), weight.detach().contiguous().float()
-    b = None if bias is None else bias.detach().contiguous().float()
-    return _conv2d_forward(x, w, b, padding, dilation, compute, stride)
+    return _conv_dispatch(Conv2dFunction, fam, input, weight, bias, (padding, dilation, stride), compute, padding, dilation, compute, stride)
 
 
 class Conv2d(nn.Module):
@@ -327,40 +370,6 @@ class Conv2d(nn.Module):
         return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute, self.stride)
 
 
-def _conv_transpose2d_geometry(x, w, stride, padding=0, output_padding=0):
-    (sh, sw), (ph, pw), (oh, ow) = _pair(stride), _pair(padding), _pair(output_padding)
-    N, Cin, H, W = x.shape
-    Cw, Cout, kh, kw = w.shape
-    if Cw != Cin:
-        raise RuntimeError("invalid number of input planes, expected: %d, but got: %d" % (Cw, Cin))
-    Ho = (H - 1) * sh - 2 * ph + (kh - 1) + oh + 1
-    Wo = (W - 1) * sw - 2 * pw + (kw - 1) + ow + 1
-    # the C ABI's argument order: N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, output_padH, output_padW, dilationH, dilationW
-    return (N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, oh, ow, 1, 1), (N, Cout, Ho, Wo)
-
-
-def _conv_transpose2d_workspace(lib, dims, dt, device):
-    nb = lib.tdrn_conv_transpose2d_workspace_bytes(*dims, dt)
-    if nb == 0:
-        raise RuntimeError("conv_transpose2d: geometry outside what libtdrn_hip covers (kernel 2 x 2, stride 2, padding 0, "
-                           "output_padding 0, dilation 1): N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, opadH, opadW, dilH, dilW = %r"
-                           % (dims,))
-    return torch.empty(nb, dtype=torch.uint8, device=device), nb
-
-
-def _conv_transpose2d_forward(x, w, b, stride, padding, output_padding, compute):
-    lib = _lib.lib()
-    dims, out_shape = _conv_transpose2d_geometry(x, w, stride, padding, output_padding)
-    if b is not None and tuple(b.shape) != (out_shape[1],):
-        raise RuntimeError("conv_transpose2d: bias has shape %r, expected (%d,)" % (tuple(b.shape), out_shape[1]))
-    dt = _lib.DTYPES[compute]
-    ws, nb = _conv_transpose2d_workspace(lib, dims, dt, x.device)
-    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-    _lib.check(lib.tdrn_conv_transpose2d_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
-                                                 _lib.current_stream(x.device)), "tdrn_conv_transpose2d_forward")
-    return out
-
-
 def _conv_transpose2d_check(input, weight, bias):
     if input is not None and input.dim() != 4:
         raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
@@ -382,54 +391,18 @@ class ConvTranspose2dFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, weight, bias=None, stride=2, padding=0, output_padding=0, compute="fp32"):
         _conv_transpose2d_check(input, weight, bias)
-        x, w = input.contiguous().float(), weight.contiguous().float()
-        b = None if bias is None else bias.contiguous().float()
-        out = _conv_transpose2d_forward(x, w, b, stride, padding, output_padding, compute)
-        ctx.conf = (stride, padding, output_padding, compute, bias is not None)
-        ctx.save_for_backward(x, w)
-        return out
+        return _conv_function_forward(ctx, _CONV_TRANSPOSE2D, input, weight, bias, (stride, padding, output_padding), compute)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        x, w = ctx.saved_tensors
-        if not grad_output.is_cuda:
-            raise NotImplementedError("conv_transpose2d backward: grad_output must be a CUDA tensor")
-        stride, padding, output_padding, compute, has_bias = ctx.conf
-        lib = _lib.lib()
-        dims, out_shape = _conv_transpose2d_geometry(x, w, stride, padding, output_padding)
-        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
-        if tuple(go.shape) != out_shape:
-            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), out_shape))
-        need_in, need_w = ctx.needs_input_grad[:2]
-        need_b = has_bias and ctx.needs_input_grad[2]
-        grad_input = grad_weight = grad_bias = None
-        if need_in or need_w or need_b:
-            dt = _lib.DTYPES[compute]
-            ws, nb = _conv_transpose2d_workspace(lib, dims, dt, x.device)
-            stream = _lib.current_stream(x.device)
-        if need_in:
-            grad_input = torch.empty_like(x)
-            _lib.check(lib.tdrn_conv_transpose2d_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws),
-                                                                nb, stream), "tdrn_conv_transpose2d_backward_input")
-        if need_w or need_b:
-            gw = torch.zeros_like(w)
-            gb = torch.zeros(w.shape[1], dtype=torch.float32, device=x.device) if need_b else None
-            _lib.check(lib.tdrn_conv_transpose2d_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
-                                                                     _lib.ptr(ws), nb, stream),
-                       "tdrn_conv_transpose2d_backward_parameters")
-            grad_weight = gw if need_w else None
-            grad_bias = gb
-        return grad_input, grad_weight, grad_bias, None, None, None, None
+        return _conv_function_backward(ctx, grad_output) + (None, None, None, None)
 
 
 def _conv_transpose2d(input, weight, bias, stride, padding, output_padding, compute):
     _conv_transpose2d_check(input, weight, bias)
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return ConvTranspose2dFunction.apply(input, weight, bias, stride, padding, output_padding, compute)
-    x, w = input.contiguous().float(), weight.detach().contiguous().float()
-    b = None if bias is None else bias.detach().contiguous().float()
-    return _conv_transpose2d_forward(x, w, b, stride, padding, output_padding, compute)
+    return _conv_dispatch(ConvTranspose2dFunction, _CONV_TRANSPOSE2D, input, weight, bias, (stride, padding, output_padding), compute,
+                          stride, padding, output_padding, compute)
 
 
 def conv_transpose2d(input, weight, bias=None, stride=2, compute="fp32"):
@@ -488,11 +461,8 @@ def _batch_norm_check(input, running_mean, running_var, weight, bias, training):
 
 
 def _batch_norm_workspace(lib, dims, device):
-    nb = lib.tdrn_batch_norm_workspace_bytes(*dims)
-    if nb == 0:
-        raise RuntimeError("batch_norm: shape outside what libtdrn_hip covers (positive sizes, fewer than 2^31 elements): "
-                           "N, C, H, W = %r" % (dims,))
-    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+    return _workspace(lib.tdrn_batch_norm_workspace_bytes, dims, device,
+                      "batch_norm: shape outside what libtdrn_hip covers (positive sizes, fewer than 2^31 elements): N, C, H, W = %r", dims)
 
 
 def _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu):
@@ -531,12 +501,8 @@ class BatchNormFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_output):
         x, w, b, save_mean, save_invstd = ctx.saved_tensors
-        if not grad_output.is_cuda:
-            raise NotImplementedError("batch_norm backward: grad_output must be a CUDA tensor")
+        go = _grad_output(grad_output, x.shape, "batch_norm")
         training, relu = ctx.conf
-        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
-        if go.shape != x.shape:
-            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(x.shape)))
         need_in, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         grad_input = gw = gb = None
         if need_in or need_w or need_b:
@@ -668,11 +634,7 @@ class MaxPool2dFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_output):
         code, = ctx.saved_tensors
-        if not grad_output.is_cuda:
-            raise NotImplementedError("max_pool2d backward: grad_output must be a CUDA tensor")
-        go = grad_output.float().contiguous()          # (y.sum().backward() hands in a stride-0 tensor)
-        if go.shape != code.shape:
-            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(code.shape)))
+        go = _grad_output(grad_output, code.shape, "max_pool2d")
         grad_input = None
         if ctx.needs_input_grad[0]:
             k, s, p, ceil, _, _ = ctx.conf
@@ -752,11 +714,7 @@ class L2NormFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_output):
         x, w, norm = ctx.saved_tensors
-        if not grad_output.is_cuda:
-            raise NotImplementedError("l2norm backward: grad_output must be a CUDA tensor")
-        go = grad_output.float().contiguous()
-        if go.shape != x.shape:
-            raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(go.shape), tuple(x.shape)))
+        go = _grad_output(grad_output, x.shape, "l2norm")
         need_in, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         grad_input = gw = None
         if need_in or need_w:

@@ -1,6 +1,6 @@
 """Which conv_igemm.hip variant each case of test_gpu_conv_grad.py reaches, without a GPU.
 
-conv2d's forward and input gradient always run on conv_igemm.hip (conv2d_args: an fp32 result and KOFF_HEAD3X3, which every other
+conv2d's forward and input gradient always run on conv_igemm.hip (conv_train_args: an fp32 result and KOFF_HEAD3X3, which every other
 kernel's *_takes refuses).  Inside it four host-side rules pick the code that runs; they are restated here in plain Python:
 
   conv_n_pad            Npad = 32 | 64 | the next multiple of 128
@@ -92,7 +92,7 @@ def wgrad_slab_bytes(case):
 
 
 def workspace_bytes(case, mode):
-    """conv2d_plan's layout (api.hip), from the restated rules"""
+    """conv_train_layout on conv2d_plan's two launches (api.hip), from the restated rules"""
     N, Cin, H, W, Cout, k, pad, dil = G.CASES[case]
     Ho, Wo = G._out_hw(case)
     es = ES[mode]

@@ -205,7 +205,7 @@ def wgrad_splits(case):
 
 
 def workspace_bytes(case, mode):
-    """convs2_plan's layout (api.hip), from the restated rules"""
+    """conv_train_layout on convs2_plan's two launches (api.hip), from the restated rules"""
     N, Cin, H, W, Cout, pad, Ho, Wo, Hd, Wd = geometry(case)
     es = ES[mode]
     f, d = problem(case, False), problem(case, True)

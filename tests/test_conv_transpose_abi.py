@@ -170,7 +170,7 @@ def wgrad_splits(case):
 
 
 def workspace_bytes(case, mode):
-    """convt2d_plan's layout (api.hip), from the restated rules"""
+    """conv_train_layout on convt2d_plan's two launches (api.hip), from the restated rules"""
     N, Cin, H, W, Cout = G.CASES[case]
     es, C4 = ES[mode], 4 * cpad(Cout)
     f, d = problem(case, False), problem(case, True)

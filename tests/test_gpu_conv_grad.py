@@ -15,11 +15,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tdrn_amd import _lib
+from _conv_train_harness import C_ACC, DEV, DT, NAMES, Guarded, check  # noqa: F401
+from _conv_train_harness import Abi as _Abi, bits_equal as _bits_equal, round_to as _round
 from tdrn_amd.model import networks
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 torch.set_num_threads(min(16, torch.get_num_threads()))      # (the float64 references of the deep_* cases: the GPU hosts' threads oversubscribe)
 
 # N, Cin, H, W, Cout, k, pad, dil
@@ -50,8 +50,6 @@ CASES = {
 AUTOGRAD_CASES = [c for c in CASES if c != "deep_fwd_scalar"]
 # seeds: the first twelve cases keep the inputs they always had (their rank among themselves), the later ones follow in table order
 SEED_ORDER = sorted(list(CASES)[:12]) + list(CASES)[12:]
-DT = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
-C_ACC = {"bf16": 2e-6, "fp16": 4e-5}
 
 
 def _dims(case):
@@ -76,10 +74,6 @@ def _inputs(case):
     return x, w, b, go
 
 
-def _round(t, mode):
-    return t if DT[mode] is None else t.to(DT[mode]).float()
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(case, mode):
     """float64 CPU autograd on the inputs as the op uses them -> ((y, gx, gw, gb), (Sy, Sgx, Sgw, Sgb)); computed once, never changed"""
@@ -96,60 +90,18 @@ def _reference(case, mode):
 
 
 def _check(case, mode, names, got):
-    ref, S = _reference(case, mode)
-    idx = {"output": 0, "grad_input": 1, "grad_weight": 2, "grad_bias": 3}
-    for name, g in zip(names, got):
-        r, s = ref[idx[name]], S[idx[name]]
-        d = (g.detach().cpu().double() - r).abs()
-        assert torch.isfinite(d).all(), "%s %s %s: non-finite values" % (case, mode, name)
-        if mode == "fp32":
-            bound = 1e-4 * max(1.0, float(r.abs().max()))
-            print("%s %s %-11s max|d| %.3e  bound %.3e" % (case, mode, name, float(d.max()), bound))
-            assert float(d.max()) <= bound, (case, mode, name, float(d.max()), bound)
-        else:
-            ratio = float((d / s.clamp_min(1e-300)).max())
-            print("%s %s %-11s max|d|/S %.3e  c %.1e" % (case, mode, name, ratio, C_ACC[mode]))
-            assert bool((d <= C_ACC[mode] * s).all()), (case, mode, name, ratio, C_ACC[mode])
+    check(_reference, case, mode, names, got)
 
 
-class Abi(object):
+def Abi(case, mode):
     """the four C entries on plain device buffers"""
-
-    def __init__(self, case, mode):
-        self.lib, self.dims, self.dt = _lib.lib(), _dims(case), _lib.DTYPES[mode]
-        self.nb = self.lib.tdrn_conv2d_workspace_bytes(*self.dims, self.dt)
-        assert self.nb > 0
-        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=DEV)
-        self.x, self.w, self.b, self.go = (t.to(DEV) for t in _inputs(case))
-        self.st = _lib.current_stream(DEV)
-
-    def forward(self, out, bias=True):
-        _lib.check(self.lib.tdrn_conv2d_forward(_lib.ptr(self.x), _lib.ptr(self.w), _lib.ptr(self.b if bias else None), _lib.ptr(out),
-                                                *self.dims, self.dt, _lib.ptr(self.ws), self.nb, self.st))
-        return out
-
-    def backward_input(self, gi):
-        _lib.check(self.lib.tdrn_conv2d_backward_input(_lib.ptr(self.go), _lib.ptr(self.w), _lib.ptr(gi), *self.dims, self.dt,
-                                                       _lib.ptr(self.ws), self.nb, self.st))
-        return gi
-
-    def backward_parameters(self, gw, gb, scale=1.0):
-        _lib.check(self.lib.tdrn_conv2d_backward_parameters(_lib.ptr(self.x), _lib.ptr(self.go), _lib.ptr(gw), _lib.ptr(gb), *self.dims,
-                                                            scale, self.dt, _lib.ptr(self.ws), self.nb, self.st))
-        return gw, gb
-
-    def all(self):
-        out = self.forward(torch.full_like(self.go, float("nan")))
-        gi = self.backward_input(torch.full_like(self.x, float("nan")))
-        gw, gb = self.backward_parameters(torch.zeros_like(self.w), torch.zeros_like(self.b))
-        torch.cuda.synchronize()
-        return out, gi, gw, gb
+    return _Abi("tdrn_conv2d", _dims(case), _inputs(case), mode)
 
 
 @pytest.mark.parametrize("mode", list(DT))
 @pytest.mark.parametrize("case", list(CASES))
 def test_conv2d_abi_matches_float64_autograd(case, mode):
-    _check(case, mode, ("output", "grad_input", "grad_weight", "grad_bias"), Abi(case, mode).all())
+    _check(case, mode, NAMES, Abi(case, mode).all())
 
 
 @pytest.mark.parametrize("mode", list(DT))
@@ -160,7 +112,7 @@ def test_conv2d_autograd_matches_float64_autograd(case, mode):
     x, w, b = (t.requires_grad_(True) for t in (x, w, b))
     y = networks.conv2d(x, w, b, padding=pad, dilation=dil, compute=mode)
     y.backward(go)
-    _check(case, mode, ("output", "grad_input", "grad_weight", "grad_bias"), (y, x.grad, w.grad, b.grad))
+    _check(case, mode, NAMES, (y, x.grad, w.grad, b.grad))
 
 
 def test_conv2d_parameter_gradients_accumulate_and_the_rest_is_overwritten():
@@ -188,37 +140,8 @@ def test_conv2d_is_bitwise_reproducible(mode):
         # other work on the device in between must not change the arithmetic
         Abi("ragged_tiles", mode).all()
         second = a.all()
-        for name, p, q in zip(("output", "grad_input", "grad_weight", "grad_bias"), first, second):
-            assert torch.equal(p.view(torch.int32), q.view(torch.int32)), (case, name)
-
-
-SENTINEL = 0x7FBADBAD
-GUARD = 4096
-
-
-class Guarded(object):
-    """`nbytes` of device memory that start `offset` bytes behind a 256-byte boundary, between two guard bands of a NaN pattern no
-    kernel computes (the pattern of test_gpu_caller_memory.py)"""
-
-    def __init__(self, shape=None, offset=0, nbytes=None, init=None):
-        n = int(nbytes) if nbytes is not None else 4 * int(torch.Size(shape).numel())
-        total = 2 * GUARD + 256 + offset + n
-        self.raw = torch.full(((total + 3) // 4,), SENTINEL, dtype=torch.int32, device=DEV).view(torch.uint8)
-        base = (-self.raw.data_ptr()) % 256 + GUARD
-        self.lo, self.hi = base + offset, base + offset + n
-        body = self.raw[self.lo:self.hi]
-        self.t = body if shape is None else body.view(torch.float32).view(shape)
-        if init is not None:
-            self.t.copy_(init)
-
-    def check(self, what, full=True):
-        torch.cuda.synchronize()
-        words = self.raw.view(torch.int32)
-        assert self.lo % 4 == 0 and self.hi % 4 == 0
-        assert bool((words[:self.lo // 4] == SENTINEL).all()), "%s: bytes in front of the buffer were written" % what
-        assert bool((words[self.hi // 4:] == SENTINEL).all()), "%s: bytes behind the end of the buffer were written" % what
-        if full:
-            assert int((words[self.lo // 4:self.hi // 4] == SENTINEL).sum()) == 0, "%s: elements never written" % what
+        for name, p, q in zip(NAMES, first, second):
+            assert _bits_equal(p, q), (case, name)
 
 
 @pytest.mark.parametrize("mode", ["bf16", "fp32"])
@@ -237,9 +160,9 @@ def test_conv2d_writes_only_the_callers_buffers(case, mode):
     a.forward(out.t)
     a.backward_input(gi.t)
     a.backward_parameters(gw.t, gb.t)
-    for name, g, w in zip(("output", "grad_input", "grad_weight", "grad_bias"), (out, gi, gw, gb), want):
+    for name, g, w in zip(NAMES, (out, gi, gw, gb), want):
         g.check("%s %s %s" % (case, mode, name))
-        assert torch.equal(g.t.contiguous().view(torch.int32), w.view(torch.int32)), name
+        assert _bits_equal(g.t, w), name
     ws.check("%s %s workspace" % (case, mode), full=False)
 
 
