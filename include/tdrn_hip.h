@@ -299,6 +299,49 @@ TDRN_API int tdrn_conv2d_strided_backward_parameters(const float *input, const f
                                                      void *stream);
 
 /* ========================================================================================
+ * (i-h) Depthwise 3x3 conv2d with gradients -- what nn.Conv2d(c, c, 3, s, 1, groups=c) + autograd give the reference's training loop
+ *     (conv_dw, model/networks.py:736-745: the thirteen blocks of the MobileNet trunk and the two of its `extras`): forward, input
+ *     gradient, weight / bias gradient, at stride 1 and 2.
+ *   input (N, C, H, W), weight (C, 1, 3, 3) (torch's layout for groups = C, channel multiplier 1), bias (C) or NULL, output /
+ *   grad_output (N, C, Ho, Wo) with Ho = (H + 2 pad - 3) / stride + 1 (floor) and Wo likewise, grad_input like input, grad_weight like
+ *   weight, grad_bias (C) or NULL: all fp32, contiguous, device, on any 4-byte boundary.  The kernels work on the NCHW planes
+ *   directly: no layout conversion, no repacked weight.
+ *   forward:             output[n][c][ho][wo] = bias[c] + sum_{i,j} input[n][c][s ho - 1 + i][s wo - 1 + j] weight[c][0][i][j], nine fmaf in
+ *                        the order (0,0) (0,1) .. (2,2) from the bias (or +0); a tap in the padding is skipped.  OVERWRITTEN.
+ *   backward_input:      grad_input[n][c][h][w] = sum over the taps (i, j) for which h + 1 - i and w + 1 - j are multiples of the stride
+ *                        with quotients inside Ho x Wo, of grad_output[n][c][(h + 1 - i) / s][(w + 1 - j) / s] weight[c][0][i][j], in
+ *                        the same tap order from +0.  OVERWRITTEN; an input row or column that no output pixel touches gets exactly 0.
+ *   backward_parameters: grad_weight[c][0][i][j] += scale * sum_{n,ho,wo} grad_output[n][c][ho][wo] input[n][c][s ho - 1 + i][s wo - 1 + j],
+ *                        grad_bias[c] += scale * sum grad_output[.][c][.][.] (NULL: not computed).  K = N*Ho*Wo is cut into S ranges
+ *                        of ceil(K / S') elements, S' = max(1, min(ceil(2048 / C), ceil(K / 1024))), S = the ranges that are not
+ *                        empty; the ranges are summed in range order.
+ *   `compute` must be TDRN_F32: the op is bandwidth-bound and has no 16-bit mode.
+ *   All outputs are bitwise reproducible run to run, and the same for caller buffers on any 4-byte boundary: nothing on this path
+ *   uses float atomics, and S depends on the geometry alone.
+ *   Geometry (the argument order is the query's in all four functions): kH = kW = 3, dH = dW in {1, 2}, padH = padW = 1, dilation 1;
+ *   any N, C, H, W >= 1 with N*C*H*W below 2^31.
+ *   The query returns 40 C S bytes rounded up to 256: the partial sums of backward_parameters.  One query serves all three entries
+ *   (forward and backward_input check the workspace and do not use it).
+ *   Errors, all decided before any launch, in this order: a null tensor pointer -> TDRN_E_ARG; k <= 0, stride / dilation <= 0, a
+ *   negative pad, N / C / H / W <= 0, an output smaller than 1 x 1 -> query 0 and TDRN_E_SHAPE; `compute` outside 0..2 -> TDRN_E_ARG;
+ *   any other well-formed geometry (other kernel sizes, stride 3, per-axis stride or pad, pad 0 or 2, dilation 2, TDRN_BF16 /
+ *   TDRN_F16, N*C*H*W of 2^31 or more) -> query 0 and TDRN_E_UNSUPPORTED; a null workspace or one below the query ->
+ *   TDRN_E_WORKSPACE.  No allocation and no host synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_dwconv2d_workspace_bytes(int N, int C, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW,
+                                              int dilationH, int dilationW, tdrn_dtype compute);
+TDRN_API int tdrn_dwconv2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int C, int H,
+                                   int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                   tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_dwconv2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int C, int H,
+                                          int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                          tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_dwconv2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias,
+                                               int N, int C, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW,
+                                               int dilationH, int dilationW, float scale, tdrn_dtype compute, void *workspace,
+                                               size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

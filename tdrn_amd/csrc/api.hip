@@ -1,5 +1,6 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g) and (ii) (section (iii) is in net.hip).
-// Sections (i-c), (i-f) and (i-g), the trainable conv families, share one plan, one workspace layout and one runner (ConvTrainPlan).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g), (i-h) and (ii) (section (iii) is in net.hip).
+// Sections (i-c), (i-f) and (i-g), the trainable dense conv families, share one plan, one workspace layout and one runner
+// (ConvTrainPlan); the depthwise conv (i-h) works on NCHW planes and has its own small plan (DwConvPlan).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -249,6 +250,36 @@ int convs2_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, 
     conv_train_dense_out(f);
     conv_train_dense_out(d);
     conv_train_layout(p, dtype);
+    return TDRN_OK;
+}
+
+// depthwise 3x3 conv (section i-h): fp32 NCHW planes straight through dwconv_train.hip, no ConvTrainPlan.  The workspace holds the
+// weight gradient's partials and nothing else; one size serves the three entries.
+struct DwConvPlan {
+    int stride, Ho, Wo;
+    size_t total;
+};
+
+int dwconv2d_plan(int N, int C, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype, DwConvPlan &p)
+{
+    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
+    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
+    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    // what the kernels cover: k = 3, one stride of 1 or 2 for both axes, pad 1, dilation 1, fp32 (the op is bandwidth-bound, and the
+    // inference engine keeps depthwise weights in fp32 in its 16-bit plans too)
+    if (kH != 3 || kW != 3 || dH != dW || dH > 2 || padH != 1 || padW != 1 || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
+    if (dtype != TDRN_F32) return TDRN_E_UNSUPPORTED;
+    // N C H W below 2^31 (every factor is >= 1, so a partial product at the limit settles it before anything can overflow)
+    long long elems = 1;
+    for (int f : {N, C, H, W}) {
+        elems *= f;
+        if (elems >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    }
+    p.stride = dH;
+    p.Ho = (H - 1) / dH + 1;
+    p.Wo = (W - 1) / dW + 1;
+    p.total = dwconv_workspace_bytes(N, C, p.Ho, p.Wo);
     return TDRN_OK;
 }
 
@@ -583,6 +614,47 @@ int tdrn_conv2d_strided_backward_parameters(const float *input, const float *gra
     TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
     TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
     return launch_conv_wgrad(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+}
+
+size_t tdrn_dwconv2d_workspace_bytes(int N, int C, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                     int dilationW, tdrn_dtype compute)
+{
+    DwConvPlan p;
+    return dwconv2d_plan(N, C, H, W, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
+}
+
+int tdrn_dwconv2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int C, int H, int W, int kH,
+                          int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute, void *workspace,
+                          size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !output) return TDRN_E_ARG;
+    DwConvPlan p;
+    TDRN_TRY(dwconv2d_plan(N, C, H, W, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    return launch_dwconv_forward(input, weight, bias, output, N, C, H, W, p.stride, p.Ho, p.Wo, (hipStream_t)stream);
+}
+
+int tdrn_dwconv2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int C, int H, int W, int kH,
+                                 int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute,
+                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
+    DwConvPlan p;
+    TDRN_TRY(dwconv2d_plan(N, C, H, W, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    return launch_dwconv_backward_input(grad_output, weight, grad_input, N, C, H, W, p.stride, p.Ho, p.Wo, (hipStream_t)stream);
+}
+
+int tdrn_dwconv2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N, int C,
+                                      int H, int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                      float scale, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
+    DwConvPlan p;
+    TDRN_TRY(dwconv2d_plan(N, C, H, W, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p));
+    if (!workspace || workspace_bytes < p.total) return TDRN_E_WORKSPACE;
+    return launch_dwconv_backward_parameters(input, grad_output, grad_weight, grad_bias, N, C, H, W, p.stride, p.Ho, p.Wo, scale, workspace,
+                                             (hipStream_t)stream);
 }
 
 size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W)

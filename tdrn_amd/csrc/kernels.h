@@ -281,6 +281,19 @@ int launch_convt_wgrad_reduce(const float *slab, const float *bias_slab, float *
 // (Hd = 2 Ho - 1 or 2 Ho, the caller's H + 2 pad - 2; Wd likewise), D[2 ho][2 wo] = go[ho][wo], every other element zero (odd rows and
 // columns, padded channels).  The kernel writes EVERY element of D itself.
 int launch_nchw_to_nhwc_dilate2(const float *in, void *out, int N, int Cout, int Ho, int Wo, int Hd, int Wd, int dtype, hipStream_t s);
+// Depthwise 3x3 conv with gradients, pad 1, stride 1 | 2, fp32 NCHW throughout (dwconv_train.hip; tdrn_hip.h section i-h).  weight
+// (C, 1, 3, 3); Ho x Wo is the caller's (H + 2 - 3) / stride + 1.  The weight gradient cuts K = N Ho Wo into `splits` ranges of per_split
+// elements, from (N, C, Ho, Wo) alone; the workspace holds its partials [C][splits][10] (nine taps and the bias), padded to 256 bytes
+void dwconv_wgrad_splits(int N, int C, int Ho, int Wo, int &splits, long long &per_split);
+size_t dwconv_workspace_bytes(int N, int C, int Ho, int Wo);
+// y is overwritten; bias (C) or null
+int launch_dwconv_forward(const float *x, const float *w, const float *bias, float *y, int N, int C, int H, int W, int stride, int Ho, int Wo,
+                          hipStream_t s);
+// gx is overwritten, rows and columns that no output touches with 0
+int launch_dwconv_backward_input(const float *go, const float *w, float *gx, int N, int C, int H, int W, int stride, int Ho, int Wo, hipStream_t s);
+// gw += scale * its sums, gb (or null) += scale * sum go; merged in split order, no atomics
+int launch_dwconv_backward_parameters(const float *x, const float *go, float *gw, float *gb, int N, int C, int H, int W, int stride, int Ho,
+                                      int Wo, float scale, void *ws, hipStream_t s);
 // BatchNorm2d with an optional fused ReLU, fp32 NCHW (batch_norm.hip; tdrn_hip.h section i-d).  Every pass cuts a channel's N*HW values
 // into `splits` pieces of per_split elements, from (N, C, HW) alone; the workspace holds the per-(channel, split) records of the reducing
 // passes and the backward's per-channel sums: 12 C splits + 8 C bytes

@@ -1,12 +1,15 @@
 """Shared host-side shell of the model mirrors: an nn.Module that owns the reference's parameter
 layout (so `load_state_dict(torch.load(...))`, `.eval()`, `.cuda()` keep working) while `forward`
-hands the batch to libtdrn_hip.so through NetEngine.  Inference only."""
+hands the batch to libtdrn_hip.so through NetEngine (inference), and TrainWalk: what the forward_train of the dual-refinement
+models is made of, on the library's differentiable ops."""
 import os
 
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from ..engine import NetEngine
+from . import networks
 
 
 class EngineModule(nn.Module):
@@ -158,3 +161,102 @@ class EngineModule(nn.Module):
             print("Finished!")
         else:
             print("Sorry only .pth and .pkl files supported.")
+
+
+def _flatten(layers):
+    """the holders of a list, with every nn.Sequential among them replaced by its own (flattened) holders"""
+    out = []
+    for m in layers:
+        out.extend(_flatten(m) if isinstance(m, nn.Sequential) else [m])
+    return out
+
+
+def _is_depthwise3x3(m):
+    return (m.groups == m.in_channels == m.out_channels and tuple(m.kernel_size) == (3, 3) and tuple(m.padding) == (1, 1)
+            and tuple(m.dilation) == (1, 1))
+
+
+class TrainWalk(object):
+    """What the forward_train of both dual-refinement models is made of: the walk over a list of parameter holders and the shared head,
+    on the library's differentiable ops.  The ops are looked up on `networks` at call time."""
+
+    def _bn_relu(self, bn, x):
+        if bn.momentum is None:
+            raise NotImplementedError("forward_train: BatchNorm2d(momentum=None) needs a host-side batch count; use networks.BatchNorm2d")
+        if self.training and bn.track_running_stats:
+            bn.num_batches_tracked.add_(1)            # on the device: no host read, no synchronisation
+        return networks.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training, bn.momentum, bn.eps,
+                                   relu=True)
+
+    def _walk(self, layers, x, compute, taps=()):
+        """A list of nn.Conv2d [+ nn.BatchNorm2d] [+ nn.ReLU] and nn.MaxPool2d holders, in order, nested nn.Sequentials flattened ->
+        (output, [the output behind conv number n (1-based, activation included) for n in taps]).  A dense conv goes to conv2d with
+        `compute`; a depthwise 3x3 conv with pad 1 (conv_dw's first layer) goes to depthwise_conv2d, which is fp32."""
+        layers, kept, n_conv, i = _flatten(layers), [], 0, 0
+        while i < len(layers):
+            m = layers[i]
+            i += 1
+            if isinstance(m, nn.MaxPool2d):
+                x = networks.max_pool2d(x, m.kernel_size, m.stride, m.padding, m.ceil_mode)
+                continue
+            if not isinstance(m, nn.Conv2d) or not (m.groups == 1 or _is_depthwise3x3(m)):
+                raise NotImplementedError("forward_train: no differentiable op for %r" % (m,))
+            if m.groups == 1:
+                x = networks.conv2d(x, m.weight, m.bias, m.padding, m.dilation, compute, m.stride)
+            else:
+                x = networks.depthwise_conv2d(x, m.weight, m.bias, m.stride, m.padding)
+            if i < len(layers) and isinstance(layers[i], nn.BatchNorm2d):
+                x = self._bn_relu(layers[i], x)        # the nn.ReLU behind it is fused
+                i += 2 if i + 1 < len(layers) and isinstance(layers[i + 1], nn.ReLU) else 1
+            elif i < len(layers) and isinstance(layers[i], nn.ReLU):
+                x = torch.relu(x)
+                i += 1
+            n_conv += 1
+            if n_conv in taps:
+                kept.append(x)
+        return x, kept
+
+    def _train_input(self, x):
+        """the checks and the engine mark every forward_train starts with -> the input as fp32"""
+        if x.dim() != 4:
+            raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(x.dim()))
+        _lib.require_cuda(x, "input")
+        object.__setattr__(self, "_dirty", True)
+        return x.float()
+
+    def _head_train(self, arm_sources, x, compute):
+        """ARM loc / offsets, last_layer_trans, the TCB pyramid and the deformable heads (add_refine_head's modules, with or without
+        biases) from the four ARM sources and the last feature map x -> forward_train's 4-tuple"""
+        B = x.size(0)
+        conv = lambda m, t, pad: networks.conv2d(t, m.weight, m.bias, pad, 1, compute)
+        arm_loc, off1, off2 = [], [], []
+        for s, a in enumerate(arm_sources):
+            loc_a = conv(self.arm_loc[s], a, 1)
+            arm_loc.append(loc_a.permute(0, 2, 3, 1).contiguous().view(B, -1))
+            off1.append(conv(self.offset[s], loc_a, 0))
+            if self.multihead:
+                off2.append(conv(self.offset2[s], loc_a, 0))
+        x, _ = self._walk(self.last_layer_trans, x, compute)
+        odm_sources = [x]
+        trans = [self._walk(self.trans_layers[s], arm_sources[s], compute)[0] for s in range(3)]
+        trans.reverse()
+        for i, t in enumerate(trans):
+            up = self.up_layers[i]
+            u = torch.relu(networks.conv_transpose2d(x, up.weight, up.bias, 2, compute) + t)
+            x = torch.relu(conv(self.latent_layers[i], u, 1))
+            odm_sources.append(x)
+        odm_sources.reverse()
+        odm_loc, odm_conf = [], []
+        for s, ob in enumerate(odm_sources):
+            heads = [(self.odm_loc[s], self.odm_conf[s], off1[s])]
+            if self.multihead:
+                heads.append((self.odm_loc_2[s], self.odm_conf_2[s], off2[s]))
+            l = c = None
+            for hl, hc, off in heads:
+                dl, dc = (networks.conv_offset2d(ob, off, h.weight, h.stride, h.padding, h.dilation, h.num_deformable_groups, compute)
+                          for h in (hl, hc))
+                l, c = (dl, dc) if l is None else (l + dl, c + dc)
+            odm_loc.append(l.permute(0, 2, 3, 1).contiguous().view(B, -1))
+            odm_conf.append(c.permute(0, 2, 3, 1).contiguous().view(B, -1))
+        return (torch.cat(arm_loc, 1).view(B, -1, 4), None, torch.cat(odm_loc, 1).view(B, -1, 4),
+                torch.cat(odm_conf, 1).view(B, -1, self.num_classes))

@@ -1,10 +1,13 @@
 """Dual-refinement detector on MobileNet-v1: drop-in for model/dualrefinedet_mobilenet.py
-(RefineSSD :8-125, forward :127-199, build_net :210-214).  All head / TCB convs are bias-free."""
+(RefineSSD :8-125, forward :127-199, build_net :210-214).  All head / TCB convs are bias-free.  `net(x)` is the inference engine;
+`net.forward_train(x)` computes the phase-'train' outputs from the module's own fp32 parameters through the library's differentiable
+ops (_base.TrainWalk), so that `loss.backward()` fills their .grad."""
 import torch.nn as nn
 
 from .. import _lib
 from ..layers.modules.l2norm import L2Norm
-from ._base import EngineModule
+from ._base import EngineModule, TrainWalk
+from . import networks
 from .dualrefinedet_vggbn import add_refine_head
 from .networks import conv_dw, mobilenet_backbone
 
@@ -13,7 +16,7 @@ def extras_block(cin):
     return nn.Sequential(nn.Conv2d(cin, 256, 1), nn.BatchNorm2d(256), nn.ReLU(inplace=True), conv_dw(256, 512, 2))
 
 
-class RefineSSD(EngineModule):
+class RefineSSD(EngineModule, TrainWalk):
     def __init__(self, size, num_classes=21, phase='train', def_groups=1, multihead=False):
         super(RefineSSD, self).__init__()
         self.num_classes, self.size, self.phase = num_classes, size, phase
@@ -32,6 +35,23 @@ class RefineSSD(EngineModule):
         r = self.engine_for(x).forward(x)
         conf = r["conf"] if self.phase == 'test' else r["conf"].view(x.size(0), -1, self.num_classes)
         return (r["arm_loc"], None, r["odm_loc"], conf)
+
+    def forward_train(self, x, compute="fp32"):
+        """-> (arm_loc (B, P, 4), None, odm_loc (B, P, 4), conf (B, P, num_classes) raw logits): the phase-'train' outputs of
+        forward (the reference's :127-199), computed from this module's fp32 parameters with an autograd graph.  BatchNorm runs in
+        the module's mode (self.training: batch statistics, running buffers updated with each layer's momentum; else the running
+        buffers).  `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the dense conv-type ops and the deformable heads;
+        the depthwise convs, BatchNorm and L2Norm are fp32.  The engine's packed weights are marked stale, so net(x) after an
+        optimizer step re-packs by itself."""
+        x = self._train_input(x)
+        x, _ = self._walk(self.backbone[:12], x, compute)
+        arm_sources = [networks.l2norm(x, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps)]
+        x, _ = self._walk(self.backbone[12:], x, compute)
+        arm_sources.append(networks.l2norm(x, self.L2Norm_5_3.weight, self.L2Norm_5_3.eps))
+        for block in self.extras:
+            x, _ = self._walk(block, x, compute)
+            arm_sources.append(x)
+        return self._head_train(arm_sources, x, compute)
 
 
 def build_net(phase, size=320, num_classes=21, def_groups=1, multihead=False):

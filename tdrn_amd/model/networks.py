@@ -3,7 +3,8 @@ conv_dw :736-745) and the deformable-conv module surface (conv_offset2d :600-615
 ConvOffset2dFunction :617-697, ConvOffset2d :699-733), plus the trainable dense conv (Conv2dFunction / conv2d / Conv2d: what
 nn.Conv2d and autograd give the reference's training loop; stride 1, and 3x3 at stride 2) and the trainable batch norm with a fused ReLU (BatchNormFunction /
 batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d) and L2Norm (L2NormFunction / l2norm / L2Norm),
-and the trainable 2x2 stride-2 transposed conv of the TCB up_layers (ConvTranspose2dFunction / conv_transpose2d / ConvTranspose2d).
+and the trainable 2x2 stride-2 transposed conv of the TCB up_layers (ConvTranspose2dFunction / conv_transpose2d / ConvTranspose2d),
+and the trainable depthwise 3x3 conv of conv_dw (DepthwiseConv2dFunction / depthwise_conv2d / DepthwiseConv2d).
 The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import collections
@@ -189,7 +190,7 @@ class ConvOffset2d(nn.Module):
                              self.num_deformable_groups)
 
 
-# One trainable conv family of the C ABI (tdrn_hip.h sections i-c, i-f, i-g): `prefix`_workspace_bytes / _forward / _backward_input /
+# One trainable conv family of the C ABI (tdrn_hip.h sections i-c, i-f, i-g, i-h): `prefix`_workspace_bytes / _forward / _backward_input /
 # _backward_parameters.  geometry(x, w, *geo) -> (the ABI's dims, the output's shape); cout_axis: the weight axis that is Cout;
 # covered / dim_names: the error message of a geometry the library refuses.  `name` is the op's name in messages.
 _ConvFamily = collections.namedtuple("_ConvFamily", "name prefix geometry cout_axis covered dim_names")
@@ -436,6 +437,82 @@ class ConvTranspose2d(nn.Module):
 
     def forward(self, input):
         return _conv_transpose2d(input, self.weight, self.bias, self.stride, self.padding, self.output_padding, self.compute)
+
+
+def _depthwise_geometry(x, w, stride, padding):
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    N, Ch, H, W = x.shape
+    if w.dim() != 4 or w.shape[0] != Ch or w.shape[1] != 1:
+        raise RuntimeError("depthwise_conv2d: weight has shape %r, expected (%d, 1, kH, kW) for an input of %d channels"
+                           % (tuple(w.shape), Ch, Ch))
+    kh, kw = w.shape[2:]
+    Ho = (H + 2 * ph - kh) // sh + 1
+    Wo = (W + 2 * pw - kw) // sw + 1
+    # the C ABI's argument order: N, C, H, W, kH, kW, dH, dW, padH, padW, dilationH, dilationW
+    return (N, Ch, H, W, kh, kw, sh, sw, ph, pw, 1, 1), (N, Ch, Ho, Wo)
+
+
+_DEPTHWISE = _ConvFamily("depthwise_conv2d", "tdrn_dwconv2d", _depthwise_geometry, 0,
+                         "kernel 3 x 3, stride 1 or 2, padding 1, dilation 1, channel multiplier 1, fewer than 2^31 elements",
+                         "N, C, H, W, kH, kW, dH, dW, padH, padW, dilH, dilW")
+
+
+def _depthwise_check(input, weight, bias):
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _conv2d_require_cuda(input, weight, bias)
+
+
+class DepthwiseConv2dFunction(torch.autograd.Function):
+    """Depthwise 3x3 conv (groups = channels, pad 1, stride 1 or 2) with gradients: forward through tdrn_dwconv2d_forward, backward
+    through tdrn_dwconv2d_backward_input (when the input needs a gradient) and tdrn_dwconv2d_backward_parameters (weight and bias
+    gradients, scale 1 into zeroed buffers).  fp32 throughout: the op has no 16-bit mode.  The weight is (channels, 1, 3, 3), torch's
+    layout.  Geometry the library rejects raises; nothing falls back to torch.
+
+        y = DepthwiseConv2dFunction.apply(input, weight, bias_or_None, stride, padding)
+    """
+
+    @staticmethod
+    def forward(ctx, input, weight, bias=None, stride=1, padding=1):
+        _depthwise_check(input, weight, bias)
+        return _conv_function_forward(ctx, _DEPTHWISE, input, weight, bias, (stride, padding), "fp32")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _conv_function_backward(ctx, grad_output) + (None, None)
+
+
+def depthwise_conv2d(input, weight, bias=None, stride=1, padding=1):
+    """F.conv2d(input, weight, bias, stride, padding, groups=channels) for a (channels, 1, 3, 3) weight on libtdrn_hip (NCHW fp32 CUDA
+    tensors in, NCHW fp32 out), differentiable in input, weight and bias: the depthwise conv of conv_dw.  `stride` is 1 or 2,
+    `padding` 1; anything else raises.  With grad mode off, or when nothing requires grad, only the forward runs and the output has
+    no grad_fn."""
+    _depthwise_check(input, weight, bias)
+    return _conv_dispatch(DepthwiseConv2dFunction, _DEPTHWISE, input, weight, bias, (stride, padding), "fp32", stride, padding)
+
+
+class DepthwiseConv2d(nn.Module):
+    """The parameters, state-dict keys and default init of nn.Conv2d(channels, channels, 3, stride, 1, groups=channels) on
+    depthwise_conv2d above."""
+
+    def __init__(self, channels, stride=1, bias=False):
+        super(DepthwiseConv2d, self).__init__()
+        self.channels, self.stride, self.padding = channels, _pair(stride), (1, 1)
+        self.weight = nn.Parameter(torch.empty(channels, 1, 3, 3))
+        self.bias = nn.Parameter(torch.empty(channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            nn.init.uniform_(self.bias, -1.0 / 3, 1.0 / 3)          # 1 / sqrt(fan_in), fan_in = 9
+
+    def forward(self, input):
+        return depthwise_conv2d(input, self.weight, self.bias, self.stride, self.padding)
+
+    def extra_repr(self):
+        return "{channels}, stride={stride}, bias={0}".format(self.bias is not None, **self.__dict__)
 
 
 def _batch_norm_check(input, running_mean, running_var, weight, bias, training):
