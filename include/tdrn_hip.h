@@ -342,6 +342,45 @@ TDRN_API int tdrn_dwconv2d_backward_parameters(const float *input, const float *
                                                size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-i) Dense 5x5 conv2d with gradients -- what nn.Conv2d(256, c, 5, 1, 2) + autograd give the reference's training loop (odm_loc_2 /
+ *     odm_conf_2 of refinedet_vgg with multihead=True): forward, input gradient, weight / bias gradient.  A family of its own: (i-c)
+ *     keeps refusing k = 5, and this one refuses every other kernel size.
+ *   Tensors, `compute`, OVERWRITTEN / += scale semantics, the argument lists and the order of the checks are (i-c)'s, with
+ *   Ho = H and Wo = W; all fp32, contiguous, device, on any 4-byte boundary.
+ *   forward:             output[n][co][h][w] = bias[co] + sum_{ci,i,j} input[n][ci][h - 2 + i][w - 2 + j] weight[co][ci][i][j].
+ *   backward_input:      grad_input is OVERWRITTEN: the same conv over grad_output with the kernel rotated by 180 degrees and its
+ *                        channel axes exchanged (pad' = 4 - 2 = 2).
+ *   backward_parameters: grad_weight += scale * sum_p grad_output[p] input[p - 2 (+) tap], grad_bias += scale * sum_p grad_output[p]
+ *                        (NULL: not computed), split over K = N*H*W and summed in split order.  The 25 taps run as five passes, one
+ *                        per kernel row, side by side in one launch; K is cut into S = ceil(K / P) ranges of
+ *                        P = ceil(ceil(K / S') / 64) * 64 pixels, S' = max(1, min(ceil(512 / (5 T)), ceil(K / 256))), T = the 64 x 64
+ *                        tiles of the padded Cout x Cin.
+ *   All outputs are bitwise reproducible run to run, and the same for caller buffers on any 4-byte boundary: nothing on this path
+ *   uses float atomics, and the split counts depend on the geometry alone.
+ *   Geometry (the argument order is the query's in all four functions): kH = kW = 5, dH = dW = 1, dilation 1, padH = padW = 2,
+ *   groups = 1; any N, Cin, Cout, H, W >= 1 inside the limits below.
+ *   Errors, all decided before any launch: a null tensor pointer -> TDRN_E_ARG (first); k <= 0, stride / dilation <= 0, negative
+ *   pad, N / Cin / Cout / H / W <= 0, an output smaller than 1 x 1 -> query 0 and TDRN_E_SHAPE; `compute` outside 0..2 -> TDRN_E_ARG;
+ *   any other well-formed geometry (k = 1 or 3 or any other size, a non-square kernel, stride 2, pad 1 or 3, per-axis pad, dilation 2;
+ *   N*H*W*Cin_pad or N*H*W*Cout_pad of 2^31 elements or more, channels padded to 64) -> query 0 and TDRN_E_UNSUPPORTED; a null
+ *   workspace or one below the query -> TDRN_E_WORKSPACE.  One query serves all three entries.  No allocation and no host
+ *   synchronisation: everything is enqueued on `stream`.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_conv5x5_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH,
+                                             int padW, int dilationH, int dilationW, tdrn_dtype compute);
+TDRN_API int tdrn_conv5x5_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin,
+                                  int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                  int dilationW, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv5x5_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin,
+                                         int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                         int dilationH, int dilationW, tdrn_dtype compute, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_conv5x5_backward_parameters(const float *input, const float *grad_output, float *grad_weight,
+                                              float *grad_bias, int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH,
+                                              int dW, int padH, int padW, int dilationH, int dilationW, float scale,
+                                              tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

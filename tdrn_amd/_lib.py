@@ -111,6 +111,11 @@ _SIGS = {
     "tdrn_conv2d_strided_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "tdrn_conv2d_strided_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p,
                                                                                                C.c_size_t, C.c_void_p]),
+    "tdrn_conv5x5_workspace_bytes": (C.c_size_t, [C.c_int] * 14),
+    "tdrn_conv5x5_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_conv5x5_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_conv5x5_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p, C.c_size_t,
+                                                                                        C.c_void_p]),
     "tdrn_dwconv2d_workspace_bytes": (C.c_size_t, [C.c_int] * 13),
     "tdrn_dwconv2d_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "tdrn_dwconv2d_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1,5 +1,5 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g), (i-h) and (ii) (section (iii) is in net.hip).
-// Sections (i-c), (i-f) and (i-g), the trainable dense conv families, share one plan, one workspace layout and one runner
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g), (i-h), (i-i) and (ii) (section (iii) is in net.hip).
+// Sections (i-c), (i-f), (i-g) and (i-i), the trainable dense conv families, share one plan, one workspace layout and one runner
 // (ConvTrainPlan); the depthwise conv (i-h) works on NCHW planes and has its own small plan (DwConvPlan).
 #include <cmath>
 #include <cstring>
@@ -76,8 +76,8 @@ int deform_bwd_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int 
     return TDRN_OK;
 }
 
-// The three trainable conv families: dense conv2d at stride 1 (section i-c), ConvTranspose2d(k = 2, s = 2) (section i-f) and the 3x3
-// conv at stride 2 (section i-g).  In each the forward and the input gradient are one launch_conv with an fp32 NHWC result, and the
+// The four trainable conv families: dense conv2d at stride 1 (section i-c), ConvTranspose2d(k = 2, s = 2) (section i-f), the 3x3
+// conv at stride 2 (section i-g) and the 5x5 conv (section i-i, conv5x5_plan).  In each the forward and the input gradient are one launch_conv with an fp32 NHWC result, and the
 // weight gradient is one conv_bwd.hip GEMM: a family is its geometry checks and these three descriptions (conv2d_plan, convt2d_plan,
 // convs2_plan); layout, bias staging and the run are shared.
 // Workspace: zero page | x NHWC | the grad_output image NHWC (what the input gradient convolves) | the rest, which is either {packed
@@ -184,6 +184,32 @@ int conv2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, 
     f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.pad = padH;
     d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin); d.pad = dilH * (kH - 1) - padH;
     f.kh = f.kw = d.kh = d.kw = kH; f.dil = d.dil = dilH;
+    conv_train_dense_out(f);
+    conv_train_dense_out(d);
+    conv_train_layout(p, dtype);
+    return TDRN_OK;
+}
+
+// dense 5x5 conv (section i-i): kH = kW = 5, stride 1, dilation 1, pad 2, so Ho x Wo = H x W.  The forward and the input gradient
+// (pad' = 4 - 2 = 2) are launch_conv at 25 taps, as the engine runs this layer; the weight gradient is conv_bwd.hip's row passes.
+int conv5x5_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
+                 ConvTrainPlan &p)
+{
+    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
+    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
+    if (kH != 5 || kW != 5 || dH != 1 || dW != 1 || padH != 2 || padW != 2 || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
+    const int CiPad = conv_bwd_cpad(Cin), CoPad = conv_bwd_cpad(Cout);
+    // 32-bit offsets of the kernels (conv_igemm.hip: elements; conv_bwd.hip: pixels), as conv2d_plan
+    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * H * W * CoPad >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, 5, 2, 1, H, W};
+    ConvArgs &f = p.fwd, &d = p.dgrad;
+    f.B = d.B = N;
+    f.H = f.Ho = d.H = d.Ho = H; f.W = f.Wo = d.W = d.Wo = W;
+    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout);
+    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin);
+    f.kh = f.kw = d.kh = d.kw = 5; f.pad = d.pad = 2;
     conv_train_dense_out(f);
     conv_train_dense_out(d);
     conv_train_layout(p, dtype);
@@ -444,8 +470,47 @@ int tdrn_deform_conv_backward_parameters(const float *input, const float *offset
     return launch_deform_bwd_weight(b.g, in_nhwc, offset, grad_output, (float *)(ws + b.o_slab), grad_weight, scale, s);
 }
 
-// The nine entries of the trainable conv families (ConvTrainPlan above): pointer check, plan, conv_train_begin, then each one's own
+// The entries of the trainable conv families (ConvTrainPlan above): pointer check, plan, conv_train_begin, then each one's own
 // layout conversion(s), weight packing and tail.
+namespace {
+
+// what the two stride-1 dense families (i-c, i-i) do once their plan has spoken: conversions, packing, one launch
+int conv_dense_forward(int plan_rc, const ConvTrainPlan &p, const float *input, const float *weight, const float *bias, float *output,
+                       int Cin, int dtype, void *workspace, size_t workspace_bytes, hipStream_t s)
+{
+    char *ws = (char *)workspace;
+    TDRN_TRY(conv_train_begin(plan_rc, p, workspace, workspace_bytes, s));
+    const ConvArgs &f = p.fwd;
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, f.B, Cin, f.H * f.W, f.Cin, dtype, s));
+    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, f.Cout, f.Npad, Cin, f.kh * f.kw, 1, f.Cin, dtype, s));
+    TDRN_TRY(conv_train_bias(f, ws + p.o_bias, bias, s));
+    return conv_train_run(p, ws, false, output, s);
+}
+
+int conv_dense_backward_input(int plan_rc, const ConvTrainPlan &p, const float *grad_output, const float *weight, float *grad_input,
+                              int dtype, void *workspace, size_t workspace_bytes, hipStream_t s)
+{
+    char *ws = (char *)workspace;
+    TDRN_TRY(conv_train_begin(plan_rc, p, workspace, workspace_bytes, s));
+    const ConvArgs &d = p.dgrad;
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, d.B, p.wg.Cout, p.wg.Ho * p.wg.Wo, d.Cin, dtype, s));
+    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, p.wg.Cout, p.wg.Cin, d.Npad, d.kh * d.kw, dtype, s));
+    TDRN_TRY(conv_train_bias(d, ws + p.o_bias, nullptr, s));
+    return conv_train_run(p, ws, true, grad_input, s);
+}
+
+int conv_dense_backward_parameters(int plan_rc, const ConvTrainPlan &p, const float *input, const float *grad_output, float *grad_weight,
+                                   float *grad_bias, float scale, int dtype, void *workspace, size_t workspace_bytes, hipStream_t s)
+{
+    char *ws = (char *)workspace;
+    TDRN_TRY(conv_train_begin(plan_rc, p, workspace, workspace_bytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, p.wg.N, p.wg.Cin, p.wg.H * p.wg.W, p.fwd.Cin, dtype, s));
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, p.wg.N, p.wg.Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, dtype, s));
+    return launch_conv_wgrad(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, dtype, s);
+}
+
+}  // namespace
+
 size_t tdrn_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
                                    int dilationH, int dilationW, tdrn_dtype compute)
 {
@@ -459,14 +524,8 @@ int tdrn_conv2d_forward(const float *input, const float *weight, const float *bi
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
     ConvTrainPlan p;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    TDRN_TRY(conv_train_begin(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
-                              workspace_bytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
-    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.fwd.Npad, Cin, kH * kW, 1, p.fwd.Cin, compute, s));
-    TDRN_TRY(conv_train_bias(p.fwd, ws + p.o_bias, bias, s));
-    return conv_train_run(p, ws, false, output, s);
+    const int rc = conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_forward(rc, p, input, weight, bias, output, Cin, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W, int Cout,
@@ -475,14 +534,8 @@ int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, fl
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
     ConvTrainPlan p;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    TDRN_TRY(conv_train_begin(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
-                              workspace_bytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
-    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.dgrad.Npad, kH * kW, compute, s));
-    TDRN_TRY(conv_train_bias(p.dgrad, ws + p.o_bias, nullptr, s));
-    return conv_train_run(p, ws, true, grad_input, s);
+    const int rc = conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_backward_input(rc, p, grad_output, weight, grad_input, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N, int Cin,
@@ -491,13 +544,48 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
     ConvTrainPlan p;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    TDRN_TRY(conv_train_begin(conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
-                              workspace_bytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
-    return launch_conv_wgrad(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+    const int rc = conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_backward_parameters(rc, p, input, grad_output, grad_weight, grad_bias, scale, compute, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
+}
+
+// section i-i: the same three bodies under conv5x5_plan
+size_t tdrn_conv5x5_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                    int dilationH, int dilationW, tdrn_dtype compute)
+{
+    ConvTrainPlan p;
+    return conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
+}
+
+int tdrn_conv5x5_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W, int Cout,
+                         int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !output) return TDRN_E_ARG;
+    ConvTrainPlan p;
+    const int rc = conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_forward(rc, p, input, weight, bias, output, Cin, compute, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int tdrn_conv5x5_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W, int Cout,
+                                int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype compute,
+                                void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
+    ConvTrainPlan p;
+    const int rc = conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_backward_input(rc, p, grad_output, weight, grad_input, compute, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int tdrn_conv5x5_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N, int Cin,
+                                     int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                     int dilationW, float scale, tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
+    ConvTrainPlan p;
+    const int rc = conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_backward_parameters(rc, p, input, grad_output, grad_weight, grad_bias, scale, compute, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
 }
 
 size_t tdrn_conv_transpose2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,

@@ -27,6 +27,10 @@
 //   * every split stores its fp32 slab [split][tap][CoutPad][CinPad] (+ [split][CoutPad] for the bias); the reduce kernel sums
 //     them in split order and applies += scale * into OIHW.  No float atomics: bitwise reproducible, and the split count is a pure
 //     function of the geometry (conv_wgrad_splits).
+//   * k = 5 (tdrn_hip.h section i-i): 25 taps x 16 accumulators do not fit the register file, so the grid gains the kernel ROW: a
+//     workgroup is (K split, kernel row r, 64 cin, 64 cout), holds the five tiles of taps 5r .. 5r+4, stages their input tiles
+//     through the same ring (the last tap index of a pass is even, as at nine taps, so slot 0 is free at the chunk boundary) and
+//     writes slab rows [split][5r + j]; it restages the grad_output tile of its chunks, and grad_bias rides along in row 0 only.
 #include <algorithm>
 
 #include "kernels.h"
@@ -73,14 +77,15 @@ template <> __device__ __forceinline__ unsigned ones2<f16_t>() { return 0x3c003c
 
 // the accumulators of one wave -> its split's slab.  C/D map of the 32x32 MFMAs: column = lane & 31 (cin), row = (reg & 3) +
 // 8 (reg >> 2) + 4 (lane >> 5) (cout)
-template <int NT>
-__device__ __forceinline__ void wgrad_store(const WgradParams &g, const f32x16 (&acc)[NT], const f32x16 &bacc, int split, int ci0, int co0,
-                                            int lane, int wm, int wn, bool with_bias)
+// (NT accumulated taps of the split's ROWS * NT, starting at tap0)
+template <int NT, int ROWS>
+__device__ __forceinline__ void wgrad_store(const WgradParams &g, const f32x16 (&acc)[NT], const f32x16 &bacc, int split, int tap0, int ci0,
+                                            int co0, int lane, int wm, int wn, bool with_bias)
 {
     const int cil = ci0 + wn * 32 + (lane & 31);
 #pragma unroll
     for (int tap = 0; tap < NT; ++tap) {
-        float *sl = g.slab + ((size_t)split * NT + tap) * g.CoPad * g.CiPad;
+        float *sl = g.slab + ((size_t)split * (ROWS * NT) + tap0 + tap) * g.CoPad * g.CiPad;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -96,18 +101,20 @@ __device__ __forceinline__ void wgrad_store(const WgradParams &g, const f32x16 (
     }
 }
 
-// NT = taps (k*k): 9 or 1
-template <typename DT, int NT>
+// NT = taps a workgroup accumulates, KK = kernel size: (9, 3) and (1, 1) are the whole kernel; (5, 5) is one kernel row, and
+// blockIdx.x = split * 5 + row
+template <typename DT, int NT, int KK>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams g)
 {
-    constexpr int ES = elem_traits<DT>::bytes, ROWB = WgLds<DT>::ROWB, V16 = WgLds<DT>::V16, KK = NT == 9 ? 3 : 1;
+    constexpr int ES = elem_traits<DT>::bytes, ROWB = WgLds<DT>::ROWB, V16 = WgLds<DT>::V16, ROWS = KK * KK / NT;
+    static_assert(ROWS * NT == KK * KK && (NT & 1) == 1, "whole passes; an even last tap index leaves ring slot 0 to the next chunk");
     constexpr int TILEB = kWgPx * ROWB;
     __shared__ __attribute__((aligned(16))) char s_go[TILEB];
     __shared__ __attribute__((aligned(16))) char s_x[2][TILEB];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-    const int split = blockIdx.x, ci0 = blockIdx.y * kWgTile, co0 = blockIdx.z * kWgTile;
+    const int split = blockIdx.x / ROWS, tap0 = (blockIdx.x % ROWS) * NT, ci0 = blockIdx.y * kWgTile, co0 = blockIdx.z * kWgTile;
     const int mbeg = split * g.per_split, mend = min(g.M, mbeg + g.per_split);
-    const bool with_bias = blockIdx.y == 0 && wn == 0;                  // (wave-uniform)
+    const bool with_bias = blockIdx.y == 0 && wn == 0 && tap0 == 0;     // (wave-uniform)
 
     // staging: thread = a quarter (16 channels) of pixel row sp
     const int sp = t >> 2, sq = t & 3;
@@ -132,7 +139,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams g)
         for (int v = 0; v < V16; ++v) rgo[v] = *(const u32x4 *)(src + 16 * v);
     };
     auto load_x = [&](int tap) {
-        const int hi = pho * g.stride - g.pad + (tap / KK) * g.dil, wi = pwo * g.stride - g.pad + (tap % KK) * g.dil;
+        const int kt = tap0 + tap;
+        const int hi = pho * g.stride - g.pad + (kt / KK) * g.dil, wi = pwo * g.stride - g.pad + (kt % KK) * g.dil;
         const bool ok = pvalid && hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
         const char *src = ok ? g.x + ((((size_t)pn * g.H + hi) * g.W + wi) * g.CiPad + ci0 + sq * 16) * ES : zsrc;
 #pragma unroll
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams g)
         }
     }
 
-    wgrad_store<NT>(g, acc, bacc, split, ci0, co0, lane, wm, wn, with_bias);
+    wgrad_store<NT, ROWS>(g, acc, bacc, split, tap0, ci0, co0, lane, wm, wn, with_bias);
 }
 
 // grad_weight[co][ci][tap] += scale * sum_{s = 0..S-1} slab[s][tap][co][ci] (thread index: ci fastest -> coalesced slab reads), then
@@ -260,8 +268,9 @@ __global__ __launch_bounds__(256) void repack_oihw_dgrad_kernel(const float *__r
 
 template <typename DT> int launch_wgrad_dt(const WgradParams &p, int taps, dim3 grid, hipStream_t s)
 {
-    if (taps == 9) hipLaunchKernelGGL((conv_wgrad_kernel<DT, 9>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<DT, 1>), grid, dim3(256), 0, s, p);
+    if (taps == 25) hipLaunchKernelGGL((conv_wgrad_kernel<DT, 5, 5>), dim3(grid.x * 5, grid.y, grid.z), dim3(256), 0, s, p);
+    else if (taps == 9) hipLaunchKernelGGL((conv_wgrad_kernel<DT, 9, 3>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((conv_wgrad_kernel<DT, 1, 1>), grid, dim3(256), 0, s, p);
     return hip_status(hipGetLastError());
 }
 
@@ -269,12 +278,13 @@ template <typename DT> int launch_wgrad_dt(const WgradParams &p, int taps, dim3 
 
 int conv_bwd_cpad(int c) { return (int)align_up((size_t)c, kChanPad); }
 
-// K splits: enough workgroups for two per CU, at least four 64-pixel chunks each.  Geometry only.
+// K splits: enough workgroups for two per CU, at least four 64-pixel chunks each.  Geometry only.  k = 5 runs five workgroups (the
+// kernel rows) per split and tile and counts them; the rule of k = 1 | 3 is untouched.
 void conv_wgrad_splits(const ConvBwdGeom &g, int &splits, int &per_split)
 {
     const int M = g.N * g.Ho * g.Wo;
     const int tiles = (conv_bwd_cpad(g.Cin) / kWgTile) * (conv_bwd_cpad(g.Cout) / kWgTile);
-    int S = cdiv(512, tiles);
+    int S = cdiv(512, g.k == 5 ? 5 * tiles : tiles);
     const int max_s = cdiv(M, 4 * kWgPx);
     S = S < 1 ? 1 : (S > max_s ? max_s : S);
     per_split = (int)align_up((size_t)cdiv(M, S), kWgPx);
@@ -304,7 +314,7 @@ int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int N
 int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, int dtype,
                             hipStream_t s, int &splits, const float *&bias_slab)
 {
-    if ((g.k != 1 && g.k != 3) || g.stride < 1 || !x_nhwc || !go_nhwc || !zero_page || !slab) return TDRN_E_UNSUPPORTED;
+    if ((g.k != 1 && g.k != 3 && g.k != 5) || g.stride < 1 || !x_nhwc || !go_nhwc || !zero_page || !slab) return TDRN_E_UNSUPPORTED;
     int S, per_split;
     conv_wgrad_splits(g, S, per_split);
     const int taps = g.k * g.k;

@@ -1,7 +1,7 @@
 """Shared host-side shell of the model mirrors: an nn.Module that owns the reference's parameter
 layout (so `load_state_dict(torch.load(...))`, `.eval()`, `.cuda()` keep working) while `forward`
-hands the batch to libtdrn_hip.so through NetEngine (inference), and TrainWalk: what the forward_train of the dual-refinement
-models is made of, on the library's differentiable ops."""
+hands the batch to libtdrn_hip.so through NetEngine (inference), and TrainWalk: what the forward_train of the five models is made
+of, on the library's differentiable ops."""
 import os
 
 import torch
@@ -177,8 +177,13 @@ def _is_depthwise3x3(m):
 
 
 class TrainWalk(object):
-    """What the forward_train of both dual-refinement models is made of: the walk over a list of parameter holders and the shared head,
-    on the library's differentiable ops.  The ops are looked up on `networks` at call time."""
+    """What the forward_train of the models is made of: the walk over a list of parameter holders, the VGG and MobileNet source walks,
+    the TCB pyramid, the dual-refinement head and the SSD4Scale heads, on the library's differentiable ops.  The ops are looked up on
+    `networks` at call time."""
+
+    # the loc and conf heads of an SSD4Scale level with deform=True run as ONE conv_offset2d over their concatenated weights (the
+    # input is transposed and gathered, and its gradient scattered, once instead of twice); False: two calls.  Measured: DESIGN 20.
+    _paired_heads = True
 
     def _bn_relu(self, bn, x):
         if bn.momentum is None:
@@ -224,6 +229,81 @@ class TrainWalk(object):
         object.__setattr__(self, "_dirty", True)
         return x.float()
 
+    def _vgg_sources(self, x, compute):
+        """the VGG trunk of the three VGG models -> ([conv4_3 and conv5_3 behind their ReLU and L2Norm, fc7, extras], extras)"""
+        x, (c43, c53) = self._walk(self.backbone, x, compute, taps=(10, 13))     # x: fc7
+        arm_sources = [networks.l2norm(c43, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps),
+                       networks.l2norm(c53, self.L2Norm_5_3.weight, self.L2Norm_5_3.eps), x]
+        x, _ = self._walk(self.extras, x, compute)
+        arm_sources.append(x)
+        return arm_sources, x
+
+    def _mobilenet_sources(self, x, compute):
+        """the MobileNet trunk of the two MobileNet models -> ([block 11 and block 13 behind their L2Norm, the two extras], extras)"""
+        x, _ = self._walk(self.backbone[:12], x, compute)
+        arm_sources = [networks.l2norm(x, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps)]
+        x, _ = self._walk(self.backbone[12:], x, compute)
+        arm_sources.append(networks.l2norm(x, self.L2Norm_5_3.weight, self.L2Norm_5_3.eps))
+        for block in self.extras:
+            x, _ = self._walk(block, x, compute)
+            arm_sources.append(x)
+        return arm_sources, x
+
+    def _ssd_heads_train(self, arm_sources, ref_loc, compute, ret_loc):
+        """the heads of the two SSD4Scale models from their four sources -> forward_train's tuple.  deform=False: two conv2d per
+        level.  deform=True: offsets from ref_loc[s] by the 1x1 conv offset[s], then both deformable heads over them."""
+        B = arm_sources[0].size(0)
+        locs, confs, loc_maps = [], [], []
+        if self.deform:
+            if not ref_loc:
+                raise ValueError("deform=True needs ref_loc")
+            if len(ref_loc) != 4:
+                raise ValueError("ref_loc must hold four loc maps, got %d" % len(ref_loc))
+            for s, (a, r) in enumerate(zip(arm_sources, ref_loc)):
+                want = (B, self.offset[s].in_channels) + tuple(a.shape[2:])
+                if not torch.is_tensor(r) or tuple(r.shape) != want:
+                    raise ValueError("ref_loc[%d] must be a tensor of shape %r, got %r" % (s, want, tuple(getattr(r, "shape", ()))))
+                _lib.require_cuda(r, "ref_loc[%d]" % s)
+        for s, a in enumerate(arm_sources):
+            hl, hc = self.arm_loc[s], self.arm_conf[s]
+            if not self.deform:
+                loc = networks.conv2d(a, hl.weight, hl.bias, 1, 1, compute)
+                conf = networks.conv2d(a, hc.weight, hc.bias, 1, 1, compute)
+                loc_maps.append(loc)
+            else:
+                off = networks.conv2d(ref_loc[s].float(), self.offset[s].weight, self.offset[s].bias, 0, 1, compute)
+                if self._paired_heads:
+                    both = networks.conv_offset2d(a, off, torch.cat([hl.weight, hc.weight]), 1, 1, 1, hl.num_deformable_groups, compute)
+                    loc, conf = both.split([hl.out_channels, hc.out_channels], 1)
+                else:
+                    loc, conf = (networks.conv_offset2d(a, off, h.weight, 1, 1, 1, h.num_deformable_groups, compute) for h in (hl, hc))
+            locs.append(loc.permute(0, 2, 3, 1).contiguous().view(B, -1))
+            confs.append(conf.permute(0, 2, 3, 1).contiguous().view(B, -1))
+        out = (torch.cat(locs, 1).view(B, -1, 4), torch.cat(confs, 1).view(B, -1, self.num_classes))
+        return out + (loc_maps,) if ret_loc else out
+
+    def _ssd_forward_train(self, sources, x, ref_loc, compute, ret_loc):
+        """forward_train of the two SSD4Scale models; `sources`: _vgg_sources or _mobilenet_sources"""
+        x = self._train_input(x)
+        arm_sources, _ = sources(x, compute)
+        return self._ssd_heads_train(arm_sources, ref_loc, compute, ret_loc)
+
+    def _tcb_train(self, arm_sources, x, compute):
+        """last_layer_trans and the TCB pyramid (trans_layers, up_layers, latent_layers) from the four ARM sources and the last
+        feature map x -> the four ODM sources, largest map first"""
+        conv = lambda m, t, pad: networks.conv2d(t, m.weight, m.bias, pad, 1, compute)
+        x, _ = self._walk(self.last_layer_trans, x, compute)
+        odm_sources = [x]
+        trans = [self._walk(self.trans_layers[s], arm_sources[s], compute)[0] for s in range(3)]
+        trans.reverse()
+        for i, t in enumerate(trans):
+            up = self.up_layers[i]
+            u = torch.relu(networks.conv_transpose2d(x, up.weight, up.bias, 2, compute) + t)
+            x = torch.relu(conv(self.latent_layers[i], u, 1))
+            odm_sources.append(x)
+        odm_sources.reverse()
+        return odm_sources
+
     def _head_train(self, arm_sources, x, compute):
         """ARM loc / offsets, last_layer_trans, the TCB pyramid and the deformable heads (add_refine_head's modules, with or without
         biases) from the four ARM sources and the last feature map x -> forward_train's 4-tuple"""
@@ -236,16 +316,7 @@ class TrainWalk(object):
             off1.append(conv(self.offset[s], loc_a, 0))
             if self.multihead:
                 off2.append(conv(self.offset2[s], loc_a, 0))
-        x, _ = self._walk(self.last_layer_trans, x, compute)
-        odm_sources = [x]
-        trans = [self._walk(self.trans_layers[s], arm_sources[s], compute)[0] for s in range(3)]
-        trans.reverse()
-        for i, t in enumerate(trans):
-            up = self.up_layers[i]
-            u = torch.relu(networks.conv_transpose2d(x, up.weight, up.bias, 2, compute) + t)
-            x = torch.relu(conv(self.latent_layers[i], u, 1))
-            odm_sources.append(x)
-        odm_sources.reverse()
+        odm_sources = self._tcb_train(arm_sources, x, compute)
         odm_loc, odm_conf = [], []
         for s, ob in enumerate(odm_sources):
             heads = [(self.odm_loc[s], self.odm_conf[s], off1[s])]
@@ -260,3 +331,21 @@ class TrainWalk(object):
             odm_conf.append(c.permute(0, 2, 3, 1).contiguous().view(B, -1))
         return (torch.cat(arm_loc, 1).view(B, -1, 4), None, torch.cat(odm_loc, 1).view(B, -1, 4),
                 torch.cat(odm_conf, 1).view(B, -1, self.num_classes))
+
+    def _refinedet_head_train(self, arm_sources, x, compute):
+        """refinedet_vgg's heads: ARM loc (use_refine), the TCB pyramid and the dense ODM heads, 3x3 through conv2d and, with
+        multihead, 5x5 through conv5x5, summed -> forward_train's tuple"""
+        B = x.size(0)
+        conv = lambda m, t: networks.conv2d(t, m.weight, m.bias, 1, 1, compute)
+        if self.use_refine:
+            arm_loc = [conv(self.arm_loc[s], a).permute(0, 2, 3, 1).contiguous().view(B, -1) for s, a in enumerate(arm_sources)]
+        odm_loc, odm_conf = [], []
+        for s, ob in enumerate(self._tcb_train(arm_sources, x, compute)):
+            l, c = conv(self.odm_loc[s], ob), conv(self.odm_conf[s], ob)
+            if self.multihead:
+                l = l + networks.conv5x5(ob, self.odm_loc_2[s].weight, self.odm_loc_2[s].bias, compute)
+                c = c + networks.conv5x5(ob, self.odm_conf_2[s].weight, self.odm_conf_2[s].bias, compute)
+            odm_loc.append(l.permute(0, 2, 3, 1).contiguous().view(B, -1))
+            odm_conf.append(c.permute(0, 2, 3, 1).contiguous().view(B, -1))
+        out = (torch.cat(odm_loc, 1).view(B, -1, 4), torch.cat(odm_conf, 1).view(B, -1, self.num_classes))
+        return (torch.cat(arm_loc, 1).view(B, -1, 4), None) + out if self.use_refine else out

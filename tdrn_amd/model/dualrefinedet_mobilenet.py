@@ -7,7 +7,6 @@ import torch.nn as nn
 from .. import _lib
 from ..layers.modules.l2norm import L2Norm
 from ._base import EngineModule, TrainWalk
-from . import networks
 from .dualrefinedet_vggbn import add_refine_head
 from .networks import conv_dw, mobilenet_backbone
 
@@ -44,13 +43,7 @@ class RefineSSD(EngineModule, TrainWalk):
         the depthwise convs, BatchNorm and L2Norm are fp32.  The engine's packed weights are marked stale, so net(x) after an
         optimizer step re-packs by itself."""
         x = self._train_input(x)
-        x, _ = self._walk(self.backbone[:12], x, compute)
-        arm_sources = [networks.l2norm(x, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps)]
-        x, _ = self._walk(self.backbone[12:], x, compute)
-        arm_sources.append(networks.l2norm(x, self.L2Norm_5_3.weight, self.L2Norm_5_3.eps))
-        for block in self.extras:
-            x, _ = self._walk(block, x, compute)
-            arm_sources.append(x)
+        arm_sources, x = self._mobilenet_sources(x, compute)
         return self._head_train(arm_sources, x, compute)
 
 

@@ -10,7 +10,6 @@ import torch.nn as nn
 
 from .. import _lib
 from ..layers.modules.l2norm import L2Norm
-from . import networks
 from ._base import EngineModule, TrainWalk
 from .networks import ConvOffset2d, vgg, vgg_base
 
@@ -73,11 +72,7 @@ class RefineSSD(EngineModule, TrainWalk):
         `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of every conv-type op; BatchNorm, pools and L2Norm are fp32.
         The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
         x = self._train_input(x)
-        x, (c43, c53) = self._walk(self.backbone, x, compute, taps=(10, 13))     # x: fc7; conv4_3, conv5_3 behind their ReLU
-        arm_sources = [networks.l2norm(c43, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps),
-                       networks.l2norm(c53, self.L2Norm_5_3.weight, self.L2Norm_5_3.eps), x]
-        x, _ = self._walk(self.extras, x, compute)
-        arm_sources.append(x)
+        arm_sources, x = self._vgg_sources(x, compute)
         return self._head_train(arm_sources, x, compute)
 
 

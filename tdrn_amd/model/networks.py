@@ -515,6 +515,78 @@ class DepthwiseConv2d(nn.Module):
         return "{channels}, stride={stride}, bias={0}".format(self.bias is not None, **self.__dict__)
 
 
+_CONV5X5_COVERED = "kernel 5 x 5, stride 1, padding 2, dilation 1, groups 1"
+
+
+def _conv5x5_geometry(x, w):
+    if w.dim() != 4 or tuple(w.shape[2:]) != (5, 5):
+        raise RuntimeError("conv5x5: weight has shape %r, expected (Cout, Cin, 5, 5); libtdrn_hip covers %s"
+                           % (tuple(w.shape), _CONV5X5_COVERED))
+    return _conv2d_geometry(x, w, 2, 1, 1)
+
+
+_CONV5X5 = _ConvFamily("conv5x5", "tdrn_conv5x5", _conv5x5_geometry, 0, _CONV5X5_COVERED,
+                       "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW")
+
+
+def _conv5x5_check(input, weight, bias):
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _conv2d_require_cuda(input, weight, bias)
+
+
+class Conv5x5Function(torch.autograd.Function):
+    """Dense 5x5 conv (pad 2, stride 1) with gradients: forward through tdrn_conv5x5_forward, backward through
+    tdrn_conv5x5_backward_input (when the input needs a gradient) and tdrn_conv5x5_backward_parameters (weight and bias gradients,
+    scale 1 into zeroed buffers).  `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the forward and of both
+    gradients.  Another weight shape raises; nothing falls back to torch.
+
+        y = Conv5x5Function.apply(input, weight, bias_or_None[, compute])
+    """
+
+    @staticmethod
+    def forward(ctx, input, weight, bias=None, compute="fp32"):
+        _conv5x5_check(input, weight, bias)
+        return _conv_function_forward(ctx, _CONV5X5, input, weight, bias, (), compute)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _conv_function_backward(ctx, grad_output) + (None,)
+
+
+def conv5x5(input, weight, bias=None, compute="fp32"):
+    """F.conv2d(input, weight, bias, padding=2) for a (Cout, Cin, 5, 5) weight on libtdrn_hip (NCHW fp32 CUDA tensors in, NCHW fp32
+    out), differentiable in input, weight and bias: the second ODM heads of refinedet_vgg's multihead.  With grad mode off, or when
+    nothing requires grad, only the forward runs and the output has no grad_fn."""
+    _conv5x5_check(input, weight, bias)
+    return _conv_dispatch(Conv5x5Function, _CONV5X5, input, weight, bias, (), compute, compute)
+
+
+class Conv5x5(nn.Module):
+    """The parameters, state-dict keys and default init of nn.Conv2d(in_channels, out_channels, 5, padding=2) on conv5x5 above."""
+
+    def __init__(self, in_channels, out_channels, bias=True, compute="fp32"):
+        super(Conv5x5, self).__init__()
+        self.in_channels, self.out_channels, self.compute = in_channels, out_channels, compute
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 5, 5))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            fan_in = self.in_channels * 25
+            bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, input):
+        return conv5x5(input, self.weight, self.bias, self.compute)
+
+    def extra_repr(self):
+        return "{in_channels}, {out_channels}, bias={0}, compute={compute}".format(self.bias is not None, **self.__dict__)
+
+
 def _batch_norm_check(input, running_mean, running_var, weight, bias, training):
     if input.dim() != 4:
         raise ValueError("expected 4D input (got {}D input)".format(input.dim()))

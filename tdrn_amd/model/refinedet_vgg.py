@@ -1,11 +1,13 @@
 """RefineDet on VGG16 (plain, non-deformable ODM heads): drop-in for model/refinedet_vgg.py
 (RefineSSD :27-110, forward :112-219, build_net :230-235).  The TRN drivers' 'FPN' branch and
-BASELINE config #5 name this model."""
+BASELINE config #5 name this model.  `net(x)` is the inference engine; `net.forward_train(x)` computes the phase-'train' outputs
+from the module's own fp32 parameters through the library's differentiable ops (_base.TrainWalk; the 5x5 heads of multihead through
+networks.conv5x5), so that `loss.backward()` fills their .grad."""
 import torch.nn as nn
 
 from .. import _lib
 from ..layers.modules.l2norm import L2Norm
-from ._base import EngineModule
+from ._base import EngineModule, TrainWalk
 from .networks import vgg, vgg_base
 
 
@@ -13,7 +15,7 @@ def _c(cin, cout, k):
     return nn.Conv2d(cin, cout, kernel_size=k, stride=1, padding=k // 2)
 
 
-class RefineSSD(EngineModule):
+class RefineSSD(EngineModule, TrainWalk):
     def __init__(self, size, num_classes=21, use_refine=False, phase='train', c7_channel=1024, bn=False, multihead=False):
         super(RefineSSD, self).__init__()
         self.num_classes, self.size, self.use_refine, self.phase = num_classes, size, use_refine, phase
@@ -51,6 +53,15 @@ class RefineSSD(EngineModule):
         if self.use_refine:
             return (r["arm_loc"], None, r["odm_loc"], conf)
         return (r["odm_loc"], conf)
+
+    def forward_train(self, x, compute="fp32"):
+        """-> (arm_loc (B, P, 4), None, odm_loc (B, P, 4), conf (B, P, num_classes) raw logits) with use_refine, else (odm_loc,
+        conf): the phase-'train' outputs of forward, computed from this module's fp32 parameters with an autograd graph.  BatchNorm
+        runs in the module's mode; `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of every conv-type op.  The engine's
+        packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
+        x = self._train_input(x)
+        arm_sources, x = self._vgg_sources(x, compute)
+        return self._refinedet_head_train(arm_sources, x, compute)
 
 
 def build_net(phase, size=320, num_classes=21, use_refine=False, c7_channel=1024, bn=False, multihead=False):

@@ -1,17 +1,18 @@
 """4-scale SSD on MobileNet-v1: drop-in for model/ssd4scale_mobile.py (SSD4Scale_MobNet :9-84,
 forward(x, ref_loc, offset_list, ret_loc, ret_off) :86-140, build_net :151-156).  With
 deform=True it is the TRN temporal net (8 deformable groups, offsets from the static net's
-loc maps)."""
+loc maps).  `net(x, ...)` is the inference engine; `net.forward_train(x, ref_loc)` is the differentiable walk train_trn.py's loop
+needs."""
 import torch.nn as nn
 
 from .. import _lib
 from ..layers.modules.l2norm import L2Norm
-from ._base import EngineModule
+from ._base import EngineModule, TrainWalk
 from .dualrefinedet_mobilenet import extras_block
 from .networks import ConvOffset2d, mobilenet_backbone
 
 
-class SSD4Scale_MobNet(EngineModule):
+class SSD4Scale_MobNet(EngineModule, TrainWalk):
     def __init__(self, size, num_classes=21, phase='train', c7_channel=1024, deform=False):
         super(SSD4Scale_MobNet, self).__init__()
         self.num_classes, self.size, self.phase, self.deform = num_classes, size, phase, deform
@@ -61,6 +62,16 @@ class SSD4Scale_MobNet(EngineModule):
             offs.token = r["offsets_token"]
             out.append(offs)
         return tuple(out)
+
+    def forward_train(self, x, ref_loc=(), compute="fp32", ret_loc=False):
+        """-> (arm_loc (B, P, 4), arm_conf (B, P, num_classes) raw logits): the phase-'train' outputs of forward whatever self.phase
+        is, computed from this module's fp32 parameters through the library's differentiable ops (_base.TrainWalk), so that
+        `loss.backward()` fills their .grad.  deform=True needs ref_loc, four CUDA tensors (B, 12, Hs, Ws): the static net's loc
+        maps (its forward with ret_loc=True); one that requires grad gets a gradient.  ret_loc=True appends the four loc maps (NCHW,
+        with their graph) when deform=False and [] when deform=True, as the reference does.  BatchNorm runs in the module's mode;
+        `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the conv-type ops.  offset_list, ret_off and ref_event belong
+        to inference.  The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
+        return self._ssd_forward_train(self._mobilenet_sources, x, ref_loc, compute, ret_loc)
 
 
 class _OffsetList(list):

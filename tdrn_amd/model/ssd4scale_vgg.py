@@ -1,16 +1,17 @@
 """4-scale SSD on VGG16: drop-in for model/ssd4scale_vgg.py (SSD4Scale :8-68, forward :71-135,
 build_net :146-151) -- the static (deform=False) and temporal (deform=True, 8 deformable groups)
-nets the TRN drivers build (train_trn.py:122-124, evaluate_trn.py:541-543, test_video_trn.py:54-56)."""
+nets the TRN drivers build (train_trn.py:122-124, evaluate_trn.py:541-543, test_video_trn.py:54-56).  `net(x, ...)` is the inference
+engine; `net.forward_train(x, ref_loc)` is the differentiable walk train_trn.py's loop needs."""
 import torch.nn as nn
 
 from .. import _lib
 from ..layers.modules.l2norm import L2Norm
-from ._base import EngineModule
+from ._base import EngineModule, TrainWalk
 from .networks import ConvOffset2d, vgg, vgg_base
 from .ssd4scale_mobile import _OffsetList
 
 
-class SSD4Scale(EngineModule):
+class SSD4Scale(EngineModule, TrainWalk):
     def __init__(self, size, num_classes=21, phase='train', c7_channel=1024, bn=True, deform=False):
         super(SSD4Scale, self).__init__()
         self.num_classes, self.size, self.phase, self.bn, self.deform = num_classes, size, phase, bn, deform
@@ -65,6 +66,16 @@ class SSD4Scale(EngineModule):
             offs.token = r["offsets_token"]
             out.append(offs)
         return tuple(out)
+
+    def forward_train(self, x, ref_loc=(), compute="fp32", ret_loc=False):
+        """-> (arm_loc (B, P, 4), arm_conf (B, P, num_classes) raw logits): the phase-'train' outputs of forward whatever self.phase
+        is, computed from this module's fp32 parameters through the library's differentiable ops (_base.TrainWalk), so that
+        `loss.backward()` fills their .grad.  deform=True needs ref_loc, four CUDA tensors (B, 12, Hs, Ws): the static net's loc
+        maps (its forward with ret_loc=True); one that requires grad gets a gradient.  ret_loc=True appends the four loc maps (NCHW,
+        with their graph) when deform=False and [] when deform=True, as the reference does.  BatchNorm runs in the module's mode;
+        `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the conv-type ops.  offset_list, ret_off and ref_event belong
+        to inference.  The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
+        return self._ssd_forward_train(self._vgg_sources, x, ref_loc, compute, ret_loc)
 
 
 def build_net(phase, size=320, num_classes=21, c7_channel=1024, bn=False, deform=False):
