@@ -7,6 +7,12 @@ results (outputs, input gradients, batch statistics) are the base's, replicated;
 times the base's.  The period -- the elements of one replica in any layout a kernel walks, the conv's channel-padded NHWC staging
 included -- divides none of 2^29, 2^30, 2^31: an offset that wrapped at 2^31 or 2^32 bytes (fp32: 2^29, 2^30 elements; 16-bit:
 2^30, 2^31 elements) or at 2^31 elements lands on another position of a replica, whose value differs.
+
+The five conv families (tdrn_hip.h sections i-c conv2d, i-f ConvTranspose2d 2x2 / stride 2, i-g 3x3 conv at stride 2, i-h depthwise
+3x3, i-i 5x5 conv) share one description: FAMILIES names each one's entry prefix, cases and modes, and op_dims, op_shapes,
+op_forward, op_inputs and op_reference serve all of them.  The stagings of the four later ones: the space-to-depth image
+[N][H][W][4][CoPad] of grad_output (i-f), the zero-inserted image [N][Hd][Wd][CoPad] of grad_output with Hd = H + 2 pad - 2 (i-g), the
+channel-padded NHWC images of x and grad_output (i-f, i-g, i-i); the depthwise kernels walk the NCHW planes themselves.
 """
 import functools
 
@@ -29,14 +35,48 @@ L2_CASES = {"l2_500": (64, 500, 500)}
 CONV_CASES = {"conv_big_output": (3, 500, 500, 64, 3, 1, 1),          # big output, big padded NHWC input
               "conv_big_grad_input": (64, 500, 500, 3, 3, 1, 1)}      # big input, big input gradient
 CONV_MODES = {"fp32": None, "bf16": torch.bfloat16}
+# ConvTranspose2d 2x2 at stride 2 (i-f): Cin, H, W, Cout
+CONVT_CASES = {"convt_big_output": (3, 250, 250, 64),          # big output and space-to-depth staging; W even: the s2d kernel's 16-byte path
+               "convt_big_grad_input": (256, 251, 251, 3)}     # big input, input gradient and both stagings; W odd: the dword path
+# 3x3 conv at stride 2 (i-g): Cin, H, W, Cout, pad
+S2_CASES = {"s2_big_grad_input": (64, 506, 506, 3, 0),         # big input and input gradient, D = 64 x 504 x 504; Wo = 252: the dilate kernel's quad
+                                                               # path; input row and column 505 are touched by no output pixel
+            "s2_big_dilated": (3, 501, 501, 64, 1)}            # big D = 64 x 501 x 501 (Hd = 2 Ho - 1) and x staging; Wo = 251: the dword path
+# depthwise 3x3, pad 1 (i-h): C, H, W, stride
+DW_CASES = {"dw_500_s1": (64, 500, 500, 1), "dw_501_s2": (64, 501, 501, 2)}       # (501 at stride 2: an odd map, Ho = 251)
+# 5x5 conv, pad 2 (i-i): Cin, H, W, Cout
+K5_CASES = {"k5_big_output": (3, 500, 500, 64), "k5_big_grad_input": (64, 500, 500, 3)}
+DW_MODES = {"fp32": None}                                      # the depthwise op has no 16-bit mode
+# family -> (entry prefix, cases, modes)
+FAMILIES = {"conv": ("tdrn_conv2d", CONV_CASES, CONV_MODES), "convt": ("tdrn_conv_transpose2d", CONVT_CASES, CONV_MODES),
+            "s2": ("tdrn_conv2d_strided", S2_CASES, CONV_MODES), "dw": ("tdrn_dwconv2d", DW_CASES, DW_MODES),
+            "k5": ("tdrn_conv5x5", K5_CASES, CONV_MODES)}
+NEW_FAMILIES = ("convt", "s2", "dw", "k5")
 
 
 def cpad(c):
     return -(-c // 64) * 64
 
 
+def family(case):
+    return next(f for f, (_, cases, _) in FAMILIES.items() if case in cases)
+
+
 def periods(case):
     """elements of one replica in every big layout of the case"""
+    if case in CONVT_CASES:                                      # x, output / grad_output, the NHWC image of x, the space-to-depth image
+        Cin, H, W, Cout = CONVT_CASES[case]
+        return sorted({Cin * H * W, Cout * 4 * H * W, cpad(Cin) * H * W, 4 * cpad(Cout) * H * W})
+    if case in S2_CASES:                                         # x, output, their NHWC images, the zero-inserted image D
+        Cin, H, W, Cout, pad = S2_CASES[case]
+        Ho, Wo, Hd, Wd = (H + 2 * pad - 3) // 2 + 1, (W + 2 * pad - 3) // 2 + 1, H + 2 * pad - 2, W + 2 * pad - 2
+        return sorted({Cin * H * W, Cout * Ho * Wo, cpad(Cin) * H * W, cpad(Cout) * Ho * Wo, cpad(Cout) * Hd * Wd})
+    if case in DW_CASES:                                         # the NCHW planes of x and of the output: no staging
+        C, H, W, s = DW_CASES[case]
+        return sorted({C * H * W, C * ((H - 1) // s + 1) * ((W - 1) // s + 1)})
+    if case in K5_CASES:                                         # x, output, their NHWC images (Ho x Wo = H x W)
+        Cin, H, W, Cout = K5_CASES[case]
+        return sorted({Cin * H * W, Cout * H * W, cpad(Cin) * H * W, cpad(Cout) * H * W})
     if case in CONV_CASES:
         Cin, H, W, Cout, k, pad, dil = CONV_CASES[case]
         Ho, Wo = H + 2 * pad - dil * (k - 1), W + 2 * pad - dil * (k - 1)
@@ -51,7 +91,9 @@ def big_elements(case):
 
 
 def _gen(case):
-    names = sorted(list(BN_CASES) + list(POOL_CASES) + list(L2_CASES) + list(CONV_CASES))
+    # (the later families follow the first four's names, whose seeds stay what they were)
+    names = sorted(list(BN_CASES) + list(POOL_CASES) + list(L2_CASES) + list(CONV_CASES)) + \
+        [c for f in NEW_FAMILIES for c in FAMILIES[f][1]]
     return torch.Generator().manual_seed(names.index(case) + 101)
 
 
@@ -168,34 +210,99 @@ def conv_out_hw(case):
     return H + 2 * pad - dil * (k - 1), W + 2 * pad - dil * (k - 1)
 
 
-@functools.lru_cache(maxsize=None)
-def conv_inputs(case):
-    Cin, H, W, Cout, k, pad, dil = CONV_CASES[case]
-    Ho, Wo = conv_out_hw(case)
-    gen = _gen(case)
-    x = torch.randn(1, Cin, H, W, generator=gen)
-    w = torch.randn(Cout, Cin, k, k, generator=gen) * (Cin * k * k) ** -0.5
-    b = torch.randn(Cout, generator=gen)
-    go = torch.randn(1, Cout, Ho, Wo, generator=gen)
-    return x, w, b, go
-
-
 def conv_round(t, mode):
     return t if CONV_MODES[mode] is None else t.to(CONV_MODES[mode]).float()
 
 
-@functools.lru_cache(maxsize=None)
-def conv_reference(case, mode):
-    """test_gpu_conv_grad.py's oracle on the base: float64 autograd on the inputs as the op uses them (rounded to the 16-bit type
-    first, bias not), and the same convolution on absolute values for the 16-bit bound -> ((y, gx, gw, gb), (Sy, Sgx, Sgw, Sgb)),
-    the parameter gradients times R"""
+# ---------------------------------------------------------------------------------------------
+# the five conv families: conv2d, conv_transpose2d, conv2d at stride 2, depthwise conv2d, conv5x5
+# ---------------------------------------------------------------------------------------------
+def op_dims(case, N=R):
+    """the argument tuple of the family's four entries, in the header's order"""
+    f = family(case)
+    if f == "convt":
+        Cin, H, W, Cout = CONVT_CASES[case]
+        return (N, Cin, H, W, Cout, 2, 2, 2, 2, 0, 0, 0, 0, 1, 1)
+    if f == "s2":
+        Cin, H, W, Cout, pad = S2_CASES[case]
+        return (N, Cin, H, W, Cout, 3, 3, 2, 2, pad, pad, 1, 1)
+    if f == "dw":
+        C, H, W, s = DW_CASES[case]
+        return (N, C, H, W, 3, 3, s, s, 1, 1, 1, 1)
+    if f == "k5":
+        Cin, H, W, Cout = K5_CASES[case]
+        return (N, Cin, H, W, Cout, 5, 5, 1, 1, 2, 2, 1, 1)
     Cin, H, W, Cout, k, pad, dil = CONV_CASES[case]
-    x, w, b, go = conv_inputs(case)
+    return (N, Cin, H, W, Cout, k, k, 1, 1, pad, pad, dil, dil)
+
+
+def op_shapes(case):
+    """base shapes (N = 1) -> (x, weight, output, fan-in of the forward sum)"""
+    f = family(case)
+    if f == "convt":
+        Cin, H, W, Cout = CONVT_CASES[case]
+        return (1, Cin, H, W), (Cin, Cout, 2, 2), (1, Cout, 2 * H, 2 * W), Cin              # one tap per output pixel
+    if f == "s2":
+        Cin, H, W, Cout, pad = S2_CASES[case]
+        return (1, Cin, H, W), (Cout, Cin, 3, 3), (1, Cout, (H + 2 * pad - 3) // 2 + 1, (W + 2 * pad - 3) // 2 + 1), 9 * Cin
+    if f == "dw":
+        C, H, W, s = DW_CASES[case]
+        return (1, C, H, W), (C, 1, 3, 3), (1, C, (H - 1) // s + 1, (W - 1) // s + 1), 1    # (plain randn: test_gpu_dwconv.py)
+    if f == "k5":
+        Cin, H, W, Cout = K5_CASES[case]
+        return (1, Cin, H, W), (Cout, Cin, 5, 5), (1, Cout, H, W), 25 * Cin
+    Cin, H, W, Cout, k, pad, dil = CONV_CASES[case]
+    return (1, Cin, H, W), (Cout, Cin, k, k), (1, Cout) + conv_out_hw(case), Cin * k * k
+
+
+def op_forward(case):
+    """torch's op of the family: (x, w, b) -> y"""
+    f = family(case)
+    if f == "convt":
+        return lambda x, w, b: F.conv_transpose2d(x, w, b, 2)
+    if f == "s2":
+        return lambda x, w, b: F.conv2d(x, w, b, 2, S2_CASES[case][4])
+    if f == "dw":
+        return lambda x, w, b: F.conv2d(x, w, b, DW_CASES[case][3], 1, 1, DW_CASES[case][0])
+    if f == "k5":
+        return lambda x, w, b: F.conv2d(x, w, b, 1, 2)
+    Cin, H, W, Cout, k, pad, dil = CONV_CASES[case]
+    return lambda x, w, b: F.conv2d(x, w, b, 1, pad, dil)
+
+
+def untouched(case):
+    """the input rows and columns that no output pixel touches: grad_input is exactly 0 there"""
+    if case not in S2_CASES:
+        return [], []
+    Cin, H, W, Cout, pad = S2_CASES[case]
+    last_h, last_w = 2 * ((H + 2 * pad - 3) // 2) + 2 - pad, 2 * ((W + 2 * pad - 3) // 2) + 2 - pad
+    return list(range(last_h + 1, H)), list(range(last_w + 1, W))
+
+
+@functools.lru_cache(maxsize=None)
+def op_inputs(case):
+    """base x, weight, bias and grad_output (CPU, fp32): unit-scale normals, the dense families' weights scaled by fan-in^-0.5"""
+    xs, ws, ys, fan_in = op_shapes(case)
+    gen = _gen(case)
+    x = torch.randn(xs, generator=gen)
+    w = torch.randn(ws, generator=gen) * fan_in ** -0.5
+    b = torch.randn(ys[1], generator=gen)
+    go = torch.randn(ys, generator=gen)
+    return x, w, b, go
+
+
+@functools.lru_cache(maxsize=None)
+def op_reference(case, mode):
+    """test_gpu_conv_grad.py's oracle on the base, for any family: float64 autograd on the inputs as the op uses them (rounded to
+    the 16-bit type first, bias not), and the same op on absolute values for the 16-bit bound -> ((y, gx, gw, gb), (Sy, Sgx, Sgw,
+    Sgb)), the parameter gradients times R"""
+    x, w, b, go = op_inputs(case)
     xr, wr, gr = (conv_round(t, mode).double() for t in (x, w, go))
+    op = op_forward(case)
 
     def run(xx, ww, bb, gg):
         xx, ww, bb = (t.clone().requires_grad_(True) for t in (xx, ww, bb))
-        y = F.conv2d(xx, ww, bb, 1, pad, dil)
+        y = op(xx, ww, bb)
         gx, gw, gb = torch.autograd.grad(y, (xx, ww, bb), gg)
         return y.detach(), gx, R * gw, R * gb
     return run(xr, wr, b.double(), gr), run(xr.abs(), wr.abs(), b.double().abs(), gr.abs())

@@ -1,5 +1,5 @@
-"""The training ops (tdrn_hip.h sections i-c, i-d, i-e) on tensors of more than 2^30 elements: past 2^32 bytes in fp32, past 2^31
-bytes in the conv's 16-bit staging.  The ABI admits up to 2^31 elements; conv1_2's activation at batch 32 and 512 pixels has 2^29.
+"""The training ops (tdrn_hip.h sections i-c to i-i) on tensors of more than 2^30 elements: past 2^32 bytes in fp32, past 2^31
+bytes in the convs' 16-bit staging.  The ABI admits up to 2^31 elements; conv1_2's activation at batch 32 and 512 pixels has 2^29.
 
 Construction, cases and float64 references: tests/_train_large_cases.py (80 replicas along N of a base with N = 1, whose period
 divides no power of two; tests/test_train_large_ref.py asserts that without a GPU).  Every element of every replica is compared, on
@@ -12,6 +12,15 @@ Bounds: the per-op files', unchanged.
                                        max(1, max|ref|) of float64, and every replica bit for bit the first one
   l2norm (test_gpu_l2norm.py)          output, gradients: 1e-4 * max(1, max|ref|); norm: 1e-5 relative
   conv2d (test_gpu_conv_grad.py)       fp32: 1e-4 * max(1, max|ref|); bf16: 2e-6 * S elementwise, S the conv of absolute values
+  conv_transpose2d (i-f), conv2d at stride 2 (i-g), conv5x5 (i-i)       conv2d's two bounds (_conv_train_harness.py)
+  dwconv2d (i-h, test_gpu_dwconv.py)   1e-4 * max(1, max|ref|); output and grad_input also bit for bit the first replica in every replica
+                                       (the header fixes their tap order)
+The later families' cases (tests/_train_large_cases.py): convt_big_output (W even: the space-to-depth kernel's 16-byte path; the
+output and the [N][H][W][4][CoPad] staging are big) and convt_big_grad_input (W odd: the dword path; x, grad_input and both stagings);
+s2_big_grad_input (Wo = 252: the dilate kernel's quad path; x, grad_input and the zero-inserted image D are big, and row and column
+505 of grad_input, which no output pixel touches, must be exactly +0.0 in all 80 replicas) and s2_big_dilated (Wo = 251: the dword
+path with Hd = 2 Ho - 1; only D and the x staging are big); dw_500_s1 and dw_501_s2; k5_big_output and k5_big_grad_input.  One
+routine, _conv_family, runs the three entries of any of the five conv families from its entry prefix and dims tuple.
 The sums over the whole batch (parameter gradients, batch statistics) add 2 * 10^7 terms per value, a count at which nobody has
 measured fp32 accumulation.  For those the bound is max(the bound above, 4 x the error of torch's own fp32 GPU reductions of the
 same quantity against the same float64 reference), test_short_training_run_with_pool_and_l2norm_follows_float64's rule, taken
@@ -20,10 +29,23 @@ conv's weight gradient, one fp32 matrix product per tap.  Measured on an MI355X:
 the project bound alone (the conv's fp32 grad_weight), no replicated result more than 0.0135 (l2norm's norm).  torch's reductions
 stay below 0.011 of the project bound, its matrix products of 2 * 10^7 terms do not: 0.39 to 1.32 of it, so for the conv's
 grad_weight the rule allows up to 5.3 times the project bound on some elements.  The library does not need that room.
+The later families, measured on an MI355X, largest share of the project bound (replicated results: fp32 / bf16; sums: ours, torch's):
+  conv_transpose2d  replicated 0.0065 / 0.070   summed 0.1154 (fp32 grad_weight of convt_big_grad_input), torch 0.33 to 1.15
+  conv2d stride 2   replicated 0.0081 / 0.099   summed 0.0124 (fp32 grad_weight of s2_big_grad_input), torch 0.37 to 1.07
+  dwconv2d          replicated 0.0014           summed 0.0063 (grad_bias of dw_500_s1), torch 0.0012 (sums, no matrix product)
+  conv5x5           replicated 0.0158 / 0.080   summed 0.0804 (fp32 grad_weight of k5_big_output), torch 0.49 to 1.73
+so the rule allows up to 6.9 times the project bound on some elements of the 5x5 grad_weight, and again the library needs none of it:
+every sum of these families passes the project bound alone.
 
 Memory: each test works out an upper bound of what it needs and skips only if torch.cuda.mem_get_info() shows less (measured
-peaks: conv fp32 24.3 GiB, bf16 19.5 GiB; batch_norm 19.6 GiB; max_pool 3/1/1 20.8 GiB; l2norm 19.7 GiB); everything is released
-at the end of each test.
+peaks: conv fp32 24.4 GiB, bf16 19.6 GiB; batch_norm 19.6 GiB; max_pool 3/1/1 20.8 GiB; l2norm 19.7 GiB; conv_transpose2d fp32
+24.6 GiB, bf16 19.8 GiB; conv2d stride 2 fp32 24.6 GiB, bf16 19.7 GiB; dwconv2d 19.6 GiB; conv5x5 fp32 24.4 GiB, bf16 19.6 GiB);
+everything is released at the end of each test.
+
+Durations (pytest --durations=0, call phase, one MI355X run of the whole file; the float64 reference on the CPU is part of each):
+conv2d 0.7 to 1.9 s; conv_transpose2d 0.4 to 0.5 s; conv2d stride 2 0.3 to 0.8 s; dwconv2d 0.6 and 0.9 s; conv5x5 1.2 to 1.4 s
+(k5_big_output) and 4.5 to 4.6 s (k5_big_grad_input, whose two float64 passes of a 64 -> 3 channel 5x5 conv over 500 x 500 pixels
+take about 4 s on the CPU; its GPU side takes as long as the other cases').
 """
 import gc
 
@@ -238,25 +260,40 @@ def test_l2norm_past_4gib(case):
 
 
 # ---------------------------------------------------------------------------------------------
-# conv2d
+# the conv families: conv2d (i-c), conv_transpose2d (i-f), conv2d at stride 2 (i-g), depthwise conv2d (i-h), conv5x5 (i-i)
 # ---------------------------------------------------------------------------------------------
-def _conv_dims(case):
-    Cin, H, W, Cout, k, pad, dil = L.CONV_CASES[case]
-    return (R, Cin, H, W, Cout, k, k, 1, 1, pad, pad, dil, dil)
+def _torch_grad_weight(fam, dims, xr, gr, wshape):
+    """torch's fp32 GPU ops on the inputs as the op uses them: per tap one fp32 matrix product over N Ho Wo terms (a convolution
+    through MIOpen would spend ten seconds a shape on its kernel search); depthwise: per tap one product and one sum"""
+    Ho, Wo = gr.shape[2:]
+    if fam == "convt":                          # weight (Cin, Cout, 2, 2): x[h][w] meets grad_output[2h + i][2w + j]
+        taps = [torch.einsum("nchw,ndhw->cd", xr, gr[:, :, i::2, j::2]) for i in range(2) for j in range(2)]
+        return torch.stack(taps, 2).reshape(wshape)
+    if fam == "dw":
+        k, s, pad, dil = dims[4], dims[6], dims[8], dims[10]
+    else:
+        k, s, pad, dil = dims[5], dims[7], dims[9], dims[11]
+    xr = torch.nn.functional.pad(xr, (pad, pad, pad, pad))
+    tap = lambda ky, kx: xr[:, :, ky * dil:ky * dil + s * (Ho - 1) + 1:s, kx * dil:kx * dil + s * (Wo - 1) + 1:s]
+    if fam == "dw":
+        return torch.stack([(gr * tap(ky, kx)).sum((0, 2, 3)) for ky in range(k) for kx in range(k)], 1).reshape(wshape)
+    return torch.stack([torch.einsum("nchw,ndhw->cd", gr, tap(ky, kx)) for ky in range(k) for kx in range(k)], 2).reshape(wshape)
 
 
-def _conv2d(case, mode, nb):
-    Cin, H, W, Cout, k, pad, dil = L.CONV_CASES[case]
+def _conv_family(fam, case, mode, nb):
+    """the three entries of one family on R replicas: prefix and dims from tests/_train_large_cases.py"""
+    prefix, dims = L.FAMILIES[fam][0], L.op_dims(case)
     tag = "%s %s" % (case, mode)
-    ref, S = L.conv_reference(case, mode)
-    lib, dims, dt, st = _lib.lib(), _conv_dims(case), _lib.DTYPES[mode], _lib.current_stream(DEV)
+    ref, S = L.op_reference(case, mode)
+    lib, dt, st = _lib.lib(), _lib.DTYPES[mode], _lib.current_stream(DEV)
+    entry = lambda name: getattr(lib, "%s_%s" % (prefix, name))
     ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
-    xb, w, b, gob = L.conv_inputs(case)
+    xb, w, b, gob = L.op_inputs(case)
     x, go, w, b = _rep(xb), _rep(gob), w.to(DEV), b.to(DEV)
     out, gi, gw, gb = _nan(go.shape), _nan(x.shape), torch.zeros_like(w), torch.zeros_like(b)
-    _lib.check(lib.tdrn_conv2d_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb, st))
-    _lib.check(lib.tdrn_conv2d_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(gi), *dims, dt, _lib.ptr(ws), nb, st))
-    _lib.check(lib.tdrn_conv2d_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt, _lib.ptr(ws), nb, st))
+    _lib.check(entry("forward")(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb, st))
+    _lib.check(entry("backward_input")(_lib.ptr(go), _lib.ptr(w), _lib.ptr(gi), *dims, dt, _lib.ptr(ws), nb, st))
+    _lib.check(entry("backward_parameters")(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt, _lib.ptr(ws), nb, st))
     torch.cuda.synchronize()
     del ws
     for name, big, i in (("output", out, 0), ("grad_input", gi, 1)):
@@ -266,30 +303,61 @@ def _conv2d(case, mode, nb):
             ratio = _worst(big, ref[i], S[i].clamp_min(1e-300))
             print("%s %-12s max|d|/S %.3e  c %.1e" % (tag, name, ratio, C_ACC[mode]))
             assert ratio <= C_ACC[mode], (tag, name, ratio)
-    del out, gi
-    # torch's fp32 GPU ops on the inputs as the op uses them: per tap one fp32 matrix product [Cout, N Ho Wo] x [N Ho Wo, Cin] (a
-    # convolution through MIOpen would spend ten seconds a shape on its kernel search)
+    rows, cols = L.untouched(case)
+    for r in rows:                              # an input row or column that no output pixel touches: exactly +0.0, in every replica
+        assert bool((gi[:, :, r, :].contiguous().view(torch.int32) == 0).all()), "%s: grad_input row %d is not +0.0 everywhere" % (tag, r)
+    for c in cols:
+        assert bool((gi[:, :, :, c].contiguous().view(torch.int32) == 0).all()), "%s: grad_input column %d is not +0.0 everywhere" % (tag, c)
+    if fam == "dw":                             # the header fixes the tap order of forward and backward_input
+        assert _same_bits(out, out[:1]), "%s: a replica's output differs from the first one's" % tag
+        assert _same_bits(gi, gi[:1]), "%s: a replica's grad_input differs from the first one's" % tag
+    del out, gi, big                            # (the loop variable holds grad_input)
     xr, gr = (x, go) if mode == "fp32" else (x.to(L.CONV_MODES[mode]).float(), go.to(L.CONV_MODES[mode]).float())
     del x, go
     gb_t = gr.sum((0, 2, 3))
-    xr = torch.nn.functional.pad(xr, (pad, pad, pad, pad))
-    Ho, Wo = gr.shape[2:]
-    gw_t = torch.stack([torch.einsum("nchw,ndhw->cd", gr, xr[:, :, ky * dil:ky * dil + Ho, kx * dil:kx * dil + Wo])
-                        for ky in range(k) for kx in range(k)], 2).reshape(w.shape)
+    gw_t = _torch_grad_weight(fam, dims, xr, gr, w.shape)
+    del xr, gr
     for name, got, i, t in (("grad_weight", gw, 2, gw_t), ("grad_bias", gb, 3, gb_t)):
         _summed(tag, name, got, ref[i], "fp32" if mode == "fp32" else (C_ACC[mode], S[i]), t)
+
+
+def _conv_family_test(fam, case, mode):
+    xs, _, ys, _ = L.op_shapes(case)
+    nb = getattr(_lib.lib(), L.FAMILIES[fam][0] + "_workspace_bytes")(*L.op_dims(case), _lib.DTYPES[mode])
+    assert nb > 0
+    caller = 2 * 4 * R * (xs[1] * xs[2] * xs[3] + ys[1] * ys[2] * ys[3])       # x, grad_input, output, grad_output
+    _reserve("%s %s" % (case, mode), nb + caller + 2 ** 31)      # + the comparisons' temporaries (torch's side runs after the workspace is freed)
+    try:
+        _conv_family(fam, case, mode, nb)
+    finally:
+        _release("%s %s" % (case, mode))
+
+
+def _cases_and_modes(fam):
+    return [(c, m) for c in L.FAMILIES[fam][1] for m in L.FAMILIES[fam][2]]
 
 
 @pytest.mark.parametrize("mode", list(L.CONV_MODES))
 @pytest.mark.parametrize("case", list(L.CONV_CASES))
 def test_conv2d_past_4gib(case, mode):
-    Cin, H, W, Cout, k, pad, dil = L.CONV_CASES[case]
-    Ho, Wo = L.conv_out_hw(case)
-    nb = _lib.lib().tdrn_conv2d_workspace_bytes(*_conv_dims(case), _lib.DTYPES[mode])
-    assert nb > 0
-    caller = 2 * 4 * R * (Cin * H * W + Cout * Ho * Wo)          # x, grad_input, output, grad_output
-    _reserve("%s %s" % (case, mode), nb + caller + 2 ** 31)      # + the comparisons' temporaries (torch's side runs after the workspace is freed)
-    try:
-        _conv2d(case, mode, nb)
-    finally:
-        _release("%s %s" % (case, mode))
+    _conv_family_test("conv", case, mode)
+
+
+@pytest.mark.parametrize("case,mode", _cases_and_modes("convt"))
+def test_conv_transpose2d_past_4gib(case, mode):
+    _conv_family_test("convt", case, mode)
+
+
+@pytest.mark.parametrize("case,mode", _cases_and_modes("s2"))
+def test_conv2d_strided_past_4gib(case, mode):
+    _conv_family_test("s2", case, mode)
+
+
+@pytest.mark.parametrize("case,mode", _cases_and_modes("dw"))
+def test_dwconv_past_4gib(case, mode):
+    _conv_family_test("dw", case, mode)
+
+
+@pytest.mark.parametrize("case,mode", _cases_and_modes("k5"))
+def test_conv5x5_past_4gib(case, mode):
+    _conv_family_test("k5", case, mode)
