@@ -87,6 +87,17 @@ OP_KINDS = ("first_conv", "conv", "conv_transpose", "depthwise", "maxpool", "l2n
 
 _lib = None
 
+
+def _conv_family(prefix, n):
+    """the four entries of a trainable conv family whose geometry and compute type are `n` ints (backward_parameters has its scale
+    in front of the type)"""
+    tail = [C.c_void_p, C.c_size_t, C.c_void_p]         # workspace, workspace_bytes, stream
+    return {prefix + "_workspace_bytes": (C.c_size_t, [C.c_int] * n),
+            prefix + "_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * n + tail),
+            prefix + "_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * n + tail),
+            prefix + "_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * (n - 1) + [C.c_float, C.c_int] + tail)}
+
+
 _SIGS = {
     "tdrn_version": (C.c_char_p, []),
     "tdrn_error_string": (C.c_char_p, [C.c_int]),
@@ -96,31 +107,11 @@ _SIGS = {
     "tdrn_deform_conv_backward_input": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "tdrn_deform_conv_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_float, C.c_void_p, C.c_size_t,
                                                                                             C.c_void_p]),
-    "tdrn_conv2d_workspace_bytes": (C.c_size_t, [C.c_int] * 14),
-    "tdrn_conv2d_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv2d_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv2d_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p, C.c_size_t,
-                                                                                       C.c_void_p]),
-    "tdrn_conv_transpose2d_workspace_bytes": (C.c_size_t, [C.c_int] * 16),
-    "tdrn_conv_transpose2d_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 16 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv_transpose2d_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 16 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv_transpose2d_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 15 + [C.c_float, C.c_int, C.c_void_p,
-                                                                                                 C.c_size_t, C.c_void_p]),
-    "tdrn_conv2d_strided_workspace_bytes": (C.c_size_t, [C.c_int] * 14),
-    "tdrn_conv2d_strided_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv2d_strided_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv2d_strided_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p,
-                                                                                               C.c_size_t, C.c_void_p]),
-    "tdrn_conv5x5_workspace_bytes": (C.c_size_t, [C.c_int] * 14),
-    "tdrn_conv5x5_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv5x5_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_conv5x5_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p, C.c_size_t,
-                                                                                        C.c_void_p]),
-    "tdrn_dwconv2d_workspace_bytes": (C.c_size_t, [C.c_int] * 13),
-    "tdrn_dwconv2d_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_dwconv2d_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "tdrn_dwconv2d_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 12 + [C.c_float, C.c_int, C.c_void_p, C.c_size_t,
-                                                                                         C.c_void_p]),
+    **_conv_family("tdrn_conv2d", 14),
+    **_conv_family("tdrn_conv_transpose2d", 16),
+    **_conv_family("tdrn_conv2d_strided", 14),
+    **_conv_family("tdrn_conv5x5", 14),
+    **_conv_family("tdrn_dwconv2d", 13),
     "tdrn_batch_norm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "tdrn_batch_norm_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t,
                                                                              C.c_void_p]),

@@ -77,9 +77,10 @@ int deform_bwd_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int 
 }
 
 // The four trainable conv families: dense conv2d at stride 1 (section i-c), ConvTranspose2d(k = 2, s = 2) (section i-f), the 3x3
-// conv at stride 2 (section i-g) and the 5x5 conv (section i-i, conv5x5_plan).  In each the forward and the input gradient are one launch_conv with an fp32 NHWC result, and the
-// weight gradient is one conv_bwd.hip GEMM: a family is its geometry checks and these three descriptions (conv2d_plan, convt2d_plan,
-// convs2_plan); layout, bias staging and the run are shared.
+// conv at stride 2 (section i-g) and the 5x5 conv (section i-i).  In each the forward and the input gradient are one launch_conv with
+// an fp32 NHWC result, and the weight gradient is one conv_bwd.hip GEMM.  The three dense families are one plan (conv_dense_plan) and
+// one set of run bodies (conv_dense_*): a family is the predicate that says which geometries it covers.  ConvTranspose2d has its own
+// description (convt2d_plan) and bodies; layout, bias staging and the run are shared by all four.
 // Workspace: zero page | x NHWC | the grad_output image NHWC (what the input gradient convolves) | the rest, which is either {packed
 // weight, padded bias, NHWC fp32 result, split-K partials of launch_conv} (forward, backward_input; each the larger of the two) or the
 // split-K slabs of the weight gradient (backward_parameters).
@@ -158,58 +159,66 @@ int conv_train_run(const ConvTrainPlan &p, char *ws, bool dgrad, float *out, hip
     return launch_nhwc_to_nchw_f32((const float *)(ws + p.o_out), a.o_bs, a.Cout, out, a.B, a.Cout, a.phases * a.Ho * a.Wo, s);
 }
 
-// dense conv2d (section i-c).  The input gradient is a stride-1 conv over grad_output, kernel rotated and transposed
-// (launch_repack_oihw_dgrad), with pad' = dil (k - 1) - pad and the same dilation.
-int conv2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
-                ConvTrainPlan &p)
+// what every conv plan checks first, each in its own order: positive sizes and no negative padding ...
+bool conv_sizes_ok(int N, int Cin, int Cout, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW)
 {
-    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
-    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
-    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
-    const long long Ho = ((long long)H + 2ll * padH - ((long long)dilH * (kH - 1) + 1)) / dH + 1;
-    const long long Wo = ((long long)W + 2ll * padW - ((long long)dilW * (kW - 1) + 1)) / dW + 1;
-    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
-    if (Ho < 1 || Wo < 1) return TDRN_E_SHAPE;
-    // what the kernels cover: square k = 1 | 3, stride 1, one pad / dilation for both axes, pad <= dil (k - 1) (pad' >= 0)
-    if (kH != kW || (kH != 1 && kH != 3) || dH != 1 || dW != 1 || padH != padW || dilH != dilW) return TDRN_E_UNSUPPORTED;
-    if ((long long)padH > (long long)dilH * (kH - 1)) return TDRN_E_UNSUPPORTED;
-    const int CiPad = conv_bwd_cpad(Cin), CoPad = conv_bwd_cpad(Cout);
-    // 32-bit offsets of the kernels (conv_igemm.hip: elements; conv_bwd.hip: pixels)
-    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * Ho * Wo * CoPad >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    if ((long long)dilH * (kH - 1) >= (1 << 20)) return TDRN_E_UNSUPPORTED;
-    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, kH, padH, dilH, (int)Ho, (int)Wo};
-    ConvArgs &f = p.fwd, &d = p.dgrad;
-    f.B = d.B = N;
-    f.H = d.Ho = H; f.W = d.Wo = W; f.Ho = d.H = (int)Ho; f.Wo = d.W = (int)Wo;
-    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.pad = padH;
-    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin); d.pad = dilH * (kH - 1) - padH;
-    f.kh = f.kw = d.kh = d.kw = kH; f.dil = d.dil = dilH;
-    conv_train_dense_out(f);
-    conv_train_dense_out(d);
-    conv_train_layout(p, dtype);
-    return TDRN_OK;
+    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return false;
+    return N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && padH >= 0 && padW >= 0;
 }
 
-// dense 5x5 conv (section i-i): kH = kW = 5, stride 1, dilation 1, pad 2, so Ho x Wo = H x W.  The forward and the input gradient
-// (pad' = 4 - 2 = 2) are launch_conv at 25 taps, as the engine runs this layer; the weight gradient is conv_bwd.hip's row passes.
-int conv5x5_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
-                 ConvTrainPlan &p)
+// ... a tdrn_dtype ...
+bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
+
+// ... and a dilated window that fits into the padded image
+bool conv_window_fits(int H, int W, int kH, int kW, int padH, int padW, int dilH, int dilW)
 {
-    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
-    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
-    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
-    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
-    if (kH != 5 || kW != 5 || dH != 1 || dW != 1 || padH != 2 || padW != 2 || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
+    return (long long)H + 2ll * padH >= (long long)dilH * (kH - 1) + 1 && (long long)W + 2ll * padW >= (long long)dilW * (kW - 1) + 1;
+}
+
+// The dense families (sections i-c, i-g, i-i): which of the public entry families is asking.  It decides what is covered, nothing else:
+// the three are disjoint, and a geometry outside the asking family is unsupported even where another family covers it.
+enum DenseFamily { DENSE_STRIDE1, DENSE_STRIDE2, DENSE_5X5 };
+
+// One plan for the dense families.  The input gradient is a stride-1 conv with pad' = dil (k - 1) - pad and the same dilation, kernel
+// rotated and transposed (launch_repack_oihw_dgrad), over D: grad_output itself at stride 1, its zero-inserted image at stride 2,
+// (N, CoPad, Hd, Wd) -> (Cin, H, W).  Hd = H + 2 pad - dil (k - 1) is the stride-1 output size, so Hd = Ho at stride 1; at stride 2
+// backward_parameters keeps the plain grad_output image in D's place (Hd >= Ho, Wd >= Wo: it fits).
+int conv_dense_plan(DenseFamily family, int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH,
+                    int dilW, int dtype, ConvTrainPlan &p)
+{
+    if (!conv_sizes_ok(N, Cin, Cout, H, W, kH, kW, dH, dW, padH, padW, dilH, dilW)) return TDRN_E_SHAPE;
+    if (!dtype_ok(dtype)) return TDRN_E_ARG;
+    if (!conv_window_fits(H, W, kH, kW, padH, padW, dilH, dilW)) return TDRN_E_SHAPE;
+    switch (family) {       // what the kernels cover
+        case DENSE_STRIDE1:  // square k = 1 | 3, stride 1, one pad / dilation for both axes, pad <= dil (k - 1) (pad' >= 0)
+            if (kH != kW || (kH != 1 && kH != 3) || dH != 1 || dW != 1 || padH != padW || dilH != dilW) return TDRN_E_UNSUPPORTED;
+            if ((long long)padH > (long long)dilH * (kH - 1)) return TDRN_E_UNSUPPORTED;
+            break;
+        case DENSE_STRIDE2:  // k = 3 at stride 2, dilation 1, one pad <= 2 for both axes (pad' >= 0).  Stride 1 is DENSE_STRIDE1's
+            if (kH != 3 || kW != 3 || dH != 2 || dW != 2 || dilH != 1 || dilW != 1 || padH != padW || padH > 2) return TDRN_E_UNSUPPORTED;
+            break;
+        case DENSE_5X5:      // kH = kW = 5, stride 1, dilation 1, pad 2, so Ho x Wo = H x W; 25 taps, as the engine runs this layer
+            if (kH != 5 || kW != 5 || dH != 1 || dW != 1 || padH != 2 || padW != 2 || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
+            break;
+    }
+    // so from here on one k, stride, pad and dilation serve both axes
+    const int k = kH, stride = dH, pad = padH, dil = dilH;
+    const long long reach = (long long)dil * (k - 1);
+    const long long Hd = (long long)H + 2ll * pad - reach, Wd = (long long)W + 2ll * pad - reach;
+    const long long Ho = (Hd - 1) / stride + 1, Wo = (Wd - 1) / stride + 1;
     const int CiPad = conv_bwd_cpad(Cin), CoPad = conv_bwd_cpad(Cout);
-    // 32-bit offsets of the kernels (conv_igemm.hip: elements; conv_bwd.hip: pixels), as conv2d_plan
-    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * H * W * CoPad >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, 5, 2, 1, H, W};
+    // 32-bit offsets of the kernels (conv_igemm.hip: elements of its input; conv_bwd.hip: pixels): every padded tensor below 2^31
+    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * Ho * Wo * CoPad >= (1ll << 31) ||
+        (long long)N * Hd * Wd * CoPad >= (1ll << 31))
+        return TDRN_E_UNSUPPORTED;
+    if (reach >= (1 << 20)) return TDRN_E_UNSUPPORTED;      // only stride 1 has a dilation to choose
+    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, k, pad, dil, (int)Ho, (int)Wo, stride};
     ConvArgs &f = p.fwd, &d = p.dgrad;
     f.B = d.B = N;
-    f.H = f.Ho = d.H = d.Ho = H; f.W = f.Wo = d.W = d.Wo = W;
-    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout);
-    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin);
-    f.kh = f.kw = d.kh = d.kw = 5; f.pad = d.pad = 2;
+    f.H = d.Ho = H; f.W = d.Wo = W; f.Ho = (int)Ho; f.Wo = (int)Wo; d.H = (int)Hd; d.W = (int)Wd;
+    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.pad = pad; f.stride = stride;
+    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin); d.pad = (int)reach - pad;
+    f.kh = f.kw = d.kh = d.kw = k; f.dil = d.dil = dil;
     conv_train_dense_out(f);
     conv_train_dense_out(d);
     conv_train_layout(p, dtype);
@@ -222,9 +231,8 @@ int conv5x5_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH,
 int convt2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int opadH, int opadW, int dilH,
                  int dilW, int dtype, ConvTrainPlan &p)
 {
-    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
-    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0 || opadH < 0 || opadW < 0) return TDRN_E_SHAPE;
-    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    if (!conv_sizes_ok(N, Cin, Cout, H, W, kH, kW, dH, dW, padH, padW, dilH, dilW) || opadH < 0 || opadW < 0) return TDRN_E_SHAPE;
+    if (!dtype_ok(dtype)) return TDRN_E_ARG;
     // what the kernels cover: the four taps of a 2x2 kernel at stride 2 write four disjoint phases of the output
     if (kH != 2 || kW != 2 || dH != 2 || dW != 2 || padH || padW || opadH || opadW || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
     const long long CiPad = ((long long)Cin + kChanPad - 1) / kChanPad * kChanPad, CoPad = ((long long)Cout + kChanPad - 1) / kChanPad * kChanPad;
@@ -246,39 +254,6 @@ int convt2d_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH,
     return TDRN_OK;
 }
 
-// dense 3x3 stride-2 conv (section i-g).  The input gradient is a stride-1 conv with pad' = 2 - pad over the zero-inserted image D of
-// grad_output, (N, CoPad, Hd, Wd) -> (Cin, H, W), kernel rotated and transposed; backward_parameters keeps the plain grad_output image
-// in D's place (Hd >= Ho, Wd >= Wo: it fits).
-int convs2_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
-                ConvTrainPlan &p)
-{
-    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
-    if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
-    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
-    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
-    // what the kernels cover: k = 3 at stride 2, dilation 1, one pad <= 2 for both axes (pad' >= 0).  Stride 1 is section i-c's: the
-    // two families are disjoint.
-    if (kH != 3 || kW != 3 || dH != 2 || dW != 2 || dilH != 1 || dilW != 1 || padH != padW || padH > 2) return TDRN_E_UNSUPPORTED;
-    const long long Ho = ((long long)H + 2 * padH - 3) / 2 + 1, Wo = ((long long)W + 2 * padW - 3) / 2 + 1;
-    const long long Hd = (long long)H + 2 * padH - 2, Wd = (long long)W + 2 * padW - 2;
-    const int CiPad = conv_bwd_cpad(Cin), CoPad = conv_bwd_cpad(Cout);
-    // 32-bit offsets of the kernels (conv_igemm.hip: elements of its input; conv_bwd.hip: pixels): every padded tensor below 2^31
-    if ((long long)N * H * W * CiPad >= (1ll << 31) || (long long)N * Ho * Wo * CoPad >= (1ll << 31) ||
-        (long long)N * Hd * Wd * CoPad >= (1ll << 31))
-        return TDRN_E_UNSUPPORTED;
-    p.wg = ConvBwdGeom{N, Cin, H, W, Cout, 3, padH, 1, (int)Ho, (int)Wo, 2};
-    ConvArgs &f = p.fwd, &d = p.dgrad;
-    f.B = d.B = N;
-    f.H = d.Ho = H; f.W = d.Wo = W; f.Ho = (int)Ho; f.Wo = (int)Wo; d.H = (int)Hd; d.W = (int)Wd;
-    f.Cin = CiPad; f.Cout = Cout; f.Npad = conv_n_pad(Cout); f.pad = padH; f.stride = 2;
-    d.Cin = CoPad; d.Cout = Cin; d.Npad = conv_n_pad(Cin); d.pad = 2 - padH;
-    f.kh = f.kw = d.kh = d.kw = 3;
-    conv_train_dense_out(f);
-    conv_train_dense_out(d);
-    conv_train_layout(p, dtype);
-    return TDRN_OK;
-}
-
 // depthwise 3x3 conv (section i-h): fp32 NCHW planes straight through dwconv_train.hip, no ConvTrainPlan.  The workspace holds the
 // weight gradient's partials and nothing else; one size serves the three entries.
 struct DwConvPlan {
@@ -288,10 +263,9 @@ struct DwConvPlan {
 
 int dwconv2d_plan(int N, int C, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype, DwConvPlan &p)
 {
-    if (kW <= 0 || kH <= 0 || dW <= 0 || dH <= 0 || dilW <= 0 || dilH <= 0) return TDRN_E_SHAPE;
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || padH < 0 || padW < 0) return TDRN_E_SHAPE;
-    if ((long long)H + 2ll * padH < (long long)dilH * (kH - 1) + 1 || (long long)W + 2ll * padW < (long long)dilW * (kW - 1) + 1) return TDRN_E_SHAPE;
-    if (dtype < 0 || dtype > 2) return TDRN_E_ARG;
+    if (!conv_sizes_ok(N, C, C, H, W, kH, kW, dH, dW, padH, padW, dilH, dilW)) return TDRN_E_SHAPE;
+    if (!conv_window_fits(H, W, kH, kW, padH, padW, dilH, dilW)) return TDRN_E_SHAPE;
+    if (!dtype_ok(dtype)) return TDRN_E_ARG;
     // what the kernels cover: k = 3, one stride of 1 or 2 for both axes, pad 1, dilation 1, fp32 (the op is bandwidth-bound, and the
     // inference engine keeps depthwise weights in fp32 in its 16-bit plans too)
     if (kH != 3 || kW != 3 || dH != dW || dH > 2 || padH != 1 || padW != 1 || dilH != 1 || dilW != 1) return TDRN_E_UNSUPPORTED;
@@ -309,14 +283,13 @@ int dwconv2d_plan(int N, int C, int H, int W, int kH, int kW, int dH, int dW, in
     return TDRN_OK;
 }
 
-// BatchNorm2d (section i-d): the geometry checks of the query and of both entries
-int batch_norm_plan(int N, int C, int H, int W, size_t &bytes)
+// BatchNorm2d (section i-d) and L2Norm (section i-e): the geometry checks of their queries and entries
+int nchw_plan(int N, int C, int H, int W)
 {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
     // 32-bit element offsets of the kernels
     const long long HW = (long long)H * W, NC = (long long)N * C;
     if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    bytes = batch_norm_workspace_bytes(N, C, H * W);
     return TDRN_OK;
 }
 
@@ -347,16 +320,6 @@ int max_pool_plan(int N, int C, int H, int W, int k, int s, int p, int ceil_mode
     if (!pool_geometry_supported(k, s, p)) return TDRN_E_UNSUPPORTED;
     if ((long long)N * C * H * W >= (1ll << 31) || (long long)N * C >= (1ll << 31) || (long long)H * W >= (1ll << 31))
         return TDRN_E_UNSUPPORTED;
-    return TDRN_OK;
-}
-
-// L2Norm (section i-e): the geometry checks of the query and of both entries
-int l2norm_plan(int N, int C, int H, int W, size_t &bytes)
-{
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
-    const long long HW = (long long)H * W, NC = (long long)N * C;
-    if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    bytes = l2norm_workspace_bytes(N, C, H * W);
     return TDRN_OK;
 }
 
@@ -470,11 +433,11 @@ int tdrn_deform_conv_backward_parameters(const float *input, const float *offset
     return launch_deform_bwd_weight(b.g, in_nhwc, offset, grad_output, (float *)(ws + b.o_slab), grad_weight, scale, s);
 }
 
-// The entries of the trainable conv families (ConvTrainPlan above): pointer check, plan, conv_train_begin, then each one's own
-// layout conversion(s), weight packing and tail.
+// The entries of the trainable conv families (ConvTrainPlan above): pointer check, plan, then conv_train_begin, layout conversion(s),
+// weight packing and tail -- for the dense families in the three bodies below, for ConvTranspose2d in its entries.
 namespace {
 
-// what the two stride-1 dense families (i-c, i-i) do once their plan has spoken: conversions, packing, one launch
+// what the dense families (i-c, i-g, i-i) do once their plan has spoken: conversions, packing, one launch
 int conv_dense_forward(int plan_rc, const ConvTrainPlan &p, const float *input, const float *weight, const float *bias, float *output,
                        int Cin, int dtype, void *workspace, size_t workspace_bytes, hipStream_t s)
 {
@@ -493,7 +456,10 @@ int conv_dense_backward_input(int plan_rc, const ConvTrainPlan &p, const float *
     char *ws = (char *)workspace;
     TDRN_TRY(conv_train_begin(plan_rc, p, workspace, workspace_bytes, s));
     const ConvArgs &d = p.dgrad;
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, d.B, p.wg.Cout, p.wg.Ho * p.wg.Wo, d.Cin, dtype, s));
+    if (p.wg.stride == 2)   // the zero-inserted image: the kernel stores every element of it, zeros included
+        TDRN_TRY(launch_nchw_to_nhwc_dilate2(grad_output, ws + p.o_go, d.B, p.wg.Cout, p.wg.Ho, p.wg.Wo, d.H, d.W, dtype, s));
+    else
+        TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, d.B, p.wg.Cout, p.wg.Ho * p.wg.Wo, d.Cin, dtype, s));
     TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, p.wg.Cout, p.wg.Cin, d.Npad, d.kh * d.kw, dtype, s));
     TDRN_TRY(conv_train_bias(d, ws + p.o_bias, nullptr, s));
     return conv_train_run(p, ws, true, grad_input, s);
@@ -515,7 +481,7 @@ size_t tdrn_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int k
                                    int dilationH, int dilationW, tdrn_dtype compute)
 {
     ConvTrainPlan p;
-    return conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
+    return conv_dense_plan(DENSE_STRIDE1, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
 }
 
 int tdrn_conv2d_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W, int Cout,
@@ -524,7 +490,7 @@ int tdrn_conv2d_forward(const float *input, const float *weight, const float *bi
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
     ConvTrainPlan p;
-    const int rc = conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    const int rc = conv_dense_plan(DENSE_STRIDE1, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_forward(rc, p, input, weight, bias, output, Cin, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -534,7 +500,7 @@ int tdrn_conv2d_backward_input(const float *grad_output, const float *weight, fl
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
     ConvTrainPlan p;
-    const int rc = conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    const int rc = conv_dense_plan(DENSE_STRIDE1, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_backward_input(rc, p, grad_output, weight, grad_input, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -544,17 +510,16 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
     ConvTrainPlan p;
-    const int rc = conv2d_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    const int rc = conv_dense_plan(DENSE_STRIDE1, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_backward_parameters(rc, p, input, grad_output, grad_weight, grad_bias, scale, compute, workspace, workspace_bytes,
                                           (hipStream_t)stream);
 }
 
-// section i-i: the same three bodies under conv5x5_plan
 size_t tdrn_conv5x5_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
                                     int dilationH, int dilationW, tdrn_dtype compute)
 {
     ConvTrainPlan p;
-    return conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
+    return conv_dense_plan(DENSE_5X5, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
 }
 
 int tdrn_conv5x5_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W, int Cout,
@@ -563,7 +528,7 @@ int tdrn_conv5x5_forward(const float *input, const float *weight, const float *b
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
     ConvTrainPlan p;
-    const int rc = conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    const int rc = conv_dense_plan(DENSE_5X5, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_forward(rc, p, input, weight, bias, output, Cin, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -573,7 +538,7 @@ int tdrn_conv5x5_backward_input(const float *grad_output, const float *weight, f
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
     ConvTrainPlan p;
-    const int rc = conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    const int rc = conv_dense_plan(DENSE_5X5, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_backward_input(rc, p, grad_output, weight, grad_input, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -583,7 +548,7 @@ int tdrn_conv5x5_backward_parameters(const float *input, const float *grad_outpu
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
     ConvTrainPlan p;
-    const int rc = conv5x5_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    const int rc = conv_dense_plan(DENSE_5X5, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_backward_parameters(rc, p, input, grad_output, grad_weight, grad_bias, scale, compute, workspace, workspace_bytes,
                                           (hipStream_t)stream);
 }
@@ -652,7 +617,7 @@ size_t tdrn_conv2d_strided_workspace_bytes(int N, int Cin, int H, int W, int Cou
                                            int dilationH, int dilationW, tdrn_dtype compute)
 {
     ConvTrainPlan p;
-    return convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
+    return conv_dense_plan(DENSE_STRIDE2, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p) == TDRN_OK ? p.total : 0;
 }
 
 int tdrn_conv2d_strided_forward(const float *input, const float *weight, const float *bias, float *output, int N, int Cin, int H, int W,
@@ -661,14 +626,8 @@ int tdrn_conv2d_strided_forward(const float *input, const float *weight, const f
 {
     if (!input || !weight || !output) return TDRN_E_ARG;
     ConvTrainPlan p;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    TDRN_TRY(conv_train_begin(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
-                              workspace_bytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
-    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, Cout, p.fwd.Npad, Cin, 9, 1, p.fwd.Cin, compute, s));
-    TDRN_TRY(conv_train_bias(p.fwd, ws + p.o_bias, bias, s));
-    return conv_train_run(p, ws, false, output, s);
+    const int rc = conv_dense_plan(DENSE_STRIDE2, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_forward(rc, p, input, weight, bias, output, Cin, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int tdrn_conv2d_strided_backward_input(const float *grad_output, const float *weight, float *grad_input, int N, int Cin, int H, int W,
@@ -677,15 +636,8 @@ int tdrn_conv2d_strided_backward_input(const float *grad_output, const float *we
 {
     if (!grad_output || !weight || !grad_input) return TDRN_E_ARG;
     ConvTrainPlan p;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    TDRN_TRY(conv_train_begin(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
-                              workspace_bytes, s));
-    // the zero-inserted image: the kernel stores every element of it, zeros included
-    TDRN_TRY(launch_nchw_to_nhwc_dilate2(grad_output, ws + p.o_go, N, Cout, p.wg.Ho, p.wg.Wo, p.dgrad.H, p.dgrad.W, compute, s));
-    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, p.dgrad.Npad, 9, compute, s));
-    TDRN_TRY(conv_train_bias(p.dgrad, ws + p.o_bias, nullptr, s));
-    return conv_train_run(p, ws, true, grad_input, s);
+    const int rc = conv_dense_plan(DENSE_STRIDE2, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_backward_input(rc, p, grad_output, weight, grad_input, compute, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int tdrn_conv2d_strided_backward_parameters(const float *input, const float *grad_output, float *grad_weight, float *grad_bias, int N,
@@ -695,13 +647,9 @@ int tdrn_conv2d_strided_backward_parameters(const float *input, const float *gra
 {
     if (!input || !grad_output || !grad_weight) return TDRN_E_ARG;
     ConvTrainPlan p;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    TDRN_TRY(conv_train_begin(convs2_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p), p, workspace,
-                              workspace_bytes, s));
-    TDRN_TRY(launch_nchw_to_nhwc(input, ws + p.o_x, N, Cin, H * W, p.fwd.Cin, compute, s));
-    TDRN_TRY(launch_nchw_to_nhwc(grad_output, ws + p.o_go, N, Cout, p.wg.Ho * p.wg.Wo, p.dgrad.Cin, compute, s));
-    return launch_conv_wgrad(p.wg, ws + p.o_x, ws + p.o_go, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, compute, s);
+    const int rc = conv_dense_plan(DENSE_STRIDE2, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
+    return conv_dense_backward_parameters(rc, p, input, grad_output, grad_weight, grad_bias, scale, compute, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
 }
 
 size_t tdrn_dwconv2d_workspace_bytes(int N, int C, int H, int W, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
@@ -747,8 +695,7 @@ int tdrn_dwconv2d_backward_parameters(const float *input, const float *grad_outp
 
 size_t tdrn_batch_norm_workspace_bytes(int N, int C, int H, int W)
 {
-    size_t bytes;
-    return batch_norm_plan(N, C, H, W, bytes) == TDRN_OK ? bytes : 0;
+    return nchw_plan(N, C, H, W) == TDRN_OK ? batch_norm_workspace_bytes(N, C, H * W) : 0;
 }
 
 int tdrn_batch_norm_forward(const float *input, const float *weight, const float *bias, float *running_mean, float *running_var,
@@ -760,11 +707,10 @@ int tdrn_batch_norm_forward(const float *input, const float *weight, const float
     if (off_dword(input) || off_dword(weight) || off_dword(bias) || off_dword(running_mean) || off_dword(running_var) || off_dword(output) ||
         off_dword(save_mean) || off_dword(save_invstd) || off_dword(workspace))
         return TDRN_E_ARG;
-    size_t bytes;
-    TDRN_TRY(batch_norm_plan(N, C, H, W, bytes));
+    TDRN_TRY(nchw_plan(N, C, H, W));
     if (training && (long long)N * H * W == 1) return TDRN_E_SHAPE;     // one value per channel has no variance
     if (!(eps > 0.f) || !(momentum >= 0.f && momentum <= 1.f)) return TDRN_E_ARG;
-    if (!workspace || workspace_bytes < bytes) return TDRN_E_WORKSPACE;
+    if (!workspace || workspace_bytes < batch_norm_workspace_bytes(N, C, H * W)) return TDRN_E_WORKSPACE;
     return launch_batch_norm_forward(input, weight, bias, running_mean, running_var, output, save_mean, save_invstd, N, C, H * W,
                                      training != 0, momentum, eps, relu != 0, workspace, (hipStream_t)stream);
 }
@@ -778,10 +724,9 @@ int tdrn_batch_norm_backward(const float *input, const float *grad_output, const
     if (off_dword(input) || off_dword(grad_output) || off_dword(weight) || off_dword(bias) || off_dword(save_mean) || off_dword(save_invstd) ||
         off_dword(grad_input) || off_dword(grad_weight) || off_dword(grad_bias) || off_dword(workspace))
         return TDRN_E_ARG;
-    size_t bytes;
-    TDRN_TRY(batch_norm_plan(N, C, H, W, bytes));
+    TDRN_TRY(nchw_plan(N, C, H, W));
     if (training && (long long)N * H * W == 1) return TDRN_E_SHAPE;
-    if (!workspace || workspace_bytes < bytes) return TDRN_E_WORKSPACE;
+    if (!workspace || workspace_bytes < batch_norm_workspace_bytes(N, C, H * W)) return TDRN_E_WORKSPACE;
     return launch_batch_norm_backward(input, grad_output, weight, bias, save_mean, save_invstd, grad_input, grad_weight, grad_bias, N, C,
                                       H * W, training != 0, relu != 0, scale, workspace, (hipStream_t)stream);
 }
@@ -811,8 +756,7 @@ int tdrn_max_pool_backward(const float *grad_output, const unsigned char *code, 
 
 size_t tdrn_l2norm_workspace_bytes(int N, int C, int H, int W)
 {
-    size_t bytes;
-    return l2norm_plan(N, C, H, W, bytes) == TDRN_OK ? bytes : 0;
+    return nchw_plan(N, C, H, W) == TDRN_OK ? l2norm_workspace_bytes(N, C, H * W) : 0;
 }
 
 int tdrn_l2norm_forward(const float *input, const float *weight, float *output, float *norm, int N, int C, int H, int W, float eps,
@@ -820,8 +764,7 @@ int tdrn_l2norm_forward(const float *input, const float *weight, float *output, 
 {
     if (!input || !weight || !output || !(eps > 0.f)) return TDRN_E_ARG;
     if (off_dword(input) || off_dword(weight) || off_dword(output) || off_dword(norm)) return TDRN_E_ARG;
-    size_t bytes;
-    TDRN_TRY(l2norm_plan(N, C, H, W, bytes));
+    TDRN_TRY(nchw_plan(N, C, H, W));
     return launch_l2norm_forward(input, weight, output, norm, N, C, H * W, eps, (hipStream_t)stream);
 }
 
@@ -833,10 +776,9 @@ int tdrn_l2norm_backward(const float *input, const float *grad_output, const flo
     if (off_dword(input) || off_dword(grad_output) || off_dword(weight) || off_dword(norm) || off_dword(grad_input) || off_dword(grad_weight) ||
         off_dword(workspace))
         return TDRN_E_ARG;
-    size_t bytes;
-    TDRN_TRY(l2norm_plan(N, C, H, W, bytes));
+    TDRN_TRY(nchw_plan(N, C, H, W));
     // the workspace holds grad_weight's partial sums and nothing else
-    if (grad_weight && (!workspace || workspace_bytes < bytes)) return TDRN_E_WORKSPACE;
+    if (grad_weight && (!workspace || workspace_bytes < l2norm_workspace_bytes(N, C, H * W))) return TDRN_E_WORKSPACE;
     return launch_l2norm_backward(input, grad_output, weight, norm, grad_input, grad_weight, N, C, H * W, eps, scale, workspace,
                                   (hipStream_t)stream);
 }

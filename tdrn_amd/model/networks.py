@@ -248,6 +248,22 @@ def _conv2d_require_cuda(input, weight, bias):
         _lib.require_cuda(bias, "bias")
 
 
+def _conv_check(input, weight, bias):
+    """what every conv op checks before it touches the library: a 4-D input, everything on the device"""
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _conv2d_require_cuda(input, weight, bias)
+
+
+def _conv_reset_parameters(weight, bias):
+    """nn.Conv2d's default init of an (out, in, kH, kW) weight and its bias (or None)"""
+    nn.init.kaiming_uniform_(weight, a=math.sqrt(5))
+    if bias is not None:
+        fan_in = weight.shape[1] * weight.shape[2] * weight.shape[3]
+        bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
+        nn.init.uniform_(bias, -bound, bound)
+
+
 def _conv_workspace(lib, fam, dims, dt, device):
     return _workspace(getattr(lib, fam.prefix + "_workspace_bytes"), dims + (dt,), device,
                       "%s: geometry outside what libtdrn_hip covers (%s): %s = %r", fam.name, fam.covered, fam.dim_names, dims)
@@ -325,9 +341,7 @@ class Conv2dFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, weight, bias=None, padding=0, dilation=1, compute="fp32", stride=1):
-        if input.dim() != 4:
-            raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-        _conv2d_require_cuda(input, weight, bias)
+        _conv_check(input, weight, bias)
         return _conv_function_forward(ctx, _CONV2D[_conv2d_family(stride)], input, weight, bias, (padding, dilation, stride), compute)
 
     @staticmethod
@@ -342,9 +356,7 @@ def conv2d(input, weight, bias=None, padding=0, dilation=1, compute="fp32", stri
     conv of the MobileNet trunk); another stride raises.  With grad mode off, or when nothing requires grad, only the forward runs
     and the output has no grad_fn."""
     fam = _CONV2D[_conv2d_family(stride)]   # a stride the library does not cover raises before anything else
-    if input is not None and input.dim() != 4:
-        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-    _conv2d_require_cuda(input, weight, bias)
+    _conv_check(input, weight, bias)
     return _conv_dispatch(Conv2dFunction, fam, input, weight, bias, (padding, dilation, stride), compute, padding, dilation, compute, stride)
 
 
@@ -361,22 +373,16 @@ class Conv2d(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        if self.bias is not None:
-            fan_in = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
-            bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
-            nn.init.uniform_(self.bias, -bound, bound)
+        _conv_reset_parameters(self.weight, self.bias)
 
     def forward(self, input):
         return conv2d(input, self.weight, self.bias, self.padding, self.dilation, self.compute, self.stride)
 
 
 def _conv_transpose2d_check(input, weight, bias):
-    if input is not None and input.dim() != 4:
-        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
     if weight.dim() != 4:
         raise ValueError("Expected a 4D weight (in_channels, out_channels, kH, kW), got {}D.".format(weight.dim()))
-    _conv2d_require_cuda(input, weight, bias)
+    _conv_check(input, weight, bias)
 
 
 class ConvTranspose2dFunction(torch.autograd.Function):
@@ -457,12 +463,6 @@ _DEPTHWISE = _ConvFamily("depthwise_conv2d", "tdrn_dwconv2d", _depthwise_geometr
                          "N, C, H, W, kH, kW, dH, dW, padH, padW, dilH, dilW")
 
 
-def _depthwise_check(input, weight, bias):
-    if input is not None and input.dim() != 4:
-        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-    _conv2d_require_cuda(input, weight, bias)
-
-
 class DepthwiseConv2dFunction(torch.autograd.Function):
     """Depthwise 3x3 conv (groups = channels, pad 1, stride 1 or 2) with gradients: forward through tdrn_dwconv2d_forward, backward
     through tdrn_dwconv2d_backward_input (when the input needs a gradient) and tdrn_dwconv2d_backward_parameters (weight and bias
@@ -474,7 +474,7 @@ class DepthwiseConv2dFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, weight, bias=None, stride=1, padding=1):
-        _depthwise_check(input, weight, bias)
+        _conv_check(input, weight, bias)
         return _conv_function_forward(ctx, _DEPTHWISE, input, weight, bias, (stride, padding), "fp32")
 
     @staticmethod
@@ -488,7 +488,7 @@ def depthwise_conv2d(input, weight, bias=None, stride=1, padding=1):
     tensors in, NCHW fp32 out), differentiable in input, weight and bias: the depthwise conv of conv_dw.  `stride` is 1 or 2,
     `padding` 1; anything else raises.  With grad mode off, or when nothing requires grad, only the forward runs and the output has
     no grad_fn."""
-    _depthwise_check(input, weight, bias)
+    _conv_check(input, weight, bias)
     return _conv_dispatch(DepthwiseConv2dFunction, _DEPTHWISE, input, weight, bias, (stride, padding), "fp32", stride, padding)
 
 
@@ -529,12 +529,6 @@ _CONV5X5 = _ConvFamily("conv5x5", "tdrn_conv5x5", _conv5x5_geometry, 0, _CONV5X5
                        "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW")
 
 
-def _conv5x5_check(input, weight, bias):
-    if input is not None and input.dim() != 4:
-        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-    _conv2d_require_cuda(input, weight, bias)
-
-
 class Conv5x5Function(torch.autograd.Function):
     """Dense 5x5 conv (pad 2, stride 1) with gradients: forward through tdrn_conv5x5_forward, backward through
     tdrn_conv5x5_backward_input (when the input needs a gradient) and tdrn_conv5x5_backward_parameters (weight and bias gradients,
@@ -546,7 +540,7 @@ class Conv5x5Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, weight, bias=None, compute="fp32"):
-        _conv5x5_check(input, weight, bias)
+        _conv_check(input, weight, bias)
         return _conv_function_forward(ctx, _CONV5X5, input, weight, bias, (), compute)
 
     @staticmethod
@@ -559,7 +553,7 @@ def conv5x5(input, weight, bias=None, compute="fp32"):
     """F.conv2d(input, weight, bias, padding=2) for a (Cout, Cin, 5, 5) weight on libtdrn_hip (NCHW fp32 CUDA tensors in, NCHW fp32
     out), differentiable in input, weight and bias: the second ODM heads of refinedet_vgg's multihead.  With grad mode off, or when
     nothing requires grad, only the forward runs and the output has no grad_fn."""
-    _conv5x5_check(input, weight, bias)
+    _conv_check(input, weight, bias)
     return _conv_dispatch(Conv5x5Function, _CONV5X5, input, weight, bias, (), compute, compute)
 
 
@@ -574,11 +568,7 @@ class Conv5x5(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        if self.bias is not None:
-            fan_in = self.in_channels * 25
-            bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
-            nn.init.uniform_(self.bias, -bound, bound)
+        _conv_reset_parameters(self.weight, self.bias)
 
     def forward(self, input):
         return conv5x5(input, self.weight, self.bias, self.compute)

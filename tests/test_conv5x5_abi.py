@@ -1,15 +1,16 @@
 """C ABI of the dense 5x5 conv with gradients (tdrn_hip.h section i-i), no GPU needed: the workspace query and the entries decide
-every error before any launch, and the plan behind the query is restated here in plain Python.
+every error before any launch, and the plan behind the query is restated in plain Python (test_conv_grad_variants.py's dense_*, the
+one restatement of the three dense families, called here at k = 5, stride 1, pad 2, dilation 1).
 
 The forward and the input gradient (pad' = 4 - 2 = 2) are launch_conv at 25 taps; the weight gradient is conv_wgrad_kernel<DT, 5, 5>,
 five kernel-row passes side by side, with a split rule of its own that counts the five workgroups of a split.  conv_igemm.hip's rules
-are test_conv_grad_variants.py's.
+are test_conv_grad_variants.py's too.
 """
 import pytest
 import torch
 
 import test_gpu_conv5x5 as G
-from test_conv_grad_variants import ES, ZERO_PAGE, cdiv, cpad, n_pad, splitk, tile, up
+from test_conv_grad_variants import ES, ZERO_PAGE, cdiv, cpad, dense_problem, dense_wgrad_splits, dense_workspace_bytes, splitk, tile, up
 from tdrn_amd import _lib
 from tdrn_amd.model import networks
 
@@ -187,39 +188,25 @@ def test_cpu_tensors_and_other_weights_raise():
 
 
 # ---- the plan, restated ---------------------------------------------------------------------------------------------------------
+def _dense(case):
+    """a case as the arguments of test_conv_grad_variants.py's dense_*: N, Cin, H, W, Cout, k = 5, stride 1, pad 2, dil 1"""
+    return G.CASES[case] + (5, 1, 2, 1)
+
+
 def problem(case, dgrad):
-    """the implicit GEMM of the forward or of the input gradient, both 5x5 at pad 2 over H x W pixels"""
-    N, Cin, H, W, Cout = G.CASES[case]
-    ci, co = (Cout, Cin) if dgrad else (Cin, Cout)
-    return dict(B=N, H=H, W=W, Cin=cpad(ci), Ho=H, Wo=W, Cout=co, Npad=n_pad(co), k=5, pad=2)
+    """the implicit GEMM of the forward or of the input gradient, both 5x5 at pad 2 (pad' = 4 - 2) over H x W pixels"""
+    p = dense_problem(*_dense(case), dgrad)
+    assert (p["H"], p["W"], p["Ho"], p["Wo"], p["pad"]) == G.CASES[case][2:4] * 2 + (2,)
+    return p
 
 
 def wgrad_splits(case):
     """conv_wgrad_splits at k = 5: five workgroups (the kernel rows) per split and tile -> (splits, per_split, M)"""
-    N, Cin, H, W, Cout = G.CASES[case]
-    M = N * H * W
-    tiles = (cpad(Cin) // 64) * (cpad(Cout) // 64)
-    S = max(1, min(cdiv(512, 5 * tiles), cdiv(M, 4 * 64)))
-    per = up(cdiv(M, S), 64)
-    return cdiv(M, per), per, M
+    return dense_wgrad_splits(*_dense(case))
 
 
 def workspace_bytes(case, mode):
-    """conv_train_layout on conv5x5_plan's two launches (api.hip), from the restated rules"""
-    N, Cin, H, W, Cout = G.CASES[case]
-    es = ES[mode]
-    f, d = problem(case, False), problem(case, True)
-    o = ZERO_PAGE + up(N * H * W * cpad(Cin) * es, 256) + up(N * H * W * cpad(Cout) * es, 256)
-    S = wgrad_splits(case)[0]
-    slab_end = o + up(S * 25 * cpad(Cout) * cpad(Cin) * 4, 256) + up(S * cpad(Cout) * 4, 256)
-    o += up(max(f["Npad"] * 25 * cpad(Cin), d["Npad"] * 25 * cpad(Cout)) * es, 256)
-    o += up(max(f["Npad"], d["Npad"]) * 4, 256)
-    o += up(max(N * H * W * Cout, N * H * W * Cin) * 4, 256)
-    partial = 0
-    for p in (f, d):
-        s = splitk(p, es)
-        partial = max(partial, s * p["B"] * p["Ho"] * p["Wo"] * p["Npad"] * 4 if s > 1 else 0)
-    return max(o + up(partial, 256), slab_end)
+    return dense_workspace_bytes(*_dense(case), mode)
 
 
 @pytest.mark.parametrize("mode", list(ES))
@@ -230,13 +217,15 @@ def test_restated_plan_reproduces_the_workspace_query(case, mode):
 
 def test_the_split_rule_of_the_other_kernel_sizes_did_not_move():
     """k = 1 | 3 keep cdiv(512, tiles): their restated workspace (test_conv_grad_variants.py, test_conv_strided_abi.py) still matches,
-    and a layer whose split count the two rules tell apart sits where the old rule puts it."""
+    and a layer whose split count the two rules tell apart sits where the old rule puts it.  The arithmetic is written out here, not
+    taken from dense_wgrad_splits: that restatement must tell the two rules apart the same way."""
     lib = _lib.lib()
     # 256 -> 256 on 40 x 40, batch 8: tiles = 16, M = 12800: the old rule asks for 32 splits and gets 29 of 448 pixels; counting five
     # workgroups per split would ask for 7
     dims = (8, 256, 40, 40, 256, 3, 3, 1, 1, 1, 1, 1, 1)
     M, S = 12800, 29
     assert min(cdiv(512, 16), cdiv(M, 256)) == 32 and cdiv(M, up(cdiv(M, 32), 64)) == S and cdiv(512, 5 * 16) == 7
+    assert dense_wgrad_splits(8, 256, 40, 40, 256, 3, 1, 1, 1) == (S, 448, M) and dense_wgrad_splits(8, 256, 40, 40, 256, 5, 1, 2, 1)[0] == 7
     slab = up(S * 9 * 256 * 256 * 4, 256) + up(S * 256 * 4, 256)
     head = ZERO_PAGE + 2 * up(M * 256 * 4, 256)
     assert lib.tdrn_conv2d_workspace_bytes(*dims, _lib.F32) == head + slab        # the slabs are the larger branch of the layout

@@ -45,13 +45,62 @@ def cpad(c):
     return up(c, 64)
 
 
-def problem(case, dgrad):
-    """the implicit GEMM of the forward or of the input gradient: B, H, W, Cin (padded), Ho, Wo, Cout, Npad, k, pad"""
-    N, Cin, H, W, Cout, k, pad, dil = G.CASES[case]
-    Ho, Wo = G._out_hw(case)
+# ---- conv_dense_plan (api.hip), restated once for the three dense families: each test file passes its cases' k, stride, pad, dil ----
+def dense_geometry(H, W, k, stride, pad, dil):
+    """(Ho, Wo, Hd, Wd): the output, and the image the input gradient convolves -- grad_output itself at stride 1 (Hd = Ho), its
+    zero-inserted image at stride 2"""
+    Hd, Wd = H + 2 * pad - dil * (k - 1), W + 2 * pad - dil * (k - 1)
+    return (Hd - 1) // stride + 1, (Wd - 1) // stride + 1, Hd, Wd
+
+
+def dense_problem(N, Cin, H, W, Cout, k, stride, pad, dil, dgrad):
+    """the implicit GEMM of the forward or of the input gradient: B, H, W, Cin (padded), Ho, Wo, Cout, Npad, k, pad.  The input
+    gradient is the stride-1 conv with pad' = dil (k - 1) - pad over the Hd x Wd image"""
+    Ho, Wo, Hd, Wd = dense_geometry(H, W, k, stride, pad, dil)
     if not dgrad:
         return dict(B=N, H=H, W=W, Cin=cpad(Cin), Ho=Ho, Wo=Wo, Cout=Cout, Npad=n_pad(Cout), k=k, pad=pad)
-    return dict(B=N, H=Ho, W=Wo, Cin=cpad(Cout), Ho=H, Wo=W, Cout=Cin, Npad=n_pad(Cin), k=k, pad=dil * (k - 1) - pad)
+    return dict(B=N, H=Hd, W=Wd, Cin=cpad(Cout), Ho=H, Wo=W, Cout=Cin, Npad=n_pad(Cin), k=k, pad=dil * (k - 1) - pad)
+
+
+def dense_wgrad_splits(N, Cin, H, W, Cout, k, stride, pad, dil):
+    """conv_wgrad_splits on the output pixels -> (splits, per_split, M).  k = 5 runs five workgroups (the kernel rows) per split and
+    tile and counts them; k = 1 | 3 count one"""
+    Ho, Wo, Hd, Wd = dense_geometry(H, W, k, stride, pad, dil)
+    M = N * Ho * Wo
+    tiles = (cpad(Cin) // 64) * (cpad(Cout) // 64)
+    S = max(1, min(cdiv(512, 5 * tiles if k == 5 else tiles), cdiv(M, 4 * 64)))
+    per = up(cdiv(M, S), 64)
+    return cdiv(M, per), per, M
+
+
+def dense_workspace_bytes(N, Cin, H, W, Cout, k, stride, pad, dil, mode):
+    """conv_train_layout on conv_dense_plan's two launches (api.hip), from the restated rules"""
+    Ho, Wo, Hd, Wd = dense_geometry(H, W, k, stride, pad, dil)
+    es = ES[mode]
+    f, d = (dense_problem(N, Cin, H, W, Cout, k, stride, pad, dil, dgrad) for dgrad in (False, True))
+    o = ZERO_PAGE + up(N * H * W * cpad(Cin) * es, 256) + up(N * Hd * Wd * cpad(Cout) * es, 256)
+    S = dense_wgrad_splits(N, Cin, H, W, Cout, k, stride, pad, dil)[0]
+    slab_end = o + up(S * k * k * cpad(Cout) * cpad(Cin) * 4, 256) + up(S * cpad(Cout) * 4, 256)
+    o += up(max(f["Npad"] * k * k * cpad(Cin), d["Npad"] * k * k * cpad(Cout)) * es, 256)
+    o += up(max(f["Npad"], d["Npad"]) * 4, 256)
+    o += up(max(N * Ho * Wo * Cout, N * H * W * Cin) * 4, 256)
+    partial = 0
+    for p in (f, d):
+        s = splitk(p, es)
+        partial = max(partial, s * p["B"] * p["Ho"] * p["Wo"] * p["Npad"] * 4 if s > 1 else 0)
+    return max(o + up(partial, 256), slab_end)
+
+
+def _dense(case):
+    """a stride-1 case as dense_*'s arguments: N, Cin, H, W, Cout, k, stride, pad, dil"""
+    N, Cin, H, W, Cout, k, pad, dil = G.CASES[case]
+    return N, Cin, H, W, Cout, k, 1, pad, dil
+
+
+def problem(case, dgrad):
+    p = dense_problem(*_dense(case), dgrad)
+    assert ((p["H"], p["W"]) if dgrad else (p["Ho"], p["Wo"])) == G._out_hw(case)     # the GPU test's own output size
+    return p
 
 
 def splitk(p, es):
@@ -81,32 +130,8 @@ def variant(case, mode, dgrad):
     return tile(p), splitk(p, ES[mode]), batch_minor(p), p["k"] * p["k"] * (p["Cin"] // (128 // ES[mode]))
 
 
-def wgrad_slab_bytes(case):
-    N, Cin, H, W, Cout, k, pad, dil = G.CASES[case]
-    Ho, Wo = G._out_hw(case)
-    M = N * Ho * Wo
-    tiles = (cpad(Cin) // 64) * (cpad(Cout) // 64)
-    S = max(1, min(cdiv(512, tiles), cdiv(M, 4 * 64)))
-    S = cdiv(M, up(cdiv(M, S), 64))
-    return up(S * k * k * cpad(Cout) * cpad(Cin) * 4, 256) + up(S * cpad(Cout) * 4, 256)
-
-
 def workspace_bytes(case, mode):
-    """conv_train_layout on conv2d_plan's two launches (api.hip), from the restated rules"""
-    N, Cin, H, W, Cout, k, pad, dil = G.CASES[case]
-    Ho, Wo = G._out_hw(case)
-    es = ES[mode]
-    f, d = problem(case, False), problem(case, True)
-    o = ZERO_PAGE + up(N * H * W * cpad(Cin) * es, 256) + up(N * Ho * Wo * cpad(Cout) * es, 256)
-    slab_end = o + wgrad_slab_bytes(case)
-    o += up(max(f["Npad"] * k * k * cpad(Cin), d["Npad"] * k * k * cpad(Cout)) * es, 256)
-    o += up(max(f["Npad"], d["Npad"]) * 4, 256)
-    o += up(max(N * Ho * Wo * Cout, N * H * W * Cin) * 4, 256)
-    partial = 0
-    for p in (f, d):
-        s = splitk(p, es)
-        partial = max(partial, s * p["B"] * p["Ho"] * p["Wo"] * p["Npad"] * 4 if s > 1 else 0)
-    return max(o + up(partial, 256), slab_end)
+    return dense_workspace_bytes(*_dense(case), mode)
 
 
 # case: ((forward tile, dgrad tile), ...) -- what each case is in the suite for

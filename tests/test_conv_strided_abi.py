@@ -1,15 +1,16 @@
 """C ABI of the dense 3x3 stride-2 conv with gradients (tdrn_hip.h section i-g), no GPU needed: the workspace query and the entries
-decide every error before any launch, and the plan behind the query is restated here in plain Python.
+decide every error before any launch, and the plan behind the query is restated in plain Python (test_conv_grad_variants.py's
+dense_*, the one restatement of the three dense families, called here at k = 3, stride 2, dilation 1).
 
 The forward is launch_conv at stride 2, the input gradient a stride-1 3x3 conv with pad' = 2 - pad over the zero-inserted image of
 grad_output (CoPad input channels, H + 2 pad - 2 rows and W + 2 pad - 2 columns), the weight gradient conv_wgrad_kernel<DT, 9> with
-the output pixel stepped by 2 (K = N Ho Wo).  conv_igemm.hip's rules are test_conv_grad_variants.py's.
+the output pixel stepped by 2 (K = N Ho Wo).  conv_igemm.hip's rules are test_conv_grad_variants.py's too.
 """
 import pytest
 import torch
 
 import test_gpu_conv_strided as G
-from test_conv_grad_variants import ES, ZERO_PAGE, cdiv, cpad, n_pad, splitk, tile, up
+from test_conv_grad_variants import ES, cpad, dense_geometry, dense_problem, dense_wgrad_splits, dense_workspace_bytes, splitk, tile
 from tdrn_amd import _lib
 from tdrn_amd.model import networks
 
@@ -180,46 +181,31 @@ def test_uncovered_strides_raise_and_cpu_tensors_are_rejected():
 
 
 # ---- the plan, restated ---------------------------------------------------------------------------------------------------------
+def _dense(case):
+    """a case as the arguments of test_conv_grad_variants.py's dense_*: N, Cin, H, W, Cout, k = 3, stride 2, pad, dil = 1"""
+    N, Cin, H, W, Cout, pad = G.CASES[case]
+    return N, Cin, H, W, Cout, 3, 2, pad, 1
+
+
 def geometry(case):
     N, Cin, H, W, Cout, pad = G.CASES[case]
-    Ho, Wo = G._out_hw(case)
-    return N, Cin, H, W, Cout, pad, Ho, Wo, H + 2 * pad - 2, W + 2 * pad - 2
+    Ho, Wo, Hd, Wd = dense_geometry(H, W, 3, 2, pad, 1)
+    assert (Ho, Wo) == G._out_hw(case) and (Hd, Wd) == (H + 2 * pad - 2, W + 2 * pad - 2)
+    return N, Cin, H, W, Cout, pad, Ho, Wo, Hd, Wd
 
 
 def problem(case, dgrad):
-    """the implicit GEMM of the forward (stride 2) or of the input gradient (stride 1 over the zero-inserted image)"""
-    N, Cin, H, W, Cout, pad, Ho, Wo, Hd, Wd = geometry(case)
-    if not dgrad:
-        return dict(B=N, H=H, W=W, Cin=cpad(Cin), Ho=Ho, Wo=Wo, Cout=Cout, Npad=n_pad(Cout), k=3, pad=pad)
-    return dict(B=N, H=Hd, W=Wd, Cin=cpad(Cout), Ho=H, Wo=W, Cout=Cin, Npad=n_pad(Cin), k=3, pad=2 - pad)
+    """the implicit GEMM of the forward (stride 2) or of the input gradient (stride 1, pad' = 2 - pad, over the zero-inserted image)"""
+    return dense_problem(*_dense(case), dgrad)
 
 
 def wgrad_splits(case):
     """conv_wgrad_splits on the strided output -> (splits, per_split, M)"""
-    N, Cin, H, W, Cout, pad, Ho, Wo, Hd, Wd = geometry(case)
-    M = N * Ho * Wo
-    tiles = (cpad(Cin) // 64) * (cpad(Cout) // 64)
-    S = max(1, min(cdiv(512, tiles), cdiv(M, 4 * 64)))
-    per = up(cdiv(M, S), 64)
-    return cdiv(M, per), per, M
+    return dense_wgrad_splits(*_dense(case))
 
 
 def workspace_bytes(case, mode):
-    """conv_train_layout on convs2_plan's two launches (api.hip), from the restated rules"""
-    N, Cin, H, W, Cout, pad, Ho, Wo, Hd, Wd = geometry(case)
-    es = ES[mode]
-    f, d = problem(case, False), problem(case, True)
-    o = ZERO_PAGE + up(N * H * W * cpad(Cin) * es, 256) + up(N * Hd * Wd * cpad(Cout) * es, 256)
-    S = wgrad_splits(case)[0]
-    slab_end = o + up(S * 9 * cpad(Cout) * cpad(Cin) * 4, 256) + up(S * cpad(Cout) * 4, 256)
-    o += up(max(f["Npad"] * 9 * cpad(Cin), d["Npad"] * 9 * cpad(Cout)) * es, 256)
-    o += up(max(f["Npad"], d["Npad"]) * 4, 256)
-    o += up(max(N * Ho * Wo * Cout, N * H * W * Cin) * 4, 256)
-    partial = 0
-    for p in (f, d):
-        s = splitk(p, es)
-        partial = max(partial, s * p["B"] * p["Ho"] * p["Wo"] * p["Npad"] * 4 if s > 1 else 0)
-    return max(o + up(partial, 256), slab_end)
+    return dense_workspace_bytes(*_dense(case), mode)
 
 
 @pytest.mark.parametrize("mode", list(ES))
