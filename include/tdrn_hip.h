@@ -381,6 +381,48 @@ TDRN_API int tdrn_conv5x5_backward_parameters(const float *input, const float *g
                                               tdrn_dtype compute, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-j) SGD, one fused step over a list of fp32 tensors -- what optimizer.step() of optim.SGD(net.parameters(), lr, momentum,
+ *     weight_decay) gives the reference's training loops (train.py:259-270, train_trn.py:218-221), with the learning rate read on
+ *     the device (adjust_learning_rate, train.py:321-328, changes it every iteration during warm-up).
+ *   tensors_host (n_tensors) HOST records {param, grad, momentum_buf: DEVICE fp32, contiguous, numel elements each, on any 4-byte
+ *   boundary; group}; the records are copied into kernel arguments before the call returns.  hyper_dev (n_groups, 4) DEVICE fp32
+ *   rows {lr, momentum, weight_decay, nesterov as 0 / 1}, read by the kernel when it runs: a captured step replayed after the row
+ *   was rewritten uses the new values.  Per element, with (lr, mom, wd, nesterov) the row of the tensor's group, every operation
+ *   rounded to fp32 on its own (nothing is contracted into an fma):
+ *       d = (wd != 0) ? g + wd*p : g
+ *       if (mom != 0) { b = mom*b + d;  u = nesterov ? d + mom*b : b; } else u = d
+ *       p = p - lr*u
+ *       if (flags & TDRN_SGD_ZERO_GRADS) g = +0
+ *   momentum_buf starts as zeros (the caller's job), so the first step is no special case and a captured step is the same in every
+ *   replay.  torch.optim.SGD starts with buf = clone(d) instead; b = mom*0 + d equals that except for the sign of a zero: where
+ *   d = -0 the buffer holds +0.  momentum_buf is neither read nor written when mom == 0, but must be a valid pointer all the same
+ *   (the host cannot read hyper_dev).  Dampening and maximize are not covered.
+ *   A record with numel = 0 or a null grad is skipped (torch skips grad is None the same way); nothing else of it is looked at but
+ *   numel and group.  The other records go out in launches of up to TDRN_SGD_TENSORS_PER_LAUNCH tensors each, in chunks of
+ *   TDRN_SGD_CHUNK elements, with 16-byte vector accesses where param, grad and momentum_buf are all 16-byte aligned and scalar
+ *   ones elsewhere (the numel % 4 tail is always scalar).
+ *   All outputs are bitwise reproducible run to run and for caller buffers on any 4-byte boundary: no atomics, and each element's
+ *   result depends on that element alone.
+ *   Errors, all decided before any launch: a null tensors_host or hyper_dev, n_tensors < 0, n_groups < 1, unknown flag bits, and per
+ *   record a negative numel, a group outside [0, n_groups), and (unless skipped) a null param or momentum_buf -> TDRN_E_ARG; a
+ *   numel of 2^31 or more -> TDRN_E_UNSUPPORTED.  No workspace, no allocation and no host synchronisation: everything is enqueued
+ *   on `stream`.
+ * ====================================================================================== */
+#define TDRN_SGD_ZERO_GRADS 1
+#define TDRN_SGD_CHUNK 4096              /* elements a workgroup handles at a time */
+#define TDRN_SGD_TENSORS_PER_LAUNCH 96   /* descriptors one launch carries in its arguments */
+typedef struct {
+    float *param;
+    float *grad;             /* NULL: the tensor is skipped */
+    float *momentum_buf;
+    int64_t numel;
+    int32_t group;           /* row of hyper_dev */
+    int32_t reserved;
+} tdrn_sgd_tensor;
+TDRN_API int tdrn_sgd_step(const tdrn_sgd_tensor *tensors_host, int n_tensors, const float *hyper_dev, int n_groups, int flags,
+                           void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -80,6 +80,13 @@ class AugmentPairParams(C.Structure):
                 ("trans_y", C.c_int32), ("attempts", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SgdTensor(C.Structure):
+    """tdrn_sgd_tensor (tdrn_hip.h section i-j): one tensor of an SGD step."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum_buf", C.c_void_p), ("numel", C.c_int64),
+                ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+SGD_ZERO_GRADS, SGD_CHUNK, SGD_TENSORS_PER_LAUNCH = 1, 4096, 96          # tdrn_hip.h TDRN_SGD_*
 AUGMENT_MAX_TRUTHS, AUGMENT_MAX_SIZE = 512, 2048
 AUGMENT_CROP_FALLBACK, AUGMENT_TAPE_EXHAUSTED, AUGMENT_TRANS_FALLBACK = 1, 2, 4
 
@@ -137,6 +144,7 @@ _SIGS = {
     "tdrn_multibox_loss_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "tdrn_multibox_loss_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "tdrn_multibox_loss_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    "tdrn_sgd_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tdrn_augment_sample": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_uint64] + [C.c_void_p] * 7),
     "tdrn_augment_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdrn_augment_pair_sample": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_double, C.c_uint64] + [C.c_void_p] * 8),

@@ -896,6 +896,11 @@ int tdrn_multibox_loss_backward(const float *loc, const float *conf, const float
                                          (hipStream_t)stream);
 }
 
+int tdrn_sgd_step(const tdrn_sgd_tensor *tensors_host, int n_tensors, const float *hyper_dev, int n_groups, int flags, void *stream)
+{
+    return launch_sgd_step(tensors_host, n_tensors, hyper_dev, n_groups, flags, (hipStream_t)stream);
+}
+
 int tdrn_augment_sample(const int32_t *hw, const double *truths, const int32_t *truth_off, int T_total, int max_truths, int B,
                         uint64_t seed, const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
                         tdrn_augment_params *params, float *out_truths, int32_t *out_off, void *stream)

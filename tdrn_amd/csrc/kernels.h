@@ -382,6 +382,11 @@ int launch_multibox_loss_backward(const float *loc, const float *conf, const flo
                                   float *grad_loc, float *grad_conf, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
+// SGD, one fused multi-tensor step (sgd.hip; semantics: tdrn_hip.h section i-j)
+// ---------------------------------------------------------------------------------------------
+int launch_sgd_step(const tdrn_sgd_tensor *tensors, int n_tensors, const float *hyper_dev, int n_groups, int flags, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // SSDAugmentation on the device (augment.hip; semantics: tdrn_hip.h section ii-c)
 // ---------------------------------------------------------------------------------------------
 int launch_augment_sample(const int32_t *hw, const double *truths, const int32_t *truth_off, int T_total, int max_truths, int B,
