@@ -423,6 +423,88 @@ TDRN_API int tdrn_sgd_step(const tdrn_sgd_tensor *tensors_host, int n_tensors, c
                            void *stream);
 
 /* ========================================================================================
+ * (i-k) Resident training tensors: conv2d, BatchNorm2d (+ ReLU) and MaxPool2d whose activations and activation gradients stay in
+ *     16-bit NHWC between layers, so that a layer converts no layout and the convs may run on the inference engine's 3x3 kernels.
+ *   A RESIDENT TENSOR of logical shape (N, C, H, W) is `dtype` = TDRN_BF16 or TDRN_F16 memory [N][H][W][C] without gaps (torch:
+ *   contiguous in channels_last), C % 64 == 0, on a 16-byte boundary, fewer than 2^31 elements.  Activations and their gradients
+ *   are resident tensors of the same type; parameters, their gradients, the BatchNorm buffers and all statistics stay fp32 as in
+ *   (i-c) .. (i-e).  All accumulation is fp32; a conv output and a BatchNorm output are each rounded ONCE to the type, to nearest
+ *   even.  Argument lists mirror the fp32 NCHW entries they stand beside.  Nothing allocates, nothing synchronises, everything is
+ *   enqueued on `stream`; no float atomics, every output is bitwise reproducible.
+ *   Errors, all decided before any launch, in this order per entry: a null pointer, an activation pointer off a 16-byte boundary, an
+ *   fp32 pointer off a 4-byte one, a dtype other than TDRN_BF16 / TDRN_F16 (TDRN_F32 included), unknown flag bits -> TDRN_E_ARG; the
+ *   shape checks of the fp32 entry -> TDRN_E_SHAPE; geometry outside the fp32 entry's family, a channel count C (Cin, Cout) with
+ *   C % 64 != 0, 2^31 or more elements -> TDRN_E_UNSUPPORTED; a null or short workspace -> TDRN_E_WORKSPACE.
+ *
+ *   Layout boundary.  tdrn_nhwc16_from_nchw: fp32 NCHW (N, C, H, W) -> resident, each value rounded once; tdrn_nchw_from_nhwc16 the
+ *   way back (exact).  Each is the other's backward.
+ *
+ *   tdrn_conv2d_nhwc_*: the geometry of (i-c) (square k = 1 | 3, stride 1, one pad / dilation, pad <= dilation (k - 1)) with
+ *   Cin % 64 == 0 and Cout % 64 == 0.  weight (OIHW) and bias are fp32 and rounded once when they are packed; bias is not rounded.
+ *   forward reads `input` and writes `output` in place -- no conversion kernel, no copy of the result; backward_input is the same
+ *   launch over grad_output with the rotated, transposed kernel and pad' = dilation (k - 1) - pad, and writes grad_input directly;
+ *   backward_parameters is the (i-c) weight-gradient GEMM straight on the two caller tensors: grad_weight / grad_bias (fp32) +=
+ *   scale * their sums.  Workspace: zero page | packed weight | padded bias | split-K partials or the weight gradient's slabs.  No
+ *   launch of these entries polls a flag written by another workgroup.  `flags`: TDRN_CONV_NHWC_IGEMM_ONLY keeps forward and
+ *   backward_input on the generic implicit GEMM (conv_igemm.hip) instead of the 3x3 direct-conv kernels and the wide 1x1 GEMM, for
+ *   comparison.  The split-K choice stays that of the default route (so the workspace size does not change; the query takes the
+ *   flag all the same), but the two routes do NOT sum in the same fp32 order: the direct-conv kernels start their accumulators at the
+ *   bias and step through (64-channel chunk, tap), conv_igemm.hip steps through (tap, chunk) and adds the bias last.  The results
+ *   are bit-equal only for a launch that convolves ONE 64-channel chunk and has no (or a zero) bias -- forward: Cin = 64, bias NULL;
+ *   backward_input: Cout = 64 --; otherwise they agree up to the one rounding of the result (a few elements per ten thousand differ
+ *   in the last places).  tdrn_conv2d_nhwc_route names the kernel forward (dgrad = 0) or backward_input (dgrad = 1) reaches
+ *   ("igemm", "patch", "pp", "pw1x1"), NULL where the entries refuse; tdrn_conv2d_nhwc_splits gives the K slices of launch_conv's
+ *   split-K in the forward and in backward_input (1 = none) and the K splits of the weight gradient; both make no GPU call.
+ *
+ *   tdrn_batch_norm_nhwc_*: (i-d)'s semantics -- training / eval, momentum, eps, relu, fp32 save_mean / save_invstd, the running
+ *   buffers moved once, NULL grad_input or NULL (grad_weight, grad_bias) dropping the kernels that compute them -- with input,
+ *   output, grad_output and grad_input resident.  z = fma(x - mean, gamma invstd, beta) in fp32, the ReLU acts on z before the one
+ *   rounding, and the backward recomputes the mask z > 0 from `input`.  A workgroup owns 64 channels and one of `splits` ranges of
+ *   per_split pixel rows: S = clamp(floor(2048 / (C / 64)), 1, ceil(M / 256)), M = N H W, per_split = ceil(M / S) rounded up to 32,
+ *   splits = ceil(M / per_split) (tdrn_batch_norm_nhwc_splits: a pure function of the shape; returns a status).  Statistics are
+ *   (count, mean, M2) records merged by Chan's formula in a fixed order, the splits in float64.  Workspace: 12 C splits + 8 C bytes.
+ *
+ *   tdrn_max_pool_nhwc_*: (i-e)'s three geometries, selection rule and one-byte codes, the codes laid out like the output
+ *   ([N][Ho][Wo][C], on any byte; NULL in the forward: none are written).  backward reads grad_output and codes only and writes
+ *   every element of grad_input once; 3x3 sums in window row-major order in fp32 from +0.0 and rounds once.
+ * ====================================================================================== */
+#define TDRN_CONV_NHWC_IGEMM_ONLY 1
+TDRN_API int tdrn_nhwc16_from_nchw(const float *in, void *out, int N, int C, int H, int W, tdrn_dtype dtype, void *stream);
+TDRN_API int tdrn_nchw_from_nhwc16(const void *in, float *out, int N, int C, int H, int W, tdrn_dtype dtype, void *stream);
+TDRN_API size_t tdrn_conv2d_nhwc_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH,
+                                                 int padW, int dilationH, int dilationW, tdrn_dtype dtype, int flags);
+TDRN_API int tdrn_conv2d_nhwc_forward(const void *input, const float *weight, const float *bias, void *output, int N, int Cin, int H,
+                                      int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW,
+                                      tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream, int flags);
+TDRN_API int tdrn_conv2d_nhwc_backward_input(const void *grad_output, const float *weight, void *grad_input, int N, int Cin, int H,
+                                             int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                             int dilationW, tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream,
+                                             int flags);
+TDRN_API int tdrn_conv2d_nhwc_backward_parameters(const void *input, const void *grad_output, float *grad_weight, float *grad_bias,
+                                                  int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH,
+                                                  int padW, int dilationH, int dilationW, float scale, tdrn_dtype dtype,
+                                                  void *workspace, size_t workspace_bytes, void *stream, int flags);
+TDRN_API const char *tdrn_conv2d_nhwc_route(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                            int dilationH, int dilationW, tdrn_dtype dtype, int flags, int dgrad);
+TDRN_API int tdrn_conv2d_nhwc_splits(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                     int dilationH, int dilationW, tdrn_dtype dtype, int flags, int *splitk_forward, int *splitk_dgrad,
+                                     int *wgrad_splits);
+TDRN_API int tdrn_batch_norm_nhwc_splits(int N, int C, int H, int W, int *splits, int *per_split);
+TDRN_API size_t tdrn_batch_norm_nhwc_workspace_bytes(int N, int C, int H, int W);
+TDRN_API int tdrn_batch_norm_nhwc_forward(const void *input, const float *weight, const float *bias, float *running_mean,
+                                          float *running_var, void *output, float *save_mean, float *save_invstd, int N, int C, int H,
+                                          int W, int training, float momentum, float eps, int relu, tdrn_dtype dtype, void *workspace,
+                                          size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_batch_norm_nhwc_backward(const void *input, const void *grad_output, const float *weight, const float *bias,
+                                           const float *save_mean, const float *save_invstd, void *grad_input, float *grad_weight,
+                                           float *grad_bias, int N, int C, int H, int W, int training, int relu, float scale,
+                                           tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_max_pool_nhwc_forward(const void *input, void *output, unsigned char *code, int N, int C, int H, int W, int kernel,
+                                        int stride, int pad, int ceil_mode, tdrn_dtype dtype, void *stream);
+TDRN_API int tdrn_max_pool_nhwc_backward(const void *grad_output, const unsigned char *code, void *grad_input, int N, int C, int H,
+                                         int W, int kernel, int stride, int pad, int ceil_mode, tdrn_dtype dtype, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -87,6 +87,7 @@ class SgdTensor(C.Structure):
 
 
 SGD_ZERO_GRADS, SGD_CHUNK, SGD_TENSORS_PER_LAUNCH = 1, 4096, 96          # tdrn_hip.h TDRN_SGD_*
+CONV_NHWC_IGEMM_ONLY = 1                                                 # tdrn_hip.h TDRN_CONV_NHWC_*
 AUGMENT_MAX_TRUTHS, AUGMENT_MAX_SIZE = 512, 2048
 AUGMENT_CROP_FALLBACK, AUGMENT_TAPE_EXHAUSTED, AUGMENT_TRANS_FALLBACK = 1, 2, 4
 
@@ -129,6 +130,24 @@ _SIGS = {
     "tdrn_l2norm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "tdrn_l2norm_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "tdrn_l2norm_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # section (i-k): resident (16-bit NHWC) tensors
+    "tdrn_nhwc16_from_nchw": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "tdrn_nchw_from_nhwc16": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "tdrn_conv2d_nhwc_workspace_bytes": (C.c_size_t, [C.c_int] * 15),
+    "tdrn_conv2d_nhwc_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    "tdrn_conv2d_nhwc_backward_input": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    "tdrn_conv2d_nhwc_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p, C.c_size_t,
+                                                                                            C.c_void_p, C.c_int]),
+    "tdrn_conv2d_nhwc_route": (C.c_char_p, [C.c_int] * 16),
+    "tdrn_conv2d_nhwc_splits": (C.c_int, [C.c_int] * 15 + [C.POINTER(C.c_int)] * 3),
+    "tdrn_batch_norm_nhwc_splits": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2),
+    "tdrn_batch_norm_nhwc_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "tdrn_batch_norm_nhwc_forward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                                                                  C.c_size_t, C.c_void_p]),
+    "tdrn_batch_norm_nhwc_backward": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_size_t,
+                                                                                   C.c_void_p]),
+    "tdrn_max_pool_nhwc_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]),
+    "tdrn_max_pool_nhwc_backward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 9 + [C.c_void_p]),
     "tdrn_nms_workspace_bytes": (C.c_size_t, [C.c_int]),
     "tdrn_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_size_t, C.c_void_p]),

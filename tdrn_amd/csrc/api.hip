@@ -1,6 +1,7 @@
-// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g), (i-h), (i-i) and (ii) (section (iii) is in net.hip).
+// api.hip -- C ABI entry points of tdrn_hip.h sections (i), (i-b), (i-c), (i-d), (i-e), (i-f), (i-g), (i-h), (i-i), (i-j), (i-k) and (ii) (section (iii) is in net.hip).
 // Sections (i-c), (i-f), (i-g) and (i-i), the trainable dense conv families, share one plan, one workspace layout and one runner
 // (ConvTrainPlan); the depthwise conv (i-h) works on NCHW planes and has its own small plan (DwConvPlan).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -222,6 +223,68 @@ int conv_dense_plan(DenseFamily family, int N, int Cin, int H, int W, int Cout, 
     conv_train_dense_out(f);
     conv_train_dense_out(d);
     conv_train_layout(p, dtype);
+    return TDRN_OK;
+}
+
+// Resident tensors (section i-k): what the entries check of an activation pointer and of the type
+bool off_16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+bool dtype16_ok(int dtype) { return dtype == TDRN_BF16 || dtype == TDRN_F16; }
+
+// The resident conv (section i-k): conv_dense_plan's geometry for DENSE_STRIDE1 with whole 64-channel blocks on both sides, so that the
+// caller's tensors ARE launch_conv's input and output and conv_wgrad's two operands.  The result is 16-bit (out_f32 = 0), which opens
+// conv3x3_patch / conv3x3_pp / pw1x1 to conv_route; conv3x3_pp gets no chained-split scratch (sk_ws stays null: whole items only), so
+// no launch polls another workgroup's flag.  Workspace: zero page | packed weight | padded bias | the split-K partials of launch_conv
+// or the weight gradient's slabs (they share their place).
+int conv_nhwc_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int dtype,
+                   int flags, ConvTrainPlan &p)
+{
+    if (!dtype16_ok(dtype) || (flags & ~TDRN_CONV_NHWC_IGEMM_ONLY)) return TDRN_E_ARG;
+    TDRN_TRY(conv_dense_plan(DENSE_STRIDE1, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW, dtype, p));
+    if (Cin % kChanPad || Cout % kChanPad) return TDRN_E_UNSUPPORTED;
+    const size_t es = dtype_bytes(dtype);
+    size_t w_bytes = 0, partial = 0;
+    int npad = 0;
+    for (ConvArgs *a : {&p.fwd, &p.dgrad}) {
+        a->out_f32 = 0;
+        a->sk_ws = nullptr;
+        // the K slices are those of the default route (a direct-conv layer has none), whatever the flag says: a split would add one
+        // more difference in fp32 order to those the two routes already have (tdrn_hip.h section i-k: bit-equal only for one
+        // 64-channel chunk and no bias), and the workspace size stays the same
+        a->kdisable = KOFF_HEAD3X3;
+        a->splitk = 1;
+        a->splitk = conv_splitk_choice(*a);
+        if (flags & TDRN_CONV_NHWC_IGEMM_ONLY) a->kdisable |= KOFF_CONV_PATCH | KOFF_CONV_PP | KOFF_PW1X1;
+        w_bytes = std::max(w_bytes, (size_t)a->Npad * a->kh * a->kw * a->Cin * es);
+        partial = std::max(partial, conv_splitk_bytes(*a, a->splitk));
+        npad = std::max(npad, a->Npad);
+    }
+    size_t o = 0;
+    p.o_zero = o; o += kZeroPageBytes;
+    p.o_w = o;    o += align_up(w_bytes, 256);
+    p.o_bias = o; o += align_up((size_t)npad * 4, 256);
+    p.o_partial = p.o_slab = o;
+    p.o_x = p.o_go = p.o_out = 0;       // (the caller's tensors)
+    p.total = o + std::max(align_up(partial, 256), conv_wgrad_slab_bytes(p.wg));
+    return TDRN_OK;
+}
+
+// launch_conv from the caller's tensor into the caller's tensor
+int conv_nhwc_run(const ConvTrainPlan &p, char *ws, bool dgrad, const void *in, void *out, hipStream_t s)
+{
+    ConvArgs a = dgrad ? p.dgrad : p.fwd;
+    a.in = in; a.w = ws + p.o_w; a.zero_page = ws + p.o_zero; a.bias = (const float *)(ws + p.o_bias);
+    a.out = out;
+    if (a.splitk > 1) a.partial = ws + p.o_partial;
+    return launch_conv(a, s);
+}
+
+// the checks the resident BatchNorm and MaxPool entries share, after their pointers and type
+int nhwc_plan(int N, int C, int H, int W)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
+    if (C % kChanPad) return TDRN_E_UNSUPPORTED;
+    const long long HW = (long long)H * W, NC = (long long)N * C;
+    if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
     return TDRN_OK;
 }
 
@@ -513,6 +576,165 @@ int tdrn_conv2d_backward_parameters(const float *input, const float *grad_output
     const int rc = conv_dense_plan(DENSE_STRIDE1, N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, compute, p);
     return conv_dense_backward_parameters(rc, p, input, grad_output, grad_weight, grad_bias, scale, compute, workspace, workspace_bytes,
                                           (hipStream_t)stream);
+}
+
+// ---- section (i-k): resident tensors ----------------------------------------------------------------------------------------------------
+int tdrn_nhwc16_from_nchw(const float *in, void *out, int N, int C, int H, int W, tdrn_dtype dtype, void *stream)
+{
+    if (!in || !out || off_dword(in) || off_16(out) || !dtype16_ok(dtype)) return TDRN_E_ARG;
+    TDRN_TRY(nhwc_plan(N, C, H, W));
+    return launch_nchw_to_nhwc(in, out, N, C, H * W, C, dtype, (hipStream_t)stream);
+}
+
+int tdrn_nchw_from_nhwc16(const void *in, float *out, int N, int C, int H, int W, tdrn_dtype dtype, void *stream)
+{
+    if (!in || !out || off_16(in) || off_dword(out) || !dtype16_ok(dtype)) return TDRN_E_ARG;
+    TDRN_TRY(nhwc_plan(N, C, H, W));
+    return launch_nhwc_any_to_nchw_f32(in, dtype, C, out, N, C, H * W, (hipStream_t)stream);
+}
+
+size_t tdrn_conv2d_nhwc_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,
+                                        int dilationH, int dilationW, tdrn_dtype dtype, int flags)
+{
+    ConvTrainPlan p;
+    return conv_nhwc_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, dtype, flags, p) == TDRN_OK ? p.total : 0;
+}
+
+const char *tdrn_conv2d_nhwc_route(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                   int dilationW, tdrn_dtype dtype, int flags, int dgrad)
+{
+    ConvTrainPlan p;
+    if (conv_nhwc_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, dtype, flags, p) != TDRN_OK) return nullptr;
+    ConvArgs a = dgrad ? p.dgrad : p.fwd;
+    if (a.splitk > 1) a.partial = &p;       // (conv_route tests the pointer for null only)
+    return conv_kernel_name(conv_route(a, false));
+}
+
+int tdrn_conv2d_nhwc_splits(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                            int dilationW, tdrn_dtype dtype, int flags, int *splitk_forward, int *splitk_dgrad, int *wgrad_splits)
+{
+    if (!splitk_forward || !splitk_dgrad || !wgrad_splits) return TDRN_E_ARG;
+    ConvTrainPlan p;
+    TDRN_TRY(conv_nhwc_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, dtype, flags, p));
+    int per_split;
+    *splitk_forward = p.fwd.splitk;
+    *splitk_dgrad = p.dgrad.splitk;
+    conv_wgrad_splits(p.wg, *wgrad_splits, per_split);
+    return TDRN_OK;
+}
+
+int tdrn_conv2d_nhwc_forward(const void *input, const float *weight, const float *bias, void *output, int N, int Cin, int H, int W, int Cout,
+                             int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype dtype,
+                             void *workspace, size_t workspace_bytes, void *stream, int flags)
+{
+    if (!input || !weight || !output || off_16(input) || off_16(output) || off_dword(weight) || off_dword(bias)) return TDRN_E_ARG;
+    ConvTrainPlan p;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(conv_train_begin(conv_nhwc_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, dtype, flags, p), p,
+                              workspace, workspace_bytes, s));
+    const ConvArgs &f = p.fwd;
+    TDRN_TRY(launch_repack_oihw(weight, ws + p.o_w, f.Cout, f.Npad, Cin, f.kh * f.kw, 1, f.Cin, dtype, s));
+    TDRN_TRY(conv_train_bias(f, ws + p.o_bias, bias, s));
+    return conv_nhwc_run(p, ws, false, input, output, s);
+}
+
+int tdrn_conv2d_nhwc_backward_input(const void *grad_output, const float *weight, void *grad_input, int N, int Cin, int H, int W, int Cout,
+                                    int kH, int kW, int dH, int dW, int padH, int padW, int dilationH, int dilationW, tdrn_dtype dtype,
+                                    void *workspace, size_t workspace_bytes, void *stream, int flags)
+{
+    if (!grad_output || !weight || !grad_input || off_16(grad_output) || off_16(grad_input) || off_dword(weight)) return TDRN_E_ARG;
+    ConvTrainPlan p;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(conv_train_begin(conv_nhwc_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, dtype, flags, p), p,
+                              workspace, workspace_bytes, s));
+    const ConvArgs &d = p.dgrad;
+    TDRN_TRY(launch_repack_oihw_dgrad(weight, ws + p.o_w, Cout, Cin, d.Npad, d.kh * d.kw, dtype, s));
+    TDRN_TRY(conv_train_bias(d, ws + p.o_bias, nullptr, s));
+    return conv_nhwc_run(p, ws, true, grad_output, grad_input, s);
+}
+
+int tdrn_conv2d_nhwc_backward_parameters(const void *input, const void *grad_output, float *grad_weight, float *grad_bias, int N, int Cin,
+                                         int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilationH,
+                                         int dilationW, float scale, tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream,
+                                         int flags)
+{
+    if (!input || !grad_output || !grad_weight || off_16(input) || off_16(grad_output) || off_dword(grad_weight) || off_dword(grad_bias))
+        return TDRN_E_ARG;
+    ConvTrainPlan p;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    TDRN_TRY(conv_train_begin(conv_nhwc_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, dtype, flags, p), p,
+                              workspace, workspace_bytes, s));
+    return launch_conv_wgrad(p.wg, input, grad_output, ws + p.o_zero, ws + p.o_slab, grad_weight, grad_bias, scale, dtype, s);
+}
+
+int tdrn_batch_norm_nhwc_splits(int N, int C, int H, int W, int *splits, int *per_split)
+{
+    if (!splits || !per_split) return TDRN_E_ARG;
+    TDRN_TRY(nhwc_plan(N, C, H, W));
+    batch_norm_nhwc_splits(N, C, H * W, *splits, *per_split);
+    return TDRN_OK;
+}
+
+size_t tdrn_batch_norm_nhwc_workspace_bytes(int N, int C, int H, int W)
+{
+    return nhwc_plan(N, C, H, W) == TDRN_OK ? batch_norm_nhwc_workspace_bytes(N, C, H * W) : 0;
+}
+
+int tdrn_batch_norm_nhwc_forward(const void *input, const float *weight, const float *bias, float *running_mean, float *running_var,
+                                 void *output, float *save_mean, float *save_invstd, int N, int C, int H, int W, int training,
+                                 float momentum, float eps, int relu, tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !bias || !output || !save_mean || !save_invstd) return TDRN_E_ARG;
+    if (!running_mean != !running_var || (!training && !running_mean)) return TDRN_E_ARG;
+    if (off_16(input) || off_16(output) || off_dword(weight) || off_dword(bias) || off_dword(running_mean) || off_dword(running_var) ||
+        off_dword(save_mean) || off_dword(save_invstd) || off_dword(workspace) || !dtype16_ok(dtype))
+        return TDRN_E_ARG;
+    TDRN_TRY(nhwc_plan(N, C, H, W));
+    if (training && (long long)N * H * W == 1) return TDRN_E_SHAPE;     // one value per channel has no variance
+    if (!(eps > 0.f) || !(momentum >= 0.f && momentum <= 1.f)) return TDRN_E_ARG;
+    if (!workspace || workspace_bytes < batch_norm_nhwc_workspace_bytes(N, C, H * W)) return TDRN_E_WORKSPACE;
+    return launch_batch_norm_nhwc_forward(input, weight, bias, running_mean, running_var, output, save_mean, save_invstd, N, C, H * W,
+                                          training != 0, momentum, eps, relu != 0, dtype, workspace, (hipStream_t)stream);
+}
+
+int tdrn_batch_norm_nhwc_backward(const void *input, const void *grad_output, const float *weight, const float *bias, const float *save_mean,
+                                  const float *save_invstd, void *grad_input, float *grad_weight, float *grad_bias, int N, int C, int H,
+                                  int W, int training, int relu, float scale, tdrn_dtype dtype, void *workspace, size_t workspace_bytes,
+                                  void *stream)
+{
+    if (!input || !grad_output || !weight || !bias || !save_mean || !save_invstd) return TDRN_E_ARG;
+    if (!grad_weight != !grad_bias || (!grad_input && !grad_weight)) return TDRN_E_ARG;
+    if (off_16(input) || off_16(grad_output) || off_16(grad_input) || off_dword(weight) || off_dword(bias) || off_dword(save_mean) ||
+        off_dword(save_invstd) || off_dword(grad_weight) || off_dword(grad_bias) || off_dword(workspace) || !dtype16_ok(dtype))
+        return TDRN_E_ARG;
+    TDRN_TRY(nhwc_plan(N, C, H, W));
+    if (training && (long long)N * H * W == 1) return TDRN_E_SHAPE;
+    if (!workspace || workspace_bytes < batch_norm_nhwc_workspace_bytes(N, C, H * W)) return TDRN_E_WORKSPACE;
+    return launch_batch_norm_nhwc_backward(input, grad_output, weight, bias, save_mean, save_invstd, grad_input, grad_weight, grad_bias, N,
+                                           C, H * W, training != 0, relu != 0, scale, dtype, workspace, (hipStream_t)stream);
+}
+
+int tdrn_max_pool_nhwc_forward(const void *input, void *output, unsigned char *code, int N, int C, int H, int W, int kernel, int stride,
+                               int pad, int ceil_mode, tdrn_dtype dtype, void *stream)
+{
+    if (!input || !output || off_16(input) || off_16(output) || !dtype16_ok(dtype)) return TDRN_E_ARG;
+    int Ho, Wo;
+    TDRN_TRY(max_pool_plan(N, C, H, W, kernel, stride, pad, ceil_mode, Ho, Wo));
+    if (C % kChanPad) return TDRN_E_UNSUPPORTED;
+    return launch_max_pool_nhwc_forward(input, output, code, N, C, H, W, Ho, Wo, kernel, dtype, (hipStream_t)stream);
+}
+
+int tdrn_max_pool_nhwc_backward(const void *grad_output, const unsigned char *code, void *grad_input, int N, int C, int H, int W, int kernel,
+                                int stride, int pad, int ceil_mode, tdrn_dtype dtype, void *stream)
+{
+    if (!grad_output || !code || !grad_input || off_16(grad_output) || off_16(grad_input) || !dtype16_ok(dtype)) return TDRN_E_ARG;
+    int Ho, Wo;
+    TDRN_TRY(max_pool_plan(N, C, H, W, kernel, stride, pad, ceil_mode, Ho, Wo));
+    if (C % kChanPad) return TDRN_E_UNSUPPORTED;
+    return launch_max_pool_nhwc_backward(grad_output, code, grad_input, N, C, H, W, Ho, Wo, kernel, dtype, (hipStream_t)stream);
 }
 
 size_t tdrn_conv5x5_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW,

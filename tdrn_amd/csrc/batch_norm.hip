@@ -11,6 +11,7 @@
 // accesses; elsewhere the same instructions run on a 4-byte boundary, which global loads and stores of a dword or more allow.
 #include <type_traits>
 
+#include "bn_prims.h"
 #include "kernels.h"
 
 namespace tdrn {
@@ -77,35 +78,7 @@ __device__ __forceinline__ void bn_piece(const BnGeom &g, unsigned &c, unsigned 
     hi = g.M - lo < g.per ? g.M : lo + g.per;
 }
 
-// the pre-activation, in forward and backward alike: the centred form keeps the bits of x - mean that x * a + (beta - mean * a) loses
-__device__ __forceinline__ float bn_z(float x, float mean, float a, float beta) { return __builtin_fmaf(x - mean, a, beta); }
-
-// ---- statistics: (count, mean, M2) records merged with Chan's formula ---------------------------------------------------------------
-struct Welford { float n, mean, m2; };
-
-__device__ __forceinline__ Welford welford_merge(Welford a, Welford b)
-{
-    const float n = a.n + b.n;
-    const float w = n > 0.f ? b.n / n : 0.f;
-    const float d = b.mean - a.mean;
-    return Welford{n, a.mean + d * w, a.m2 + b.m2 + d * d * a.n * w};
-}
-
-// K values held in registers: mean and M2 about the mean in two passes, differences taken against the first value
-template <int K> __device__ __forceinline__ Welford welford_chunk(const float *v)
-{
-    float s = 0.f;
-#pragma unroll
-    for (int i = 1; i < K; ++i) s += v[i] - v[0];
-    const float mu = s * (1.f / K);
-    float m2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        const float d = (v[i] - v[0]) - mu;
-        m2 = __builtin_fmaf(d, d, m2);
-    }
-    return Welford{(float)K, v[0] + mu, m2};
-}
+// (the pre-activation bn_z and the (count, mean, M2) records with their merge: bn_prims.h, shared with batch_norm_nhwc.hip)
 
 __global__ __launch_bounds__(kT) void bn_stats_kernel(const float *__restrict__ x, float *__restrict__ rec, BnGeom g)
 {
@@ -325,6 +298,24 @@ size_t batch_norm_workspace_bytes(int N, int C, int HW)
 {
     const BnGeom g = bn_geom(N, C, HW);
     return bn_rec_bytes(g) + (size_t)g.C * 2 * 4;
+}
+
+// the two per-channel finalize kernels for a caller with its own sweeps (batch_norm_nhwc.hip): records [C][S][3] / [C][S][2]
+int launch_bn_stats_finalize(const float *rec, float *running_mean, float *running_var, float *save_mean, float *save_invstd, int C,
+                             long long M, int S, int training, float momentum, float eps, hipStream_t s)
+{
+    const BnGeom g{(unsigned)C, 0u, (unsigned)M, (unsigned)S, 0u};
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((g.C + kT - 1) / kT), dim3(kT), 0, s, rec, running_mean, running_var, save_mean,
+                       save_invstd, g, training, momentum, eps);
+    return hip_status(hipGetLastError());
+}
+
+int launch_bn_bwd_finalize(const float *rec, float *sums, float *grad_weight, float *grad_bias, int C, long long M, int S, float scale,
+                           hipStream_t s)
+{
+    const BnGeom g{(unsigned)C, 0u, (unsigned)M, (unsigned)S, 0u};
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((g.C + kT - 1) / kT), dim3(kT), 0, s, rec, sums, grad_weight, grad_bias, g, scale);
+    return hip_status(hipGetLastError());
 }
 
 int launch_batch_norm_forward(const float *input, const float *weight, const float *bias, float *running_mean, float *running_var,

@@ -73,6 +73,9 @@ struct ConvArgs {
 // the output is wanted: CONV_WS / CONV_PATCH pool in their epilogue, CONV_IGEMM leaves it to launch_maxpool2.  CONV_NONE: a fused-first launch
 // (fuse_x / fuse_x8) nobody takes: the caller runs the first conv on its own.  All but CONV_HEAD3X3 (another fp32 K order; geometry only)
 // give the same output bits, so the choice may depend on the batch.
+// (Measured on the resident training entries, DESIGN 22: that holds for a launch with one 64-channel chunk and no bias; with a bias, or
+// with several chunks, the direct-conv kernels and conv_igemm.hip sum in different fp32 orders and differ by a rounding of the result in a
+// few elements per ten thousand.  Do not rely on bit equality across routes beyond that without measuring it.)
 enum ConvKernel { CONV_IGEMM, CONV_PATCH, CONV_PP, CONV_WS, CONV_HEAD3X3, CONV_PW1X1, CONV_NONE };
 ConvKernel conv_route(const ConvArgs &a, bool pooled);
 const char *conv_kernel_name(ConvKernel k);
@@ -307,6 +310,32 @@ int launch_batch_norm_forward(const float *input, const float *weight, const flo
 int launch_batch_norm_backward(const float *input, const float *grad_output, const float *weight, const float *bias, const float *save_mean,
                                const float *save_invstd, float *grad_input, float *grad_weight, float *grad_bias, int N, int C, int HW,
                                int training, int relu, float scale, void *ws, hipStream_t s);
+// ... its two per-channel finalize kernels for a caller with its own sweeps: the records [C][S][3] (count, mean, M2) in split order ->
+// save_mean / save_invstd and the running buffers (training), or the running buffers read (eval); the records [C][S][2] -> sums[C][2] =
+// (sum dy' / M, sum dy' xhat / M), grad_weight / grad_bias (both or neither) += scale * their sums.  Both merge in float64.
+int launch_bn_stats_finalize(const float *rec, float *running_mean, float *running_var, float *save_mean, float *save_invstd, int C,
+                             long long M, int S, int training, float momentum, float eps, hipStream_t s);
+int launch_bn_bwd_finalize(const float *rec, float *sums, float *grad_weight, float *grad_bias, int C, long long M, int S, float scale,
+                           hipStream_t s);
+// BatchNorm2d with an optional fused ReLU on resident tensors: 16-bit NHWC activations [N HW][C], C % 64 == 0, 16-byte aligned; fp32
+// parameters and statistics (batch_norm_nhwc.hip; tdrn_hip.h section i-k).  The semantics are those of the fp32 entries above; a
+// workgroup owns 64 channels and one of `splits` ranges of per_split pixel rows, from (N, C, HW) alone; the workspace holds the same
+// records: 12 C splits + 8 C bytes
+void batch_norm_nhwc_splits(int N, int C, int HW, int &splits, int &per_split);
+size_t batch_norm_nhwc_workspace_bytes(int N, int C, int HW);
+int launch_batch_norm_nhwc_forward(const void *input, const float *weight, const float *bias, float *running_mean, float *running_var,
+                                   void *output, float *save_mean, float *save_invstd, int N, int C, int HW, int training, float momentum,
+                                   float eps, int relu, int dtype, void *ws, hipStream_t s);
+int launch_batch_norm_nhwc_backward(const void *input, const void *grad_output, const float *weight, const float *bias,
+                                    const float *save_mean, const float *save_invstd, void *grad_input, float *grad_weight,
+                                    float *grad_bias, int N, int C, int HW, int training, int relu, float scale, int dtype, void *ws,
+                                    hipStream_t s);
+// Trainable MaxPool2d on resident tensors (pool_nhwc.hip; tdrn_hip.h section i-k): the geometries, selection rule and codes of the fp32
+// NCHW kernels below, 16-bit NHWC tensors with C % 8 == 0 on 16-byte boundaries, codes [N][Ho][Wo][C] on any byte
+int launch_max_pool_nhwc_forward(const void *input, void *output, unsigned char *code, int N, int C, int H, int W, int Ho, int Wo, int kernel,
+                                 int dtype, hipStream_t s);
+int launch_max_pool_nhwc_backward(const void *grad_output, const unsigned char *code, void *grad_input, int N, int C, int H, int W, int Ho,
+                                  int Wo, int kernel, int dtype, hipStream_t s);
 // Trainable MaxPool2d and L2Norm, fp32 NCHW (pool_l2norm.hip; tdrn_hip.h section i-e).  kernel = 2: 2x2 / 2 / 0 with a floor or ceil
 // Ho x Wo; kernel = 3: 3x3 / 1 / 1 (Ho x Wo = H x W).  code (or null) gets one byte per output element, the selected slot dy * k + dx
 int launch_max_pool_forward(const float *input, float *output, unsigned char *code, int planes, int H, int W, int Ho, int Wo, int kernel,

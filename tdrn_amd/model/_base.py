@@ -185,41 +185,68 @@ class TrainWalk(object):
     # input is transposed and gathered, and its gradient scattered, once instead of twice); False: two calls.  Measured: DESIGN 20.
     _paired_heads = True
 
-    def _bn_relu(self, bn, x):
+    def _bn_relu(self, bn, x, resident=False):
         if bn.momentum is None:
             raise NotImplementedError("forward_train: BatchNorm2d(momentum=None) needs a host-side batch count; use networks.BatchNorm2d")
         if self.training and bn.track_running_stats:
             bn.num_batches_tracked.add_(1)            # on the device: no host read, no synchronisation
-        return networks.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training, bn.momentum, bn.eps,
-                                   relu=True)
+        op = networks.batch_norm_nhwc if resident else networks.batch_norm
+        return op(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training, bn.momentum, bn.eps, relu=True)
 
-    def _walk(self, layers, x, compute, taps=()):
+    @staticmethod
+    def _check_resident(resident, compute, vgg_trunk=True):
+        """forward_train's `resident` switch, checked before anything else happens (a refused call does not mark the engine's weights
+        stale): the VGG trunks only, and a 16-bit compute type, which is the resident tensors' dtype"""
+        if resident and not vgg_trunk:
+            raise NotImplementedError("forward_train: resident=True covers the VGG trunks; the MobileNet trunk's depthwise conv is fp32 NCHW")
+        if resident and compute not in ("bf16", "fp16"):
+            raise ValueError("forward_train: resident=True needs compute 'bf16' or 'fp16', got %r" % (compute,))
+
+    @staticmethod
+    def _resident_conv(m):
+        """a conv the resident path takes: the stride-1 family of conv2d_nhwc with whole 64-channel blocks on both sides"""
+        return (m.groups == 1 and tuple(m.stride) == (1, 1) and tuple(m.kernel_size) in ((1, 1), (3, 3))
+                and m.in_channels % networks.RESIDENT_CHANNELS == 0 and m.out_channels % networks.RESIDENT_CHANNELS == 0)
+
+    def _walk(self, layers, x, compute, taps=(), resident=False):
         """A list of nn.Conv2d [+ nn.BatchNorm2d] [+ nn.ReLU] and nn.MaxPool2d holders, in order, nested nn.Sequentials flattened ->
         (output, [the output behind conv number n (1-based, activation included) for n in taps]).  A dense conv goes to conv2d with
-        `compute`; a depthwise 3x3 conv with pad 1 (conv_dw's first layer) goes to depthwise_conv2d, which is fp32."""
-        layers, kept, n_conv, i = _flatten(layers), [], 0, 0
+        `compute`; a depthwise 3x3 conv with pad 1 (conv_dw's first layer) goes to depthwise_conv2d, which is fp32.
+        resident=True (compute "bf16" | "fp16"): from the first conv of the stride-1 family whose input and output both hold whole
+        64-channel blocks on, the activation is a resident tensor (networks.to_nhwc) and stays one through conv2d_nhwc,
+        batch_norm_nhwc (or torch.relu) and max_pool2d_nhwc; a conv outside that family takes it back to fp32 NCHW first, and so do
+        a tap and the result (networks.from_nhwc)."""
+        layers, kept, n_conv, i, nhwc = _flatten(layers), [], 0, 0, False
         while i < len(layers):
             m = layers[i]
             i += 1
             if isinstance(m, nn.MaxPool2d):
-                x = networks.max_pool2d(x, m.kernel_size, m.stride, m.padding, m.ceil_mode)
+                pool = networks.max_pool2d_nhwc if nhwc else networks.max_pool2d
+                x = pool(x, m.kernel_size, m.stride, m.padding, m.ceil_mode)
                 continue
             if not isinstance(m, nn.Conv2d) or not (m.groups == 1 or _is_depthwise3x3(m)):
                 raise NotImplementedError("forward_train: no differentiable op for %r" % (m,))
-            if m.groups == 1:
-                x = networks.conv2d(x, m.weight, m.bias, m.padding, m.dilation, compute, m.stride)
+            if resident and self._resident_conv(m):
+                if not nhwc:
+                    x, nhwc = networks.to_nhwc(x, compute), True
+                x = networks.conv2d_nhwc(x, m.weight, m.bias, m.padding, m.dilation)
             else:
-                x = networks.depthwise_conv2d(x, m.weight, m.bias, m.stride, m.padding)
+                if nhwc:
+                    x, nhwc = networks.from_nhwc(x), False
+                if m.groups == 1:
+                    x = networks.conv2d(x, m.weight, m.bias, m.padding, m.dilation, compute, m.stride)
+                else:
+                    x = networks.depthwise_conv2d(x, m.weight, m.bias, m.stride, m.padding)
             if i < len(layers) and isinstance(layers[i], nn.BatchNorm2d):
-                x = self._bn_relu(layers[i], x)        # the nn.ReLU behind it is fused
+                x = self._bn_relu(layers[i], x, nhwc)  # the nn.ReLU behind it is fused
                 i += 2 if i + 1 < len(layers) and isinstance(layers[i + 1], nn.ReLU) else 1
             elif i < len(layers) and isinstance(layers[i], nn.ReLU):
                 x = torch.relu(x)
                 i += 1
             n_conv += 1
             if n_conv in taps:
-                kept.append(x)
-        return x, kept
+                kept.append(networks.from_nhwc(x) if nhwc else x)
+        return (networks.from_nhwc(x) if nhwc else x), kept
 
     def _train_input(self, x):
         """the checks and the engine mark every forward_train starts with -> the input as fp32"""
@@ -229,17 +256,23 @@ class TrainWalk(object):
         object.__setattr__(self, "_dirty", True)
         return x.float()
 
-    def _vgg_sources(self, x, compute):
-        """the VGG trunk of the three VGG models -> ([conv4_3 and conv5_3 behind their ReLU and L2Norm, fc7, extras], extras)"""
-        x, (c43, c53) = self._walk(self.backbone, x, compute, taps=(10, 13))     # x: fc7
+    def _vgg_sources(self, x, compute, resident=False):
+        """the VGG trunk of the three VGG models -> ([conv4_3 and conv5_3 behind their ReLU and L2Norm, fc7, extras], extras).
+        resident: the trunk behind conv1_1, up to and including fc7, on resident tensors (_walk); the taps, fc7 and everything behind
+        them are fp32 NCHW either way."""
+        self._check_resident(resident, compute)
+        x, (c43, c53) = self._walk(self.backbone, x, compute, taps=(10, 13), resident=resident)     # x: fc7
         arm_sources = [networks.l2norm(c43, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps),
                        networks.l2norm(c53, self.L2Norm_5_3.weight, self.L2Norm_5_3.eps), x]
         x, _ = self._walk(self.extras, x, compute)
         arm_sources.append(x)
         return arm_sources, x
 
-    def _mobilenet_sources(self, x, compute):
-        """the MobileNet trunk of the two MobileNet models -> ([block 11 and block 13 behind their L2Norm, the two extras], extras)"""
+    def _mobilenet_sources(self, x, compute, resident=False):
+        """the MobileNet trunk of the two MobileNet models -> ([block 11 and block 13 behind their L2Norm, the two extras], extras).
+        Its depthwise op is fp32 NCHW: there is no resident path."""
+        if resident:
+            raise NotImplementedError("forward_train: resident=True covers the VGG trunks; the MobileNet trunk's depthwise conv is fp32 NCHW")
         x, _ = self._walk(self.backbone[:12], x, compute)
         arm_sources = [networks.l2norm(x, self.L2Norm_4_3.weight, self.L2Norm_4_3.eps)]
         x, _ = self._walk(self.backbone[12:], x, compute)
@@ -282,10 +315,11 @@ class TrainWalk(object):
         out = (torch.cat(locs, 1).view(B, -1, 4), torch.cat(confs, 1).view(B, -1, self.num_classes))
         return out + (loc_maps,) if ret_loc else out
 
-    def _ssd_forward_train(self, sources, x, ref_loc, compute, ret_loc):
+    def _ssd_forward_train(self, sources, x, ref_loc, compute, ret_loc, resident=False):
         """forward_train of the two SSD4Scale models; `sources`: _vgg_sources or _mobilenet_sources"""
+        self._check_resident(resident, compute, sources == self._vgg_sources)
         x = self._train_input(x)
-        arm_sources, _ = sources(x, compute)
+        arm_sources, _ = sources(x, compute, resident)
         return self._ssd_heads_train(arm_sources, ref_loc, compute, ret_loc)
 
     def _tcb_train(self, arm_sources, x, compute):

@@ -65,14 +65,19 @@ class RefineSSD(EngineModule, TrainWalk):
         conf = r["conf"] if self.phase == 'test' else r["conf"].view(x.size(0), -1, self.num_classes)
         return (r["arm_loc"], r["offsets"] if self.phase == 'test' else None, r["odm_loc"], conf)
 
-    def forward_train(self, x, compute="fp32"):
+    def forward_train(self, x, compute="fp32", resident=False):
         """-> (arm_loc (B, P, 4), None, odm_loc (B, P, 4), conf (B, P, num_classes) raw logits): the phase-'train' outputs of
         forward, computed from this module's fp32 parameters with an autograd graph.  BatchNorm runs in the module's mode
         (self.training: batch statistics, running buffers updated with each layer's momentum; else the running buffers).
         `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of every conv-type op; BatchNorm, pools and L2Norm are fp32.
+        resident=True (compute "bf16" | "fp16"; ValueError otherwise) keeps the VGG trunk's activations and their gradients behind
+        conv1_1, up to and including fc7, as 16-bit NHWC tensors between layers (networks.conv2d_nhwc, batch_norm_nhwc,
+        max_pool2d_nhwc): each conv and BatchNorm output is rounded once to the type; parameters, statistics and everything behind
+        the taps and fc7 are as with resident=False, which is the default and unchanged.
         The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
+        self._check_resident(resident, compute)
         x = self._train_input(x)
-        arm_sources, x = self._vgg_sources(x, compute)
+        arm_sources, x = self._vgg_sources(x, compute, resident)
         return self._head_train(arm_sources, x, compute)
 
 

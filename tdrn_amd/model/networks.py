@@ -5,6 +5,8 @@ nn.Conv2d and autograd give the reference's training loop; stride 1, and 3x3 at 
 batch_norm / BatchNorm2d), max pool (MaxPool2dFunction / max_pool2d / MaxPool2d) and L2Norm (L2NormFunction / l2norm / L2Norm),
 and the trainable 2x2 stride-2 transposed conv of the TCB up_layers (ConvTranspose2dFunction / conv_transpose2d / ConvTranspose2d),
 and the trainable depthwise 3x3 conv of conv_dw (DepthwiseConv2dFunction / depthwise_conv2d / DepthwiseConv2d).
+and the resident-tensor ops (to_nhwc / from_nhwc, conv2d_nhwc, batch_norm_nhwc, max_pool2d_nhwc: 16-bit NHWC activations and
+gradients between layers, C ABI section i-k).
 The modules only own parameters with the reference's names and
 shapes; arithmetic happens in libtdrn_hip.so."""
 import collections
@@ -893,3 +895,335 @@ class L2Norm(nn.Module):
 
     def forward(self, x):
         return l2norm(x, self.weight, self.eps)
+
+
+# ---- resident tensors (tdrn_hip.h section i-k): activations and their gradients as 16-bit NHWC between layers ----------------------------
+_RESIDENT_DTYPES = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+_RESIDENT_NAMES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "f16": torch.float16,
+                   "float16": torch.float16, "half": torch.float16}
+RESIDENT_CHANNELS = 64          # kChanPad: a resident tensor holds whole 64-channel blocks
+
+
+def _resident_dtype(dtype):
+    dtype = _RESIDENT_NAMES.get(dtype, dtype)
+    if dtype not in _RESIDENT_DTYPES:
+        raise ValueError("a resident tensor is torch.bfloat16 or torch.float16, got %r" % (dtype,))
+    return dtype
+
+
+def _resident(t, dtype=None):
+    """`t` as a resident tensor: of `dtype` (default: its own), contiguous in channels_last, its data on a 16-byte boundary (a
+    misaligned storage is cloned)"""
+    if dtype is not None and t.dtype != dtype:
+        t = t.to(dtype)
+    t = t.contiguous(memory_format=torch.channels_last)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.channels_last)
+
+
+def _resident_input(input, op):
+    """the checks every resident op starts with -> the library's type code"""
+    if input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _lib.require_cuda(input, "input")
+    if input.dtype not in _RESIDENT_DTYPES:
+        raise ValueError("%s: input must be torch.bfloat16 or torch.float16 (got %s); to_nhwc makes one" % (op, input.dtype))
+    if input.shape[1] % RESIDENT_CHANNELS:
+        raise RuntimeError("%s: %d channels are outside what libtdrn_hip covers (a multiple of %d)" % (op, input.shape[1], RESIDENT_CHANNELS))
+    return _RESIDENT_DTYPES[input.dtype]
+
+
+def _resident_empty(shape, dtype, device):
+    return torch.empty(tuple(shape), dtype=dtype, device=device, memory_format=torch.channels_last)
+
+
+def _resident_grad_output(grad_output, shape, dtype, op):
+    """what every resident backward does first: a CUDA grad_output of the output's shape, made resident whatever it arrives as"""
+    if not grad_output.is_cuda:
+        raise NotImplementedError("%s backward: grad_output must be a CUDA tensor" % op)
+    if tuple(grad_output.shape) != tuple(shape):
+        raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(grad_output.shape), tuple(shape)))
+    return _resident(grad_output, dtype)
+
+
+def _to_nhwc_forward(x, dtype):
+    out = _resident_empty(x.shape, dtype, x.device)
+    _lib.check(_lib.lib().tdrn_nhwc16_from_nchw(_lib.ptr(x), _lib.ptr(out), *x.shape, _RESIDENT_DTYPES[dtype],
+                                                _lib.current_stream(x.device)), "tdrn_nhwc16_from_nchw")
+    return out
+
+
+def _from_nhwc_forward(x):
+    out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().tdrn_nchw_from_nhwc16(_lib.ptr(x), _lib.ptr(out), *x.shape, _RESIDENT_DTYPES[x.dtype],
+                                                _lib.current_stream(x.device)), "tdrn_nchw_from_nhwc16")
+    return out
+
+
+class ToNhwcFunction(torch.autograd.Function):
+    """fp32 NCHW -> resident (tdrn_nhwc16_from_nchw); the backward is from_nhwc's forward."""
+
+    @staticmethod
+    def forward(ctx, input, dtype):
+        ctx.dtype = dtype
+        return _to_nhwc_forward(input.contiguous().float(), dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _from_nhwc_forward(_resident_grad_output(grad_output, grad_output.shape, ctx.dtype, "to_nhwc")), None
+
+
+class FromNhwcFunction(torch.autograd.Function):
+    """resident -> fp32 NCHW (tdrn_nchw_from_nhwc16); the backward is to_nhwc's forward in the input's type."""
+
+    @staticmethod
+    def forward(ctx, input):
+        ctx.dtype = input.dtype
+        return _from_nhwc_forward(_resident(input))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _to_nhwc_forward(_grad_output(grad_output, grad_output.shape, "from_nhwc"), ctx.dtype)
+
+
+def to_nhwc(x, dtype):
+    """An NCHW CUDA tensor (C a multiple of 64) -> the resident tensor of the same values, each rounded once to `dtype`
+    (torch.bfloat16 / torch.float16 or "bf16" / "fp16"): logical shape (N, C, H, W), contiguous in channels_last.  Bit for bit
+    x.to(dtype).contiguous(memory_format=torch.channels_last); differentiable (the gradient comes back as fp32 NCHW)."""
+    dtype = _resident_dtype(dtype)
+    if x.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(x.dim()))
+    _lib.require_cuda(x, "input")
+    if x.shape[1] % RESIDENT_CHANNELS:
+        raise RuntimeError("to_nhwc: %d channels are outside what libtdrn_hip covers (a multiple of %d)" % (x.shape[1], RESIDENT_CHANNELS))
+    if torch.is_grad_enabled() and x.requires_grad:
+        return ToNhwcFunction.apply(x, dtype)
+    return _to_nhwc_forward(x.detach().contiguous().float(), dtype)
+
+
+def from_nhwc(x):
+    """A resident tensor -> the same values as fp32 NCHW (exact); differentiable (the gradient is rounded once to x's type)."""
+    _resident_input(x, "from_nhwc")
+    if torch.is_grad_enabled() and x.requires_grad:
+        return FromNhwcFunction.apply(x)
+    return _from_nhwc_forward(_resident(x.detach()))
+
+
+_CONV2D_NHWC_COVERED = "square k in {1, 3} at stride 1 with 0 <= pad <= dilation * (k - 1), Cin and Cout multiples of 64"
+_CONV2D_NHWC_DIMS = "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW"
+
+
+def _conv2d_nhwc_workspace(lib, dims, dt, flags, device):
+    return _workspace(lib.tdrn_conv2d_nhwc_workspace_bytes, dims + (dt, flags), device,
+                      "conv2d_nhwc: geometry outside what libtdrn_hip covers (%s): %s = %r", _CONV2D_NHWC_COVERED, _CONV2D_NHWC_DIMS, dims)
+
+
+def _conv2d_nhwc_forward(x, w, b, padding, dilation, flags):
+    lib = _lib.lib()
+    dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
+    if b is not None and tuple(b.shape) != (out_shape[1],):
+        raise RuntimeError("conv2d_nhwc: bias has shape %r, expected (%d,)" % (tuple(b.shape), out_shape[1]))
+    dt = _RESIDENT_DTYPES[x.dtype]
+    ws, nb = _conv2d_nhwc_workspace(lib, dims, dt, flags, x.device)
+    out = _resident_empty(out_shape, x.dtype, x.device)
+    _lib.check(lib.tdrn_conv2d_nhwc_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
+                                            _lib.current_stream(x.device), flags), "tdrn_conv2d_nhwc_forward")
+    return out
+
+
+class Conv2dNhwcFunction(torch.autograd.Function):
+    """Dense stride-1 conv2d on resident tensors with gradients: tdrn_conv2d_nhwc_forward / _backward_input / _backward_parameters
+    (scale 1 into zeroed fp32 buffers).  The compute type is the input's dtype; weight and bias stay fp32.
+
+        y = Conv2dNhwcFunction.apply(input, weight, bias_or_None, padding, dilation[, flags])
+    """
+
+    @staticmethod
+    def forward(ctx, input, weight, bias=None, padding=0, dilation=1, flags=0):
+        _resident_input(input, "conv2d_nhwc")
+        _conv2d_require_cuda(input, weight, bias)
+        x, w = _resident(input), weight.contiguous().float()
+        b = None if bias is None else bias.contiguous().float()
+        out = _conv2d_nhwc_forward(x, w, b, padding, dilation, flags)
+        ctx.conf = (padding, dilation, flags, bias is not None)
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, w = ctx.saved_tensors
+        padding, dilation, flags, has_bias = ctx.conf
+        dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
+        go = _resident_grad_output(grad_output, out_shape, x.dtype, "conv2d_nhwc")
+        need_in, need_w = ctx.needs_input_grad[:2]
+        need_b = has_bias and ctx.needs_input_grad[2]
+        grad_input = grad_weight = grad_bias = None
+        if need_in or need_w or need_b:
+            lib, dt = _lib.lib(), _RESIDENT_DTYPES[x.dtype]
+            ws, nb = _conv2d_nhwc_workspace(lib, dims, dt, flags, x.device)
+            stream = _lib.current_stream(x.device)
+        if need_in:
+            grad_input = _resident_empty(x.shape, x.dtype, x.device)
+            _lib.check(lib.tdrn_conv2d_nhwc_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws), nb,
+                                                           stream, flags), "tdrn_conv2d_nhwc_backward_input")
+        if need_w or need_b:
+            gw = torch.zeros_like(w)
+            gb = torch.zeros(w.shape[0], dtype=torch.float32, device=x.device) if need_b else None
+            _lib.check(lib.tdrn_conv2d_nhwc_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
+                                                                _lib.ptr(ws), nb, stream, flags), "tdrn_conv2d_nhwc_backward_parameters")
+            grad_weight = gw if need_w else None
+            grad_bias = gb
+        return grad_input, grad_weight, grad_bias, None, None, None
+
+
+def conv2d_nhwc(input, weight, bias=None, padding=0, dilation=1, flags=0):
+    """Dense stride-1 conv2d on libtdrn_hip from a resident tensor to a resident tensor (to_nhwc), differentiable in input, weight and
+    bias; weight (OIHW) and bias are fp32.  The compute type is the input's dtype.  `flags`: _lib.CONV_NHWC_IGEMM_ONLY keeps the
+    launches on the generic implicit GEMM (for comparison: bit-equal only for one 64-channel chunk and no bias, otherwise equal up to
+    one rounding of the result; tdrn_hip.h section i-k).  Geometry the library rejects raises; nothing falls back to torch.  With
+    grad mode off, or when nothing requires grad, only the forward runs and the output has no grad_fn."""
+    _resident_input(input, "conv2d_nhwc")
+    _conv2d_require_cuda(input, weight, bias)
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return Conv2dNhwcFunction.apply(input, weight, bias, padding, dilation, flags)
+    b = None if bias is None else bias.detach().contiguous().float()
+    return _conv2d_nhwc_forward(_resident(input.detach()), weight.detach().contiguous().float(), b, padding, dilation, flags)
+
+
+def _batch_norm_nhwc_workspace(lib, dims, device):
+    return _workspace(lib.tdrn_batch_norm_nhwc_workspace_bytes, dims, device,
+                      "batch_norm_nhwc: shape outside what libtdrn_hip covers (positive sizes, C a multiple of 64, fewer than 2^31 "
+                      "elements): N, C, H, W = %r", dims)
+
+
+def _batch_norm_nhwc_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu):
+    lib = _lib.lib()
+    dims = tuple(x.shape)
+    ws, nb = _batch_norm_nhwc_workspace(lib, dims, x.device)
+    out = _resident_empty(dims, x.dtype, x.device)
+    save_mean = torch.empty(dims[1], dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty_like(save_mean)
+    _lib.check(lib.tdrn_batch_norm_nhwc_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                                _lib.ptr(out), _lib.ptr(save_mean), _lib.ptr(save_invstd), *dims, int(bool(training)),
+                                                float(momentum), float(eps), int(bool(relu)), _RESIDENT_DTYPES[x.dtype], _lib.ptr(ws), nb,
+                                                _lib.current_stream(x.device)), "tdrn_batch_norm_nhwc_forward")
+    return out, save_mean, save_invstd
+
+
+class BatchNormNhwcFunction(torch.autograd.Function):
+    """BatchNormFunction on resident tensors: tdrn_batch_norm_nhwc_forward / _backward.  Saves the 16-bit input and the fp32
+    statistics; the backward recomputes the ReLU mask from the input.
+
+        y = BatchNormNhwcFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+    """
+
+    @staticmethod
+    def forward(ctx, input, running_mean, running_var, weight, bias, training=True, momentum=0.1, eps=1e-5, relu=False):
+        _resident_input(input, "batch_norm_nhwc")
+        _batch_norm_check(input, running_mean, running_var, weight, bias, training)
+        x, w, b = _resident(input), weight.contiguous().float(), bias.contiguous().float()
+        out, save_mean, save_invstd = _batch_norm_nhwc_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)
+        ctx.conf = (bool(training), bool(relu))
+        ctx.save_for_backward(x, w, b, save_mean, save_invstd)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, w, b, save_mean, save_invstd = ctx.saved_tensors
+        go = _resident_grad_output(grad_output, x.shape, x.dtype, "batch_norm_nhwc")
+        training, relu = ctx.conf
+        need_in, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        grad_input = gw = gb = None
+        if need_in or need_w or need_b:
+            lib = _lib.lib()
+            dims = tuple(x.shape)
+            ws, nb = _batch_norm_nhwc_workspace(lib, dims, x.device)
+            if need_in:
+                grad_input = _resident_empty(dims, x.dtype, x.device)
+            if need_w or need_b:
+                gw, gb = torch.zeros_like(w), torch.zeros_like(b)
+            _lib.check(lib.tdrn_batch_norm_nhwc_backward(_lib.ptr(x), _lib.ptr(go), _lib.ptr(w), _lib.ptr(b), _lib.ptr(save_mean),
+                                                         _lib.ptr(save_invstd), _lib.ptr(grad_input), _lib.ptr(gw), _lib.ptr(gb), *dims,
+                                                         int(training), int(relu), 1.0, _RESIDENT_DTYPES[x.dtype], _lib.ptr(ws), nb,
+                                                         _lib.current_stream(x.device)), "tdrn_batch_norm_nhwc_backward")
+        return grad_input, None, None, gw if need_w else None, gb if need_b else None, None, None, None, None
+
+
+def batch_norm_nhwc(input, running_mean, running_var, weight, bias, training, momentum=0.1, eps=1e-5, relu=False):
+    """batch_norm above from a resident tensor to a resident tensor: the same semantics, fp32 parameters, buffers and statistics,
+    the output rounded once to the input's dtype.  With grad mode off, or when nothing requires grad, only the forward runs and the
+    output has no grad_fn."""
+    _resident_input(input, "batch_norm_nhwc")
+    _batch_norm_check(input, running_mean, running_var, weight, bias, training)
+    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or bias.requires_grad):
+        return BatchNormNhwcFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+    x, w, b = _resident(input.detach()), weight.detach().contiguous().float(), bias.detach().contiguous().float()
+    return _batch_norm_nhwc_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)[0]
+
+
+def _max_pool_nhwc_check(input, kernel_size, stride, padding, ceil_mode):
+    """-> (kernel, stride, pad, ceil, Ho, Wo, the library's type code) of a call the library covers"""
+    dt = _resident_input(input, "max_pool2d_nhwc")
+    k = _square(kernel_size, "kernel_size")
+    geo = (k, k if stride is None else _square(stride, "stride"), _square(padding, "padding"), int(bool(ceil_mode)))
+    lib = _lib.lib()
+    Ho, Wo = (lib.tdrn_max_pool_output_size(int(n), *geo) for n in input.shape[2:])
+    if geo[:3] not in ((2, 2, 0), (3, 1, 1)):
+        raise NotImplementedError("max_pool2d_nhwc: kernel_size %d, stride %d, padding %d is not covered; libtdrn_hip covers %s"
+                                  % (geo[0], geo[1], geo[2], _POOL_GEOMETRIES))
+    if Ho == 0 or Wo == 0 or input.numel() == 0:
+        raise RuntimeError("max_pool2d_nhwc: input %r gives an empty output" % (tuple(input.shape),))
+    return geo + (Ho, Wo, dt)
+
+
+def _max_pool_nhwc_forward(x, conf, with_code):
+    k, s, p, ceil, Ho, Wo, dt = conf
+    N, Ch, H, W = x.shape
+    out = _resident_empty((N, Ch, Ho, Wo), x.dtype, x.device)
+    code = torch.empty((N, Ho, Wo, Ch), dtype=torch.uint8, device=x.device) if with_code else None
+    _lib.check(_lib.lib().tdrn_max_pool_nhwc_forward(_lib.ptr(x), _lib.ptr(out), _lib.ptr(code), N, Ch, H, W, k, s, p, ceil, dt,
+                                                     _lib.current_stream(x.device)), "tdrn_max_pool_nhwc_forward")
+    return out, code
+
+
+class MaxPool2dNhwcFunction(torch.autograd.Function):
+    """MaxPool2dFunction on resident tensors: tdrn_max_pool_nhwc_forward / _backward.  Saves one uint8 code per output element,
+    (N, Ho, Wo, C).
+
+        y = MaxPool2dNhwcFunction.apply(input, kernel_size, stride, padding, ceil_mode)
+    """
+
+    @staticmethod
+    def forward(ctx, input, kernel_size, stride=None, padding=0, ceil_mode=False):
+        conf = _max_pool_nhwc_check(input, kernel_size, stride, padding, ceil_mode)
+        x = _resident(input)
+        out, code = _max_pool_nhwc_forward(x, conf, True)
+        ctx.conf, ctx.in_shape, ctx.dtype = conf, tuple(x.shape), x.dtype
+        ctx.save_for_backward(code)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        code, = ctx.saved_tensors
+        k, s, p, ceil, Ho, Wo, dt = ctx.conf
+        N, Ch, H, W = ctx.in_shape
+        go = _resident_grad_output(grad_output, (N, Ch, Ho, Wo), ctx.dtype, "max_pool2d_nhwc")
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            grad_input = _resident_empty(ctx.in_shape, ctx.dtype, go.device)
+            _lib.check(_lib.lib().tdrn_max_pool_nhwc_backward(_lib.ptr(go), _lib.ptr(code), _lib.ptr(grad_input), N, Ch, H, W, k, s, p, ceil,
+                                                              dt, _lib.current_stream(go.device)), "tdrn_max_pool_nhwc_backward")
+        return grad_input, None, None, None, None
+
+
+def max_pool2d_nhwc(input, kernel_size, stride=None, padding=0, ceil_mode=False):
+    """max_pool2d above from a resident tensor to a resident tensor: the same three geometries, the same selection.  With grad mode
+    off, or an input that does not require grad, only the forward runs, no code tensor is made and the output has no grad_fn."""
+    conf = _max_pool_nhwc_check(input, kernel_size, stride, padding, ceil_mode)
+    if torch.is_grad_enabled() and input.requires_grad:
+        return MaxPool2dNhwcFunction.apply(input, kernel_size, stride, padding, ceil_mode)
+    return _max_pool_nhwc_forward(_resident(input.detach()), conf, False)[0]

@@ -54,13 +54,16 @@ class RefineSSD(EngineModule, TrainWalk):
             return (r["arm_loc"], None, r["odm_loc"], conf)
         return (r["odm_loc"], conf)
 
-    def forward_train(self, x, compute="fp32"):
+    def forward_train(self, x, compute="fp32", resident=False):
         """-> (arm_loc (B, P, 4), None, odm_loc (B, P, 4), conf (B, P, num_classes) raw logits) with use_refine, else (odm_loc,
         conf): the phase-'train' outputs of forward, computed from this module's fp32 parameters with an autograd graph.  BatchNorm
         runs in the module's mode; `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of every conv-type op.  The engine's
-        packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
+        packed weights are marked stale, so net(x) after an optimizer step re-packs by itself.  resident=True (compute "bf16" | "fp16"; ValueError otherwise) keeps the VGG trunk's
+        activations and their gradients from conv1_2 to fc7 as 16-bit NHWC tensors between layers; the default,
+        resident=False, is unchanged."""
+        self._check_resident(resident, compute)
         x = self._train_input(x)
-        arm_sources, x = self._vgg_sources(x, compute)
+        arm_sources, x = self._vgg_sources(x, compute, resident)
         return self._refinedet_head_train(arm_sources, x, compute)
 
 

@@ -67,15 +67,17 @@ class SSD4Scale(EngineModule, TrainWalk):
             out.append(offs)
         return tuple(out)
 
-    def forward_train(self, x, ref_loc=(), compute="fp32", ret_loc=False):
+    def forward_train(self, x, ref_loc=(), compute="fp32", ret_loc=False, resident=False):
         """-> (arm_loc (B, P, 4), arm_conf (B, P, num_classes) raw logits): the phase-'train' outputs of forward whatever self.phase
         is, computed from this module's fp32 parameters through the library's differentiable ops (_base.TrainWalk), so that
         `loss.backward()` fills their .grad.  deform=True needs ref_loc, four CUDA tensors (B, 12, Hs, Ws): the static net's loc
         maps (its forward with ret_loc=True); one that requires grad gets a gradient.  ret_loc=True appends the four loc maps (NCHW,
         with their graph) when deform=False and [] when deform=True, as the reference does.  BatchNorm runs in the module's mode;
         `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the conv-type ops.  offset_list, ret_off and ref_event belong
-        to inference.  The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
-        return self._ssd_forward_train(self._vgg_sources, x, ref_loc, compute, ret_loc)
+        to inference.  The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself.  resident=True (compute "bf16" | "fp16"; ValueError otherwise) keeps the VGG trunk's
+        activations and their gradients from conv1_2 to fc7 as 16-bit NHWC tensors between layers; the default,
+        resident=False, is unchanged."""
+        return self._ssd_forward_train(self._vgg_sources, x, ref_loc, compute, ret_loc, resident)
 
 
 def build_net(phase, size=320, num_classes=21, c7_channel=1024, bn=False, deform=False):
