@@ -505,6 +505,50 @@ TDRN_API int tdrn_max_pool_nhwc_backward(const void *grad_output, const unsigned
                                          int W, int kernel, int stride, int pad, int ceil_mode, tdrn_dtype dtype, void *stream);
 
 /* ========================================================================================
+ * (i-l) Deformable convolution v1 with gradients in the transform domain ("transform, then sample") -- an opt-in second algorithm
+ *     beside (i) / (i-b), for one deformable group and a 16-bit compute type.  A deformable conv is linear in the sampled values:
+ *     with b(p,t,q) the bilinear coefficient of input pixel q for the sample of output pixel p at tap t (the sampling rule of (i):
+ *     rejection outside the map, the [H-1, H) clamp band, fp32 coordinates),
+ *         Y_t[n,co,q]      = sum_c W[co,c,t] X[n,c,q]                   1x1 GEMM on un-deformed pixels (MFMA)
+ *         out[n,co,p]      = sum_t sum_q b(p,t,q) Y_t[n,co,q]           sampling, Cout wide
+ *         Z_t[n,co,q]      = sum_p b(p,t,q) gO[n,co,p]                  scatter, Cout wide (fp32 atomics)
+ *         grad_input       = sum_t sum_co W[co,c,t] Z_t[n,co,q]         1x1 GEMM, K = kH kW Cout (MFMA)
+ *         grad_weight      = sum_{n,q} Z_t[n,co,q] X[n,c,q]             1x1 weight-gradient GEMM, K = N H W (MFMA)
+ *         grad_offset[p,t] = sum_co gO[n,co,p] d/dpos sum_q b(p,t,q) Y_t[n,co,q]
+ *   Tensors and the order of the geometry arguments are (i)'s: input, offset, output, grad_output, the three gradients fp32 NCHW,
+ *   weight OIHW fp32; every fp32 pointer on a 4-byte boundary.  Y is (N, H, W, YC) in `dtype`, YC = kH kW ceil8(Cout) rounded up to a
+ *   multiple of 64, tdrn_deform_conv_ts_y_bytes bytes on a 16-byte boundary.
+ *   Scope: deformable_group = 1; dtype TDRN_BF16 or TDRN_F16; Cin % 64 == 0; 1 <= Cout <= 256; any kernel, stride, padding and
+ *   dilation (i-b) accepts (Y lives on input pixels, so Ho x Wo need not be H x W).  Outside it: TDRN_E_UNSUPPORTED; so is any
+ *   buffer (a tensor, Y, Z) of 2^31 elements or more.  A NULL or misaligned required pointer: TDRN_E_ARG; a failed shape_check:
+ *   TDRN_E_SHAPE; a short workspace: TDRN_E_WORKSPACE.  Every refusal is decided before the first launch.  The queries are pure
+ *   host functions and return 0 where the entries refuse.  No allocation, no host synchronisation: everything is enqueued on `stream`.
+ *   Numerics: X, W and Z are rounded ONCE to `dtype`, to nearest even; Y is the GEMM's fp32 sum rounded once; everything else is
+ *   fp32 (the four bilinear weights are the reference's fp32 products; taps are summed in tap order).
+ *   forward:  output is OVERWRITTEN.  y_save: NULL, or it receives Y for the backward.
+ *   backward: ONE entry, so that Z is scattered once and serves grad_input and grad_weight.  Each of grad_input, grad_offset and
+ *     grad_weight may be NULL (not all three) and is OVERWRITTEN otherwise; work that nobody asked for is skipped: grad_offset needs
+ *     no Z, grad_input and grad_weight need no Y.  y_saved: the forward's Y, or NULL: Y is recomputed (the same bits).  grad_offset
+ *     has the one-sided derivative at integer coordinates and a zero derivative along an axis inside its clamp band, as (i-b).
+ *   Reproducibility: output, Y and grad_offset are bitwise reproducible (no atomics, fixed summation orders).  grad_input and
+ *     grad_weight are not: the float atomics into Z arrive in any order, as with (i-b)'s grad_input; behind Z every sum has a
+ *     fixed order.
+ * ====================================================================================== */
+TDRN_API size_t tdrn_deform_conv_ts_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW,
+                                                    int padH, int dilationH, int dilationW, int deformable_group, tdrn_dtype dtype);
+TDRN_API size_t tdrn_deform_conv_ts_y_bytes(int N, int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH,
+                                            int dilationH, int dilationW, int deformable_group, tdrn_dtype dtype);
+TDRN_API int tdrn_deform_conv_ts_forward(const float *input, const float *weight, const float *offset, float *output, void *y_save,
+                                         int N, int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH,
+                                         int dilationH, int dilationW, int deformable_group, tdrn_dtype dtype, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+TDRN_API int tdrn_deform_conv_ts_backward(const float *input, const float *weight, const float *offset, const float *grad_output,
+                                          const void *y_saved, float *grad_input, float *grad_offset, float *grad_weight, int N,
+                                          int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH,
+                                          int dilationH, int dilationW, int deformable_group, tdrn_dtype dtype, void *workspace,
+                                          size_t workspace_bytes, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

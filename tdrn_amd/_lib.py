@@ -115,6 +115,10 @@ _SIGS = {
     "tdrn_deform_conv_backward_input": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "tdrn_deform_conv_backward_parameters": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_float, C.c_void_p, C.c_size_t,
                                                                                             C.c_void_p]),
+    "tdrn_deform_conv_ts_workspace_bytes": (C.c_size_t, [C.c_int] * 15),
+    "tdrn_deform_conv_ts_y_bytes": (C.c_size_t, [C.c_int] * 15),
+    "tdrn_deform_conv_ts_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 15 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tdrn_deform_conv_ts_backward": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 15 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     **_conv_family("tdrn_conv2d", 14),
     **_conv_family("tdrn_conv_transpose2d", 16),
     **_conv_family("tdrn_conv2d_strided", 14),

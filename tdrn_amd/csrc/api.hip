@@ -386,6 +386,96 @@ int max_pool_plan(int N, int C, int H, int W, int k, int s, int p, int ceil_mode
     return TDRN_OK;
 }
 
+// The transform-domain deformable conv (section i-l): one plan and one workspace size for the forward and the backward.
+// Workspace: zero page | X 16-bit NHWC | Y (when the caller holds none) | the packed weight of the GEMM that runs (Y's or grad_input's)
+// | a zero bias | launch_conv's split-K partials | grad_output / the sampled result as fp32 [pixel][Cout] | Z fp32 | Z 16-bit | the
+// NHWC fp32 grad_input or, after it, the weight gradient's slabs.
+struct DeformTsPlan {
+    DeformBwdGeom g;
+    ConvArgs ygemm, dgrad;      // launch_conv's arguments without their pointers: X -> Y (16-bit result), Z -> grad_input (fp32 NHWC)
+    ConvBwdGeom wg;             // the weight gradient: a one-tap GEMM with Z as its "grad_output"
+    int YC;
+    size_t y_bytes, z_elems;
+    size_t o_zero, o_x, o_y, o_w, o_bias, o_partial, o_go, o_z32, o_z16, o_gin, o_slab, total;
+};
+
+// the product of positive factors stays below 2^31 (a partial product at the limit settles it before anything can overflow)
+bool below_2_31(std::initializer_list<long long> factors)
+{
+    long long e = 1;
+    for (long long f : factors) {
+        if (f >= (1ll << 31)) return false;
+        e *= f;
+        if (e >= (1ll << 31)) return false;
+    }
+    return true;
+}
+
+int deform_ts_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int dH, int dW, int padH, int padW, int dilH, int dilW, int G,
+                   int dtype, DeformTsPlan &t)
+{
+    // shape_check as in deform_plan, without its "input image is smaller than kernel" rule: Y lives on input pixels and a padded
+    // window that fits is all the sampling needs (a 1 x 1 map under a 3 x 3 kernel with pad 1 is covered)
+    if (!conv_sizes_ok(N, Cin, Cout, H, W, kH, kW, dH, dW, padH, padW, dilH, dilW) || G <= 0 || Cin % G != 0) return TDRN_E_SHAPE;
+    if (!dtype_ok(dtype)) return TDRN_E_ARG;
+    if (!conv_window_fits(H, W, kH, kW, padH, padW, dilH, dilW)) return TDRN_E_SHAPE;
+    // what the kernels cover
+    if (G != 1 || !dtype16_ok(dtype) || Cin % kChanPad != 0 || Cout > 256) return TDRN_E_UNSUPPORTED;
+    if (!below_2_31({kH, kW}) || !below_2_31({dilH, kH}) || !below_2_31({dilW, kW})) return TDRN_E_UNSUPPORTED;
+    const long long Ho = ((long long)H + 2ll * padH - ((long long)dilH * (kH - 1) + 1)) / dH + 1;
+    const long long Wo = ((long long)W + 2ll * padW - ((long long)dilW * (kW - 1) + 1)) / dW + 1;
+    const long long taps = (long long)kH * kW, cols = (taps * deform_ts_cp(Cout) + kChanPad - 1) / kChanPad * kChanPad;
+    // every buffer below 2^31 elements: the tensors, Y and Z, the packed weights; and the coordinates of deform_sample stay ints
+    if (!below_2_31({N, H, W, Cin}) || !below_2_31({N, H, W, cols}) || !below_2_31({N, Ho, Wo, Cout}) || !below_2_31({N, Ho, Wo, 2 * taps}) ||
+        !below_2_31({Cout, Cin, taps}) || !below_2_31({conv_n_pad(Cin), cols}) || !below_2_31({cols + 128, Cin}) ||
+        !below_2_31({Ho, dH}) || !below_2_31({Wo, dW}))
+        return TDRN_E_UNSUPPORTED;
+    t.g = DeformBwdGeom{N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW, G, (int)Ho, (int)Wo};
+    t.YC = deform_ts_cols(t.g);
+    const size_t es = dtype_bytes(dtype), Mx = (size_t)N * H * W, M = (size_t)N * Ho * Wo;
+    t.z_elems = Mx * t.YC;
+    t.y_bytes = t.z_elems * es;
+    t.wg = ConvBwdGeom{N, Cin, H, W, t.YC, 1, 0, 1, H, W};
+    ConvArgs &y = t.ygemm, &d = t.dgrad;        // both 1x1 at stride 1 over H x W pixels: ConvArgs' defaults
+    y.B = d.B = N;
+    y.H = y.Ho = d.H = d.Ho = H; y.W = y.Wo = d.W = d.Wo = W;
+    y.Cin = Cin; y.Cout = t.YC; y.Npad = conv_n_pad(t.YC);
+    d.Cin = t.YC; d.Cout = Cin; d.Npad = conv_n_pad(Cin);
+    conv_train_dense_out(y);
+    conv_train_dense_out(d);
+    conv_train_args(y, dtype);
+    y.out_f32 = 0;                              // Y is rounded once, in the GEMM's epilogue
+    y.splitk = 1;
+    y.splitk = conv_splitk_choice(y);
+    conv_train_args(d, dtype);
+    const size_t wy = (size_t)y.Npad * y.Cin * es, wd = (size_t)d.Npad * d.Cin * es;
+    const size_t py = conv_splitk_bytes(y, y.splitk), pd = conv_splitk_bytes(d, d.splitk);
+    size_t o = 0;
+    t.o_zero = o;    o += kZeroPageBytes;
+    t.o_x = o;       o += align_up(Mx * Cin * es, 256);
+    t.o_y = o;       o += align_up(t.y_bytes, 256);
+    t.o_w = o;       o += align_up(std::max(wy, wd), 256);
+    t.o_bias = o;    o += align_up((size_t)std::max(y.Npad, d.Npad) * 4, 256);
+    t.o_partial = o; o += align_up(std::max(py, pd), 256);
+    t.o_go = o;      o += align_up(M * Cout * 4, 256);
+    t.o_z32 = o;     o += align_up(t.z_elems * 4, 256);
+    t.o_z16 = o;     o += align_up(t.z_elems * es, 256);
+    t.o_gin = t.o_slab = o;
+    t.total = o + std::max(align_up(Mx * Cin * 4, 256), conv_wgrad_slab_bytes(t.wg));
+    return TDRN_OK;
+}
+
+// Y = X W^T into `y` (the caller's buffer or the workspace's): X is in the workspace already
+int deform_ts_ygemm(const DeformTsPlan &t, char *ws, const float *weight, void *y, int dtype, hipStream_t s)
+{
+    ConvArgs a = t.ygemm;
+    TDRN_TRY(launch_deform_ts_repack(t.g, weight, ws + t.o_w, a.Npad, 0, dtype, s));
+    TDRN_TRY(conv_train_bias(a, ws + t.o_bias, nullptr, s));
+    a.in = ws + t.o_x; a.w = ws + t.o_w; a.zero_page = ws + t.o_zero; a.bias = (const float *)(ws + t.o_bias); a.out = y;
+    if (a.splitk > 1) a.partial = ws + t.o_partial;
+    return launch_conv(a, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -494,6 +584,92 @@ int tdrn_deform_conv_backward_parameters(const float *input, const float *offset
     float *in_nhwc = (float *)(ws + b.o_in);
     TDRN_TRY(launch_nchw_to_nhwc_grouped(input, in_nhwc, N, Cin, H * W, deformable_group, deform_bwd_cpg64(b.g), TDRN_F32, s));
     return launch_deform_bwd_weight(b.g, in_nhwc, offset, grad_output, (float *)(ws + b.o_slab), grad_weight, scale, s);
+}
+
+// ---- section (i-l): the transform-domain deformable conv ---------------------------------------------------------------------------------
+size_t tdrn_deform_conv_ts_workspace_bytes(int N, int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH,
+                                           int dilationH, int dilationW, int deformable_group, tdrn_dtype dtype)
+{
+    DeformTsPlan t;
+    return deform_ts_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, dtype, t) == TDRN_OK ? t.total : 0;
+}
+
+size_t tdrn_deform_conv_ts_y_bytes(int N, int Cin, int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH, int dilationH,
+                                   int dilationW, int deformable_group, tdrn_dtype dtype)
+{
+    DeformTsPlan t;
+    return deform_ts_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, dtype, t) == TDRN_OK ? t.y_bytes : 0;
+}
+
+int tdrn_deform_conv_ts_forward(const float *input, const float *weight, const float *offset, float *output, void *y_save, int N, int Cin,
+                                int H, int W, int Cout, int kW, int kH, int dW, int dH, int padW, int padH, int dilationH, int dilationW,
+                                int deformable_group, tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !offset || !output) return TDRN_E_ARG;
+    if (off_dword(input) || off_dword(weight) || off_dword(offset) || off_dword(output) || off_16(y_save)) return TDRN_E_ARG;
+    DeformTsPlan t;
+    TDRN_TRY(deform_ts_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, dtype, t));
+    if (!workspace || workspace_bytes < t.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    void *y = y_save ? y_save : (void *)(ws + t.o_y);
+    const int HoWo = t.g.Ho * t.g.Wo;
+    TDRN_TRY(launch_fill_zero(ws + t.o_zero, kZeroPageBytes, s));
+    TDRN_TRY(launch_nchw_to_nhwc(input, ws + t.o_x, N, Cin, H * W, Cin, dtype, s));
+    TDRN_TRY(deform_ts_ygemm(t, ws, weight, y, dtype, s));
+    TDRN_TRY(launch_deform_ts_sample(t.g, y, offset, (float *)(ws + t.o_go), dtype, s));
+    return launch_nhwc_to_nchw_f32((const float *)(ws + t.o_go), (long long)HoWo * Cout, Cout, output, N, Cout, HoWo, s);
+}
+
+int tdrn_deform_conv_ts_backward(const float *input, const float *weight, const float *offset, const float *grad_output, const void *y_saved,
+                                 float *grad_input, float *grad_offset, float *grad_weight, int N, int Cin, int H, int W, int Cout, int kW,
+                                 int kH, int dW, int dH, int padW, int padH, int dilationH, int dilationW, int deformable_group,
+                                 tdrn_dtype dtype, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!input || !weight || !offset || !grad_output || (!grad_input && !grad_offset && !grad_weight)) return TDRN_E_ARG;
+    if (off_dword(input) || off_dword(weight) || off_dword(offset) || off_dword(grad_output) || off_16(y_saved) || off_dword(grad_input) ||
+        off_dword(grad_offset) || off_dword(grad_weight))
+        return TDRN_E_ARG;
+    DeformTsPlan t;
+    TDRN_TRY(deform_ts_plan(N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilationH, dilationW, deformable_group, dtype, t));
+    if (!workspace || workspace_bytes < t.total) return TDRN_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    const bool need_z = grad_input || grad_weight, need_y = grad_offset != nullptr;
+    const int HW = H * W, HoWo = t.g.Ho * t.g.Wo;
+    TDRN_TRY(launch_fill_zero(ws + t.o_zero, kZeroPageBytes, s));
+    if (grad_weight || (need_y && !y_saved)) TDRN_TRY(launch_nchw_to_nhwc(input, ws + t.o_x, N, Cin, HW, Cin, dtype, s));
+    const void *y = nullptr;
+    if (need_y) {
+        y = y_saved;
+        if (!y) {
+            TDRN_TRY(deform_ts_ygemm(t, ws, weight, ws + t.o_y, dtype, s));
+            y = ws + t.o_y;
+        }
+    }
+    float *go = (float *)(ws + t.o_go), *z32 = (float *)(ws + t.o_z32);
+    TDRN_TRY(launch_nchw_to_nhwc(grad_output, go, N, Cout, HoWo, Cout, TDRN_F32, s));
+    if (need_z) TDRN_TRY(launch_fill_zero(z32, t.z_elems * 4, s));
+    // one pass over (pixel, tap): grad_offset from Y's corners, Z by atomics
+    TDRN_TRY(launch_deform_ts_backward(t.g, y, offset, go, need_z ? z32 : nullptr, grad_offset, dtype, s));
+    if (!need_z) return TDRN_OK;
+    TDRN_TRY(launch_deform_ts_round(z32, ws + t.o_z16, (long long)t.z_elems, dtype, s));
+    if (grad_input) {
+        ConvArgs a = t.dgrad;
+        TDRN_TRY(launch_deform_ts_repack(t.g, weight, ws + t.o_w, a.Npad, 1, dtype, s));
+        TDRN_TRY(conv_train_bias(a, ws + t.o_bias, nullptr, s));
+        a.in = ws + t.o_z16; a.w = ws + t.o_w; a.zero_page = ws + t.o_zero; a.bias = (const float *)(ws + t.o_bias); a.out = ws + t.o_gin;
+        if (a.splitk > 1) a.partial = ws + t.o_partial;
+        TDRN_TRY(launch_conv(a, s));
+        TDRN_TRY(launch_nhwc_to_nchw_f32((const float *)(ws + t.o_gin), a.o_bs, a.Cout, grad_input, N, Cin, HW, s));
+    }
+    if (grad_weight) {
+        int splits;
+        const float *bslab;
+        TDRN_TRY(launch_conv_wgrad_slabs(t.wg, ws + t.o_x, ws + t.o_z16, ws + t.o_zero, ws + t.o_slab, dtype, s, splits, bslab));
+        TDRN_TRY(launch_deform_ts_wgrad_reduce(t.g, (const float *)(ws + t.o_slab), grad_weight, splits, s));
+    }
+    return TDRN_OK;
 }
 
 // The entries of the trainable conv families (ConvTrainPlan above): pointer check, plan, then conv_train_begin, layout conversion(s),

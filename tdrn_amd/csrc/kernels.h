@@ -249,6 +249,20 @@ int launch_deform_bwd_input_add(const DeformBwdGeom &g, const float *gin_nhwc, f
 void deform_bwd_weight_splits(const DeformBwdGeom &g, int &splits, int &per_split);
 int launch_deform_bwd_weight(const DeformBwdGeom &g, const float *in_nhwc, const float *off, const float *gout, float *slab, float *grad_weight,
                              float scale, hipStream_t s);
+// Transform-domain deformable conv with gradients, G = 1, 16-bit types (deform_ts.hip; tdrn_hip.h section i-l).  Y and Z are pixel-major
+// over INPUT pixels, [N H W][deform_ts_cols] with column t * deform_ts_cp(Cout) + co and zero padding behind the last tap.
+int deform_ts_cp(int Cout);                         // Cout rounded up to 8
+int deform_ts_cols(const DeformBwdGeom &g);         // kh kw deform_ts_cp(Cout) rounded up to kChanPad
+// OIHW fp32 -> DT: dgrad = 0: [Npad][Cin] with row t Cp + co (launch_conv's weight of Y); dgrad = 1: [Npad][cols] with row c (of grad_input)
+int launch_deform_ts_repack(const DeformBwdGeom &g, const float *w, void *out, int Npad, int dgrad, int dtype, hipStream_t s);
+// out_nhwc [N Ho Wo][Cout] fp32 = the blend of Y's corner rows; off: the caller's NCHW offsets
+int launch_deform_ts_sample(const DeformBwdGeom &g, const void *y, const float *off, float *out_nhwc, int dtype, hipStream_t s);
+// go_nhwc [N Ho Wo][Cout] fp32.  y and goff both or neither: goff (NCHW) is stored once.  z (or null; fp32, zeroed by the caller) += b gO
+int launch_deform_ts_backward(const DeformBwdGeom &g, const void *y, const float *off, const float *go_nhwc, float *z, float *goff,
+                              int dtype, hipStream_t s);
+int launch_deform_ts_round(const float *in, void *out, long long elems, int dtype, hipStream_t s);      // fp32 -> DT; elems % 8 == 0
+// grad_weight (OIHW, overwritten) = the sum in split order of the slabs [splits][cols][Cin] of launch_conv_wgrad_slabs
+int launch_deform_ts_wgrad_reduce(const DeformBwdGeom &g, const float *slab, float *grad_weight, int splits, hipStream_t s);
 // Dense stride-1 conv backward (conv_bwd.hip; tdrn_hip.h section i-c).  x_nhwc / go_nhwc: the input and grad_output as NHWC in the compute
 // type, channels padded to conv_bwd_cpad (launch_nchw_to_nhwc).  Square kernels k = 1 | 3, one pad / dilation for both axes.
 // stride (trailing, default 1: every positional initialiser keeps its meaning) steps the output pixel of the weight gradient: 2 for

@@ -202,6 +202,17 @@ class TrainWalk(object):
         if resident and compute not in ("bf16", "fp16"):
             raise ValueError("forward_train: resident=True needs compute 'bf16' or 'fp16', got %r" % (compute,))
 
+    def _check_deform_algo(self, deform_algo, compute):
+        """forward_train's `deform_algo` switch of the dual-refinement models, checked like `resident` before anything else happens:
+        "gather" (conv_offset2d, the default) or "transform" (conv_offset2d_ts: 16-bit compute types, one deformable group)"""
+        if deform_algo not in ("gather", "transform"):
+            raise ValueError("forward_train: deform_algo must be 'gather' or 'transform', got %r" % (deform_algo,))
+        if deform_algo == "transform":
+            if compute not in ("bf16", "fp16"):
+                raise ValueError("forward_train: deform_algo='transform' needs compute 'bf16' or 'fp16', got %r" % (compute,))
+            if self.def_groups != 1:
+                raise NotImplementedError("forward_train: deform_algo='transform' covers def_groups=1, this model has %d" % self.def_groups)
+
     @staticmethod
     def _resident_conv(m):
         """a conv the resident path takes: the stride-1 family of conv2d_nhwc with whole 64-channel blocks on both sides"""
@@ -338,9 +349,11 @@ class TrainWalk(object):
         odm_sources.reverse()
         return odm_sources
 
-    def _head_train(self, arm_sources, x, compute):
+    def _head_train(self, arm_sources, x, compute, deform_algo="gather"):
         """ARM loc / offsets, last_layer_trans, the TCB pyramid and the deformable heads (add_refine_head's modules, with or without
-        biases) from the four ARM sources and the last feature map x -> forward_train's 4-tuple"""
+        biases) from the four ARM sources and the last feature map x -> forward_train's 4-tuple.
+        deform_algo="transform": the loc and conf heads of one (level, branch) run as ONE conv_offset2d_ts over their concatenated
+        weights (one Y, one scatter, one grad_offset: what _paired_heads does for SSD4Scale); the multihead branch is a second call."""
         B = x.size(0)
         conv = lambda m, t, pad: networks.conv2d(t, m.weight, m.bias, pad, 1, compute)
         arm_loc, off1, off2 = [], [], []
@@ -358,8 +371,12 @@ class TrainWalk(object):
                 heads.append((self.odm_loc_2[s], self.odm_conf_2[s], off2[s]))
             l = c = None
             for hl, hc, off in heads:
-                dl, dc = (networks.conv_offset2d(ob, off, h.weight, h.stride, h.padding, h.dilation, h.num_deformable_groups, compute)
-                          for h in (hl, hc))
+                if deform_algo == "transform":
+                    both = networks.conv_offset2d_ts(ob, off, torch.cat([hl.weight, hc.weight]), hl.stride, hl.padding, hl.dilation, compute)
+                    dl, dc = both.split([hl.out_channels, hc.out_channels], 1)
+                else:
+                    dl, dc = (networks.conv_offset2d(ob, off, h.weight, h.stride, h.padding, h.dilation, h.num_deformable_groups, compute)
+                              for h in (hl, hc))
                 l, c = (dl, dc) if l is None else (l + dl, c + dc)
             odm_loc.append(l.permute(0, 2, 3, 1).contiguous().view(B, -1))
             odm_conf.append(c.permute(0, 2, 3, 1).contiguous().view(B, -1))

@@ -35,18 +35,20 @@ class RefineSSD(EngineModule, TrainWalk):
         conf = r["conf"] if self.phase == 'test' else r["conf"].view(x.size(0), -1, self.num_classes)
         return (r["arm_loc"], None, r["odm_loc"], conf)
 
-    def forward_train(self, x, compute="fp32", resident=False):
+    def forward_train(self, x, compute="fp32", resident=False, deform_algo="gather"):
         """-> (arm_loc (B, P, 4), None, odm_loc (B, P, 4), conf (B, P, num_classes) raw logits): the phase-'train' outputs of
         forward (the reference's :127-199), computed from this module's fp32 parameters with an autograd graph.  BatchNorm runs in
         the module's mode (self.training: batch statistics, running buffers updated with each layer's momentum; else the running
         buffers).  `compute` ("fp32" | "bf16" | "fp16") is the MFMA input type of the dense conv-type ops and the deformable heads;
         the depthwise convs, BatchNorm and L2Norm are fp32.  The engine's packed weights are marked stale, so net(x) after an
         optimizer step re-packs by itself.  resident=True raises NotImplementedError: the resident path
-        covers the VGG trunks, and this trunk's depthwise conv is fp32 NCHW."""
+        covers the VGG trunks, and this trunk's depthwise conv is fp32 NCHW.  deform_algo: "gather" (the default, conv_offset2d) or
+        "transform" (conv_offset2d_ts; compute "bf16" | "fp16" and def_groups == 1), as in dualrefinedet_vggbn."""
         self._check_resident(resident, compute, vgg_trunk=False)
+        self._check_deform_algo(deform_algo, compute)
         x = self._train_input(x)
         arm_sources, x = self._mobilenet_sources(x, compute, resident)
-        return self._head_train(arm_sources, x, compute)
+        return self._head_train(arm_sources, x, compute, deform_algo)
 
 
 def build_net(phase, size=320, num_classes=21, def_groups=1, multihead=False):

@@ -65,7 +65,7 @@ class RefineSSD(EngineModule, TrainWalk):
         conf = r["conf"] if self.phase == 'test' else r["conf"].view(x.size(0), -1, self.num_classes)
         return (r["arm_loc"], r["offsets"] if self.phase == 'test' else None, r["odm_loc"], conf)
 
-    def forward_train(self, x, compute="fp32", resident=False):
+    def forward_train(self, x, compute="fp32", resident=False, deform_algo="gather"):
         """-> (arm_loc (B, P, 4), None, odm_loc (B, P, 4), conf (B, P, num_classes) raw logits): the phase-'train' outputs of
         forward, computed from this module's fp32 parameters with an autograd graph.  BatchNorm runs in the module's mode
         (self.training: batch statistics, running buffers updated with each layer's momentum; else the running buffers).
@@ -74,11 +74,16 @@ class RefineSSD(EngineModule, TrainWalk):
         conv1_1, up to and including fc7, as 16-bit NHWC tensors between layers (networks.conv2d_nhwc, batch_norm_nhwc,
         max_pool2d_nhwc): each conv and BatchNorm output is rounded once to the type; parameters, statistics and everything behind
         the taps and fc7 are as with resident=False, which is the default and unchanged.
+        deform_algo="transform" (compute "bf16" | "fp16", ValueError otherwise; def_groups == 1, NotImplementedError otherwise) runs
+        the deformable ODM heads through networks.conv_offset2d_ts: forward and backward in the transform domain and in `compute`,
+        the loc and conf heads of a level as one call.  "gather", the default, is networks.conv_offset2d as
+        before; any other value raises ValueError.
         The engine's packed weights are marked stale, so net(x) after an optimizer step re-packs by itself."""
         self._check_resident(resident, compute)
+        self._check_deform_algo(deform_algo, compute)
         x = self._train_input(x)
         arm_sources, x = self._vgg_sources(x, compute, resident)
-        return self._head_train(arm_sources, x, compute)
+        return self._head_train(arm_sources, x, compute, deform_algo)
 
 
 def build_net(phase, size=320, num_classes=21, c7_channel=1024, def_groups=1, bn=True, multihead=False,

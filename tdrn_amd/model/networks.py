@@ -176,6 +176,99 @@ def conv_offset2d(input, offset, weight, stride=1, padding=0, dilation=1, deform
     return _deform_forward(x, off, w, stride, padding, dilation, deform_groups, compute)
 
 
+_DEFORM_TS_COVERED = ("conv_offset2d_ts covers one deformable group, compute 'bf16' or 'fp16', Cin a multiple of 64, 1 <= Cout <= 256 and "
+                      "tensors (input, offset, output, the transform Y of kH*kW*ceil8(Cout) columns per input pixel) below 2^31 elements; "
+                      "got input %r, offset %r, weight %r, stride %r, padding %r, dilation %r, compute %r")
+
+
+def _deform_ts_dims(x, off, w, stride, padding, dilation, compute):
+    """the checks of the transform-domain op that need no device, in this order: compute (ValueError), the shapes (_deform_geometry),
+    the library's scope (RuntimeError naming what is covered) -> (the C ABI's dims, the output's shape, the workspace's bytes)"""
+    if compute not in ("bf16", "fp16"):
+        raise ValueError("conv_offset2d_ts: compute must be 'bf16' or 'fp16', got %r (the fp32 op is conv_offset2d)" % (compute,))
+    dims, out_shape = _deform_geometry(x, off, w, stride, padding, dilation, 1)
+    nb = _lib.lib().tdrn_deform_conv_ts_workspace_bytes(*dims, _lib.DTYPES[compute])
+    if nb == 0:
+        raise RuntimeError(_DEFORM_TS_COVERED % (tuple(x.shape), tuple(off.shape), tuple(w.shape), stride, padding, dilation, compute))
+    return dims, out_shape, nb
+
+
+def _deform_ts_forward(x, off, w, stride, padding, dilation, compute, save_y):
+    """-> (output, Y as a uint8 tensor when save_y else None)"""
+    lib = _lib.lib()
+    dims, out_shape, nb = _deform_ts_dims(x, off, w, stride, padding, dilation, compute)
+    _lib.require_cuda(x, "input")
+    dt = _lib.DTYPES[compute]
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    y = torch.empty(lib.tdrn_deform_conv_ts_y_bytes(*dims, dt), dtype=torch.uint8, device=x.device) if save_y else None
+    _lib.check(lib.tdrn_deform_conv_ts_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(out), _lib.ptr(y), *dims, dt,
+                                               _lib.ptr(ws), nb, _lib.current_stream(x.device)), "tdrn_deform_conv_ts_forward")
+    return out, y
+
+
+class ConvOffset2dTsFunction(torch.autograd.Function):
+    """Deformable conv v1 with gradients in the transform domain (tdrn_hip.h section i-l): one deformable
+    group, compute "bf16" | "fp16".  The forward forms Y = the 1x1 product of the un-deformed input with every tap's weight on MFMA
+    and samples rows of Cout values; the backward is ONE call of tdrn_deform_conv_ts_backward, with null pointers for the gradients
+    that needs_input_grad does not ask for, in the same compute type.  Saved: input, offset, weight and (save_y, the default) Y;
+    save_y = False recomputes Y in the backward, to the same bits.
+
+        y = ConvOffset2dTsFunction.apply(input, offset, weight, stride, padding, dilation[, compute])
+    """
+
+    save_y = True
+
+    @staticmethod
+    def forward(ctx, input, offset, weight, stride=1, padding=0, dilation=1, compute="bf16"):
+        if input.dim() != 4:
+            raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+        x, off, w = input.contiguous().float(), offset.contiguous().float(), weight.contiguous().float()
+        out, y = _deform_ts_forward(x, off, w, stride, padding, dilation, compute, ConvOffset2dTsFunction.save_y)
+        ctx.conf = (stride, padding, dilation, compute)
+        ctx.save_for_backward(*((x, off, w) if y is None else (x, off, w, y)))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, off, w = ctx.saved_tensors[:3]
+        y = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        stride, padding, dilation, compute = ctx.conf
+        dims, out_shape, nb = _deform_ts_dims(x, off, w, stride, padding, dilation, compute)
+        go = _grad_output(grad_output, out_shape, "conv_offset2d_ts")
+        need_in, need_off, need_w = ctx.needs_input_grad[:3]
+        if not (need_in or need_off or need_w):
+            return (None,) * 7
+        lib = _lib.lib()
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        gi = torch.empty_like(x) if need_in else None
+        goff = torch.empty_like(off) if need_off else None
+        gw = torch.empty_like(w) if need_w else None
+        _lib.check(lib.tdrn_deform_conv_ts_backward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(go), _lib.ptr(y), _lib.ptr(gi),
+                                                    _lib.ptr(goff), _lib.ptr(gw), *dims, _lib.DTYPES[compute], _lib.ptr(ws), nb,
+                                                    _lib.current_stream(x.device)), "tdrn_deform_conv_ts_backward")
+        return gi, goff, gw, None, None, None, None
+
+
+def conv_offset2d_ts(input, offset, weight, stride=1, padding=0, dilation=1, compute="bf16"):
+    """Deformable conv v1, one deformable group, by the transform-then-sample algorithm: an opt-in sibling of conv_offset2d whose
+    forward AND backward run in the 16-bit `compute` type ("bf16" | "fp16"; "fp32" raises ValueError), with all Cin-wide arithmetic
+    on MFMA.  NCHW fp32 tensors in, NCHW fp32 out, no bias.  The dispatch rule is conv_offset2d's: differentiable exactly when
+    torch.is_grad_enabled() and the input or the offset requires grad; otherwise the output has no grad_fn.
+    A geometry outside the library's scope raises RuntimeError naming what is covered, CPU tensors raise NotImplementedError: there
+    is no fall-back to the gather op.  grad_input and grad_weight come through float atomics (their low bits depend on arrival
+    order); the output and grad_offset are bitwise reproducible."""
+    if input is not None and input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    if torch.is_grad_enabled() and (input.requires_grad or offset.requires_grad):
+        return ConvOffset2dTsFunction.apply(input, offset, weight, stride, padding, dilation, compute)
+    x = input.contiguous().float()
+    off = offset.contiguous().float()
+    w = weight.detach().contiguous().float()
+    return _deform_ts_forward(x, off, w, stride, padding, dilation, compute, False)[0]
+
+
 class ConvOffset2d(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
                  num_deformable_groups=1):
