@@ -20,10 +20,12 @@ def _pr(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
 
-def deform_conv(x, off, w, stride=1, padding=0, dilation=1, G=1, with_coords=False):
+def deform_conv(x, off, w, stride=1, padding=0, dilation=1, G=1, with_coords=False, tap_cols=None):
     """x (N,Cin,H,W), off (N,G*2*kh*kw,Ho,Wo), w (Cout,Cin,kh,kw): fp64 CPU tensors (may require grad).
     Returns out (N,Cout,Ho,Wo) fp64; with_coords=True also the fp32 sample coordinates (h_im, w_im) of every
-    (n, g, tap, ho, wo) -- what the tests use to find the measure-zero points."""
+    (n, g, tap, ho, wo) -- what the tests use to find the measure-zero points.
+    tap_cols: None is the op (tap t sits at divmod(t, kw)); another divisor restates a kernel that splits its taps wrongly, for the
+    tests that show such a kernel could not pass (tests/test_deform_ts_ref.py)."""
     (sh, sw), (ph, pw), (dh, dw) = _pr(stride), _pr(padding), _pr(dilation)
     N, Cin, H, W = x.shape
     Cout, _, kh, kw = w.shape
@@ -39,7 +41,7 @@ def deform_conv(x, off, w, stride=1, padding=0, dilation=1, G=1, with_coords=Fal
         xg = xf[:, g * cpg:(g + 1) * cpg]
         gcols = []
         for t in range(taps):
-            ti, tj = divmod(t, kw)
+            ti, tj = divmod(t, kw if tap_cols is None else tap_cols)
             oh = off[:, g * 2 * taps + 2 * t]
             ow = off[:, g * 2 * taps + 2 * t + 1]
             oh32, ow32 = oh.detach().float(), ow.detach().float()
@@ -83,11 +85,11 @@ def deform_conv(x, off, w, stride=1, padding=0, dilation=1, G=1, with_coords=Fal
     return out
 
 
-def grads(x, off, w, grad_out, stride=1, padding=0, dilation=1, G=1):
+def grads(x, off, w, grad_out, stride=1, padding=0, dilation=1, G=1, tap_cols=None):
     """(out, grad_input, grad_offset, grad_weight), all fp64 CPU tensors, for numpy / torch inputs."""
     t = lambda a: torch.as_tensor(a).detach().double().clone().requires_grad_(True)
     x, off, w = t(x), t(off), t(w)
-    out = deform_conv(x, off, w, stride, padding, dilation, G)
+    out = deform_conv(x, off, w, stride, padding, dilation, G, tap_cols=tap_cols)
     gx, go, gw = torch.autograd.grad(out, (x, off, w), torch.as_tensor(grad_out).double())
     return out.detach(), gx, go, gw
 

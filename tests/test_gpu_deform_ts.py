@@ -1,5 +1,6 @@
 """The transform-domain deformable conv (tdrn_hip.h section i-l) on the GPU: the C entries and the Python op
-against the float64 oracle of tests/_deform_grad_ref.py.
+against the float64 oracle of tests/_deform_grad_ref.py.  The entries' wrapper, the inputs, the references and the bound are those of
+tests/_deform_ts_harness.py (shared with test_gpu_deform_ts_scope.py, which leaves the square stride-1 geometry of the cases here).
 
 Inputs are exact by construction, so the bound is derived, not tuned: X, W and grad_output are exactly representable in the compute
 type; offsets are fp32 multiples of 2^-6 with |offset| <= 16, so coordinates, fractions, the four bilinear weights and b * gO are exact
@@ -17,17 +18,14 @@ The worst share of the bound is printed per result.
 The link to the gather op (conv_offset2d on the same inputs) allows the sum of both ops' bounds; the gather op's is the same
 expression: it rounds the sampled column once (U) and has the blend and the GEMM as its two fp32 stages.  The gather op keeps the
 reference's "input image is smaller than kernel" rule, so the 1 x 1 case has no such link (it raises there)."""
-import functools
-
 import pytest
 import torch
 
-from tdrn_amd import _lib
 from tdrn_amd.model import networks
 
-from _conv_train_harness import C_ACC, DEV, Guarded
-from _deform_grad_ref import grads
-from _nhwc_harness import TINY, U, exact
+from _conv_train_harness import DEV, Guarded
+from _deform_ts_harness import MODES, NAMES, REGIMES, bound, same_bits, square, within
+from _deform_ts_harness import Ts as _Ts, problem as _problem
 
 pytestmark = pytest.mark.gpu
 
@@ -39,157 +37,17 @@ CASES = [(1, 64, 1, 1, 12, 3),          # one pixel; every neighbour tap rejecte
          (1, 64, 9, 8, 105, 3),         # past 64, 80 and 96 columns
          (1, 1024, 3, 3, 63, 3),        # K = 1024
          (3, 64, 24, 24, 75, 3)]        # several workgroups
-MODES = ("bf16", "fp16")
-REGIMES = ("half", "wide", "converging")
-NAMES = ("output", "grad_input", "grad_offset", "grad_weight")
 ids = lambda c: "x".join(str(v) for v in c)
 
 
-def make_offsets(case, regime, g):
-    N, Cin, H, W, Cout, k = case
-    pad, taps = k // 2, k * k
-    if regime != "converging":
-        sigma = 0.5 if regime == "half" else float(max(H, W))
-        off = (torch.round(sigma * torch.randn(N, 2 * taps, H, W, generator=g) * 64) / 64).clamp(-16, 16)
-        kind = torch.rand(N, 2 * taps, H, W, generator=g)
-        off = torch.where(kind < 0.1, torch.zeros_like(off), off)                   # offset 0: the sample sits on its tap
-        off = torch.where((kind >= 0.1) & (kind < 0.2), torch.round(off), off)      # other integer coordinates
-        return off.float()
-    # every sample of an image is aimed at one of two of its pixels: maximal collision of the scatter's atomics
-    targets = [(H // 2, W // 2), (max(H // 2 - 1, 0), max(W // 2 - 1, 0))]
-    pick = torch.randint(0, 2, (N, taps, H, W), generator=g)
-    th = torch.tensor([targets[0][0], targets[1][0]])[pick].float()
-    tw = torch.tensor([targets[0][1], targets[1][1]])[pick].float()
-    off = torch.empty(N, 2 * taps, H, W)
-    ho = torch.arange(H).view(1, H, 1).float()
-    wo = torch.arange(W).view(1, 1, W).float()
-    for t in range(taps):
-        ti, tj = divmod(t, k)
-        off[:, 2 * t] = th[:, t] - (ho - pad + ti)
-        off[:, 2 * t + 1] = tw[:, t] - (wo - pad + tj)
-    assert float(off.abs().max()) <= 16
-    return off
-
-
-def offset_S(x, off, w, go, k, pad):
-    """sum_co |gO| sum_corners |db/dpos| Ybar, float64: the sampling geometry as the device forms it (fp32 coordinates, rejection, the
-    [H-1, H) clamp: the rule of tests/_deform_grad_ref.py), the absolute values of the four corner derivatives of the bilinear weights"""
-    N, Cin, H, W = x.shape
-    Cout, taps, HW = w.shape[0], k * k, H * W
-    ybar = torch.einsum("oct,ncq->ntoq", w.abs().double().reshape(Cout, Cin, taps), x.abs().double().reshape(N, Cin, HW))
-    ago = go.abs().double().reshape(N, Cout, HW)
-    h_in = (torch.arange(H) - pad).view(1, H, 1)
-    w_in = (torch.arange(W) - pad).view(1, 1, W)
-    S = torch.zeros(N, 2 * taps, H, W, dtype=torch.float64)
-    for t in range(taps):
-        ti, tj = divmod(t, k)
-        oh, ow = off[:, 2 * t].float(), off[:, 2 * t + 1].float()
-        h_im, w_im = (h_in + ti).float() + oh, (w_in + tj).float() + ow
-        valid = (h_im >= 0) & (w_im >= 0) & (h_im < H) & (w_im < W)
-        hm, wm = torch.tensor(float(ti)) + oh, torch.tensor(float(tj)) + ow
-        height, width = H - h_in, W - w_in
-        h_low, w_low = torch.floor(hm).long(), torch.floor(wm).long()
-        ch, cw = h_low >= height - 1, w_low >= width - 1
-        h_low = torch.where(ch, (height - 1).expand_as(h_low), h_low)
-        w_low = torch.where(cw, (width - 1).expand_as(w_low), w_low)
-        h_high, w_high = torch.where(ch, h_low, h_low + 1), torch.where(cw, w_low, w_low + 1)
-        lh = torch.where(ch, torch.zeros_like(oh, dtype=torch.float64), (ti + oh.double()) - h_low.double())
-        lw = torch.where(cw, torch.zeros_like(ow, dtype=torch.float64), (tj + ow.double()) - w_low.double())
-        hh, hw = 1 - lh, 1 - lw
-        r0, r1 = (h_in + h_low).clamp(0, H - 1), (h_in + h_high).clamp(0, H - 1)
-        q0, q1 = (w_in + w_low).clamp(0, W - 1), (w_in + w_high).clamp(0, W - 1)
-
-        def corner(r, q):
-            idx = (r * W + q).reshape(N, 1, HW).expand(N, Cout, HW)
-            return torch.gather(ybar[:, t], 2, idx)
-
-        y1, y2, y3, y4 = corner(r0, q0), corner(r0, q1), corner(r1, q0), corner(r1, q1)
-        f = lambda a: a.reshape(N, 1, HW)
-        dh = (f(hw) * (y1 + y3) + f(lw) * (y2 + y4)) * f((~ch).double())
-        dw = (f(hh) * (y1 + y2) + f(lh) * (y3 + y4)) * f((~cw).double())
-        S[:, 2 * t] = (ago * dh).sum(1).reshape(N, H, W) * valid.double()
-        S[:, 2 * t + 1] = (ago * dw).sum(1).reshape(N, H, W) * valid.double()
-    return S
-
-
-@functools.lru_cache(maxsize=None)
 def problem(case, mode, regime):
-    """inputs (CPU fp32), float64 references and absolute-value sums, computed once and left unchanged"""
-    N, Cin, H, W, Cout, k = case
-    pad = k // 2
-    g = torch.Generator().manual_seed(1000 * CASES.index(case) + 10 * REGIMES.index(regime) + MODES.index(mode))
-    x = exact(torch.randn(N, Cin, H, W, generator=g), mode)
-    w = exact(torch.randn(Cout, Cin, k, k, generator=g) / 8, mode)
-    go = exact(torch.randn(N, Cout, H, W, generator=g), mode)
-    off = make_offsets(case, regime, g)
-    assert torch.equal(off * 64, torch.round(off * 64)) and off.dtype == torch.float32
-    ref = dict(zip(NAMES, grads(x, off, w, go, 1, pad, 1, 1)))          # (out, grad_input, grad_offset, grad_weight)
-    so, sgx, _, sgw = grads(x.abs(), off, w.abs(), go.abs(), 1, pad, 1, 1)
-    S = {"output": so, "grad_input": sgx, "grad_offset": offset_S(x, off, w, go, k, pad), "grad_weight": sgw}
-    return dict(x=x, w=w, off=off, go=go, ref=ref, S=S)
+    """inputs (CPU fp32), float64 references and absolute-value sums, computed once and left unchanged (the harness caches them)"""
+    return _problem(square(*case), mode, regime, 1000 * CASES.index(case) + 10 * REGIMES.index(regime) + MODES.index(mode))
 
 
-def bound(mode, S):
-    return (U[mode] + 2 * C_ACC[mode]) * S + TINY[mode]
-
-
-def within(what, mode, name, got, p, scale=1.0):
-    d = (got.detach().cpu().double() - p["ref"][name]).abs()
-    assert torch.isfinite(d).all(), "%s %s: non-finite values" % (what, name)
-    b = scale * bound(mode, p["S"][name])
-    share = float((d / b).max())
-    print("%s %-11s max|d| %.3e  worst share of the bound %.3e" % (what, name, float(d.max()), share))
-    assert bool((d <= b).all()), (what, name, share)
-    return share
-
-
-def bits(t):
-    return t.contiguous().view(torch.uint8) if t.dtype == torch.uint8 else t.contiguous().view(torch.int32)
-
-
-def same_bits(p, q):
-    return p.shape == q.shape and torch.equal(bits(p), bits(q))
-
-
-class Ts(object):
+def Ts(case, mode):
     """the entries on plain device buffers"""
-
-    def __init__(self, case, mode):
-        N, Cin, H, W, Cout, k = case
-        self.lib, self.dt, self.case = _lib.lib(), _lib.DTYPES[mode], case
-        self.dims = (N, Cin, H, W, Cout, k, k, 1, 1, k // 2, k // 2, 1, 1, 1)
-        self.nb = self.lib.tdrn_deform_conv_ts_workspace_bytes(*self.dims, self.dt)
-        self.yb = self.lib.tdrn_deform_conv_ts_y_bytes(*self.dims, self.dt)
-        assert self.nb > 0 and self.yb > 0
-        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=DEV)
-
-    def inputs(self, p):
-        return tuple(p[n].to(DEV) for n in ("x", "w", "off", "go"))
-
-    def new_y(self):
-        return torch.full((self.yb,), 0xFF, dtype=torch.uint8, device=DEV)
-
-    def forward(self, x, w, off, out, y=None, ws=None):
-        ws = self.ws if ws is None else ws
-        _lib.check(self.lib.tdrn_deform_conv_ts_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(out), _lib.ptr(y), *self.dims,
-                                                        self.dt, _lib.ptr(ws), self.nb, _lib.current_stream(DEV)))
-        return out
-
-    def backward(self, x, w, off, go, y, gi, goff, gw, ws=None):
-        ws = self.ws if ws is None else ws
-        _lib.check(self.lib.tdrn_deform_conv_ts_backward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), _lib.ptr(go), _lib.ptr(y), _lib.ptr(gi),
-                                                         _lib.ptr(goff), _lib.ptr(gw), *self.dims, self.dt, _lib.ptr(ws), self.nb,
-                                                         _lib.current_stream(DEV)))
-
-    def all(self, p, y_given=True):
-        """-> (output, grad_input, grad_offset, grad_weight, Y), every output pre-filled with NaN"""
-        x, w, off, go = self.inputs(p)
-        nan = lambda t: torch.full_like(t, float("nan"))
-        out, gi, goff, gw, y = nan(go), nan(x), nan(off), nan(w), self.new_y()
-        self.forward(x, w, off, out, y)
-        self.backward(x, w, off, go, y if y_given else None, gi, goff, gw)
-        torch.cuda.synchronize()
-        return out, gi, goff, gw, y
+    return _Ts(square(*case), mode)
 
 
 @pytest.mark.parametrize("regime", REGIMES)
