@@ -278,16 +278,6 @@ int conv_nhwc_run(const ConvTrainPlan &p, char *ws, bool dgrad, const void *in, 
     return launch_conv(a, s);
 }
 
-// the checks the resident BatchNorm and MaxPool entries share, after their pointers and type
-int nhwc_plan(int N, int C, int H, int W)
-{
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return TDRN_E_SHAPE;
-    if (C % kChanPad) return TDRN_E_UNSUPPORTED;
-    const long long HW = (long long)H * W, NC = (long long)N * C;
-    if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    return TDRN_OK;
-}
-
 // ConvTranspose2d(k = 2, s = 2) (section i-f).  The forward is four phase GEMMs, each a 1x1 conv that writes every second pixel of
 // every second row; the input gradient is one 1x1 conv over the space-to-depth image of grad_output, whose C4 = 4 CoPad channels are
 // the (tap, cout) pairs of the sum; the weight gradient is the one-tap GEMM over that image with C4 "output channels".
@@ -354,6 +344,14 @@ int nchw_plan(int N, int C, int H, int W)
     const long long HW = (long long)H * W, NC = (long long)N * C;
     if (HW >= (1ll << 31) || NC >= (1ll << 31) || NC * HW >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
     return TDRN_OK;
+}
+
+// the checks the resident BatchNorm and MaxPool entries share, after their pointers and type: nchw_plan's, and whole channel blocks
+int nhwc_plan(int N, int C, int H, int W)
+{
+    const int rc = nchw_plan(N, C, H, W);
+    if (rc != TDRN_OK) return rc;
+    return C % kChanPad ? TDRN_E_UNSUPPORTED : TDRN_OK;
 }
 
 bool off_dword(const void *p) { return ((uintptr_t)p & 3) != 0; }

@@ -75,6 +75,80 @@ def _workspace(query, args, device, message, *what):
     return torch.empty(nb, dtype=torch.uint8, device=device), nb
 
 
+def _dispatch(function, args, tracked, plain):
+    """the grad-or-plain rule of every public op: through `function` when grad mode is on and one of `tracked` (tensors, or None)
+    requires grad; else plain(), the forward alone on detached tensors, whose output has no grad_fn"""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tracked):
+        return function.apply(*args)
+    return plain()
+
+
+# ---- resident tensors (tdrn_hip.h section i-k): activations and their gradients as 16-bit NHWC between layers ----------------------------
+_RESIDENT_DTYPES = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+_RESIDENT_NAMES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "f16": torch.float16,
+                   "float16": torch.float16, "half": torch.float16}
+RESIDENT_CHANNELS = 64          # kChanPad: a resident tensor holds whole 64-channel blocks
+
+
+def _resident_dtype(dtype):
+    dtype = _RESIDENT_NAMES.get(dtype, dtype)
+    if dtype not in _RESIDENT_DTYPES:
+        raise ValueError("a resident tensor is torch.bfloat16 or torch.float16, got %r" % (dtype,))
+    return dtype
+
+
+def _resident(t, dtype=None):
+    """`t` as a resident tensor: of `dtype` (default: its own), contiguous in channels_last, its data on a 16-byte boundary (a
+    misaligned storage is cloned)"""
+    if dtype is not None and t.dtype != dtype:
+        t = t.to(dtype)
+    t = t.contiguous(memory_format=torch.channels_last)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.channels_last)
+
+
+def _resident_input(input, op):
+    """the checks every resident op starts with -> the library's type code"""
+    if input.dim() != 4:
+        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
+    _lib.require_cuda(input, "input")
+    if input.dtype not in _RESIDENT_DTYPES:
+        raise ValueError("%s: input must be torch.bfloat16 or torch.float16 (got %s); to_nhwc makes one" % (op, input.dtype))
+    if input.shape[1] % RESIDENT_CHANNELS:
+        raise RuntimeError("%s: %d channels are outside what libtdrn_hip covers (a multiple of %d)" % (op, input.shape[1], RESIDENT_CHANNELS))
+    return _RESIDENT_DTYPES[input.dtype]
+
+
+def _resident_empty(shape, dtype, device):
+    return torch.empty(tuple(shape), dtype=dtype, device=device, memory_format=torch.channels_last)
+
+
+def _resident_grad_output(grad_output, shape, dtype, op):
+    """what every resident backward does first: a CUDA grad_output of the output's shape, made resident whatever it arrives as"""
+    if not grad_output.is_cuda:
+        raise NotImplementedError("%s backward: grad_output must be a CUDA tensor" % op)
+    if tuple(grad_output.shape) != tuple(shape):
+        raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(grad_output.shape), tuple(shape)))
+    return _resident(grad_output, dtype)
+
+
+# One tensor format of the training ops: what differs between an op on fp32 NCHW tensors and its twin on resident ones, and nothing else.
+#   infix: in the C entries' names and behind the op's name in messages; covered: the channel rule in a "shape outside" message
+#   check(input, op): the format's own checks of an op's input, before the op's
+#   ready(t): `t` as the entries read it (for max_pool2d, which has checked for float32, no cast: plain contiguous())
+#   empty(like, shape=None): an output or gradient like `like`, or of `shape` in like's type and on its device
+#   grad_output(grad_output, shape, dtype, op): what a backward does first
+#   codes(dtype) -> the type-code arguments of an entry; code_shape(N, C, Ho, Wo) -> the shape of max pool's code tensor
+_Format = collections.namedtuple("_Format", "infix covered check ready empty grad_output codes code_shape")
+_NCHW = _Format("", "", lambda input, op: None, lambda t: t.contiguous().float(),
+                lambda like, shape=None: (torch.empty_like(like) if shape is None
+                                          else torch.empty(tuple(shape), dtype=torch.float32, device=like.device)),
+                lambda grad_output, shape, dtype, op: _grad_output(grad_output, shape, op),
+                lambda dtype: (), lambda N, C, Ho, Wo: (N, C, Ho, Wo))
+_NHWC = _Format("_nhwc", "C a multiple of 64, ", _resident_input, _resident,
+                lambda like, shape=None: _resident_empty(like.shape if shape is None else shape, like.dtype, like.device),
+                _resident_grad_output, lambda dtype: (_RESIDENT_DTYPES[dtype],), lambda N, C, Ho, Wo: (N, Ho, Wo, C))
+
+
 def _deform_geometry(x, off, w, stride, padding, dilation, deform_groups):
     (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
     N, Cin, H, W = x.shape
@@ -168,12 +242,9 @@ def conv_offset2d(input, offset, weight, stride=1, padding=0, dilation=1, deform
     if input is not None and input.dim() != 4:
         raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
     _lib.require_cuda(input, "input")
-    if torch.is_grad_enabled() and (input.requires_grad or offset.requires_grad):
-        return ConvOffset2dFunction.apply(input, offset, weight, stride, padding, dilation, deform_groups, compute)
-    x = input.contiguous().float()
-    off = offset.contiguous().float()
-    w = weight.detach().contiguous().float()
-    return _deform_forward(x, off, w, stride, padding, dilation, deform_groups, compute)
+    return _dispatch(ConvOffset2dFunction, (input, offset, weight, stride, padding, dilation, deform_groups, compute), (input, offset),
+                     lambda: _deform_forward(input.contiguous().float(), offset.contiguous().float(), weight.detach().contiguous().float(),
+                                             stride, padding, dilation, deform_groups, compute))
 
 
 _DEFORM_TS_COVERED = ("conv_offset2d_ts covers one deformable group, compute 'bf16' or 'fp16', Cin a multiple of 64, 1 <= Cout <= 256 and "
@@ -261,12 +332,9 @@ def conv_offset2d_ts(input, offset, weight, stride=1, padding=0, dilation=1, com
     order); the output and grad_offset are bitwise reproducible."""
     if input is not None and input.dim() != 4:
         raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-    if torch.is_grad_enabled() and (input.requires_grad or offset.requires_grad):
-        return ConvOffset2dTsFunction.apply(input, offset, weight, stride, padding, dilation, compute)
-    x = input.contiguous().float()
-    off = offset.contiguous().float()
-    w = weight.detach().contiguous().float()
-    return _deform_ts_forward(x, off, w, stride, padding, dilation, compute, False)[0]
+    return _dispatch(ConvOffset2dTsFunction, (input, offset, weight, stride, padding, dilation, compute), (input, offset),
+                     lambda: _deform_ts_forward(input.contiguous().float(), offset.contiguous().float(), weight.detach().contiguous().float(),
+                                                stride, padding, dilation, compute, False)[0])
 
 
 class ConvOffset2d(nn.Module):
@@ -287,8 +355,9 @@ class ConvOffset2d(nn.Module):
 
 # One trainable conv family of the C ABI (tdrn_hip.h sections i-c, i-f, i-g, i-h): `prefix`_workspace_bytes / _forward / _backward_input /
 # _backward_parameters.  geometry(x, w, *geo) -> (the ABI's dims, the output's shape); cout_axis: the weight axis that is Cout;
-# covered / dim_names: the error message of a geometry the library refuses.  `name` is the op's name in messages.
-_ConvFamily = collections.namedtuple("_ConvFamily", "name prefix geometry cout_axis covered dim_names")
+# covered / dim_names: the error message of a geometry the library refuses.  `name` is the op's name in messages.  fmt: the tensor format
+# of input, output and their gradients (weight and bias are fp32 in both).
+_ConvFamily = collections.namedtuple("_ConvFamily", "name prefix geometry cout_axis covered dim_names fmt", defaults=(_NCHW,))
 
 
 def _conv2d_family(stride):
@@ -333,6 +402,9 @@ _CONV2D = {prefix: _ConvFamily("conv2d", prefix, _conv2d_geometry, 0, _CONV2D_CO
 _CONV_TRANSPOSE2D = _ConvFamily("conv_transpose2d", "tdrn_conv_transpose2d", _conv_transpose2d_geometry, 1,
                                 "kernel 2 x 2, stride 2, padding 0, output_padding 0, dilation 1",
                                 "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, opadH, opadW, dilH, dilW")
+_CONV2D_NHWC = _ConvFamily("conv2d_nhwc", "tdrn_conv2d_nhwc", _conv2d_geometry, 0,
+                           "square k in {1, 3} at stride 1 with 0 <= pad <= dilation * (k - 1), Cin and Cout multiples of 64",
+                           "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW", _NHWC)
 
 
 def _conv2d_require_cuda(input, weight, bias):
@@ -359,69 +431,73 @@ def _conv_reset_parameters(weight, bias):
         nn.init.uniform_(bias, -bound, bound)
 
 
-def _conv_workspace(lib, fam, dims, dt, device):
-    return _workspace(getattr(lib, fam.prefix + "_workspace_bytes"), dims + (dt,), device,
+def _conv_workspace(lib, fam, dims, dt, extra, device):
+    return _workspace(getattr(lib, fam.prefix + "_workspace_bytes"), dims + (dt,) + extra, device,
                       "%s: geometry outside what libtdrn_hip covers (%s): %s = %r", fam.name, fam.covered, fam.dim_names, dims)
 
 
-def _conv_forward(fam, x, w, b, geo, compute):
+def _conv_type(fam, x, compute):
+    """the type code of a conv entry: that of a resident input, else the MFMA input type `compute` of an fp32 one"""
+    return (fam.fmt.codes(x.dtype) or (_lib.DTYPES[compute],))[0]
+
+
+def _conv_forward(fam, x, w, b, geo, compute, extra=()):
+    """`extra`: the entry arguments a family has behind the stream (conv2d_nhwc's flags)"""
     lib = _lib.lib()
     dims, out_shape = fam.geometry(x, w, *geo)
     if b is not None and tuple(b.shape) != (out_shape[1],):
         raise RuntimeError("%s: bias has shape %r, expected (%d,)" % (fam.name, tuple(b.shape), out_shape[1]))
-    dt = _lib.DTYPES[compute]
-    ws, nb = _conv_workspace(lib, fam, dims, dt, x.device)
-    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    dt = _conv_type(fam, x, compute)
+    ws, nb = _conv_workspace(lib, fam, dims, dt, extra, x.device)
+    out = fam.fmt.empty(x, out_shape)
     _lib.check(getattr(lib, fam.prefix + "_forward")(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
-                                                     _lib.current_stream(x.device)), fam.prefix + "_forward")
+                                                     _lib.current_stream(x.device), *extra), fam.prefix + "_forward")
     return out
 
 
-def _conv_function_forward(ctx, fam, input, weight, bias, geo, compute):
-    """the forward of both conv Functions, after their checks"""
-    x, w = input.contiguous().float(), weight.contiguous().float()
+def _conv_function_forward(ctx, fam, input, weight, bias, geo, compute, extra=()):
+    """the forward of every conv Function, after its checks"""
+    x, w = fam.fmt.ready(input), weight.contiguous().float()
     b = None if bias is None else bias.contiguous().float()
-    out = _conv_forward(fam, x, w, b, geo, compute)
-    ctx.conf = (fam, geo, compute, bias is not None)
+    out = _conv_forward(fam, x, w, b, geo, compute, extra)
+    ctx.conf = (fam, geo, compute, extra, bias is not None)
     ctx.save_for_backward(x, w)
     return out
 
 
 def _conv_function_backward(ctx, grad_output):
-    """the backward of both conv Functions -> (grad_input, grad_weight, grad_bias), each None where it is not needed"""
+    """the backward of every conv Function -> (grad_input, grad_weight, grad_bias), each None where it is not needed"""
     x, w = ctx.saved_tensors
-    fam, geo, compute, has_bias = ctx.conf
+    fam, geo, compute, extra, has_bias = ctx.conf
     dims, out_shape = fam.geometry(x, w, *geo)
-    go = _grad_output(grad_output, out_shape, fam.name)
+    go = fam.fmt.grad_output(grad_output, out_shape, x.dtype, fam.name)
     lib = _lib.lib()
     need_in, need_w = ctx.needs_input_grad[:2]
     need_b = has_bias and ctx.needs_input_grad[2]
     grad_input = grad_weight = grad_bias = None
     if need_in or need_w or need_b:
-        dt = _lib.DTYPES[compute]
-        ws, nb = _conv_workspace(lib, fam, dims, dt, x.device)
+        dt = _conv_type(fam, x, compute)
+        ws, nb = _conv_workspace(lib, fam, dims, dt, extra, x.device)
         stream = _lib.current_stream(x.device)
     if need_in:
-        grad_input = torch.empty_like(x)
+        grad_input = fam.fmt.empty(x)
         _lib.check(getattr(lib, fam.prefix + "_backward_input")(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws),
-                                                                nb, stream), fam.prefix + "_backward_input")
+                                                                nb, stream, *extra), fam.prefix + "_backward_input")
     if need_w or need_b:
         gw = torch.zeros_like(w)
         gb = torch.zeros(w.shape[fam.cout_axis], dtype=torch.float32, device=x.device) if need_b else None
         _lib.check(getattr(lib, fam.prefix + "_backward_parameters")(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
-                                                                     _lib.ptr(ws), nb, stream), fam.prefix + "_backward_parameters")
+                                                                     _lib.ptr(ws), nb, stream, *extra), fam.prefix + "_backward_parameters")
         grad_weight = gw if need_w else None
         grad_bias = gb
     return grad_input, grad_weight, grad_bias
 
 
-def _conv_dispatch(function, fam, input, weight, bias, geo, compute, *apply_args):
-    """through `function` when something requires grad and grad mode is on; else the forward alone, no grad_fn"""
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return function.apply(input, weight, bias, *apply_args)
-    x, w = input.contiguous().float(), weight.detach().contiguous().float()
-    b = None if bias is None else bias.detach().contiguous().float()
-    return _conv_forward(fam, x, w, b, geo, compute)
+def _conv_dispatch(function, fam, input, weight, bias, geo, compute, *apply_args, extra=()):
+    """_dispatch for a conv family: input, weight and bias count"""
+    return _dispatch(function, (input, weight, bias) + apply_args, (input, weight, bias),
+                     lambda: _conv_forward(fam, fam.fmt.ready(input.detach()), weight.detach().contiguous().float(),
+                                           None if bias is None else bias.detach().contiguous().float(), geo, compute, extra))
 
 
 class Conv2dFunction(torch.autograd.Function):
@@ -694,23 +770,66 @@ def _batch_norm_check(input, running_mean, running_var, weight, bias, training):
         raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(input.size()))
 
 
-def _batch_norm_workspace(lib, dims, device):
-    return _workspace(lib.tdrn_batch_norm_workspace_bytes, dims, device,
-                      "batch_norm: shape outside what libtdrn_hip covers (positive sizes, fewer than 2^31 elements): N, C, H, W = %r", dims)
+def _batch_norm_workspace(fmt, lib, dims, device):
+    return _workspace(getattr(lib, "tdrn_batch_norm%s_workspace_bytes" % fmt.infix), dims, device,
+                      "batch_norm%s: shape outside what libtdrn_hip covers (positive sizes, %sfewer than 2^31 elements): N, C, H, W = %r",
+                      fmt.infix, fmt.covered, dims)
 
 
-def _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu):
+def _batch_norm_forward(fmt, x, running_mean, running_var, w, b, training, momentum, eps, relu):
     lib = _lib.lib()
     dims = tuple(x.shape)
-    ws, nb = _batch_norm_workspace(lib, dims, x.device)
-    out = torch.empty_like(x)
+    ws, nb = _batch_norm_workspace(fmt, lib, dims, x.device)
+    out = fmt.empty(x)
     save_mean = torch.empty(dims[1], dtype=torch.float32, device=x.device)
     save_invstd = torch.empty_like(save_mean)
-    _lib.check(lib.tdrn_batch_norm_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                           _lib.ptr(out), _lib.ptr(save_mean), _lib.ptr(save_invstd), *dims, int(bool(training)),
-                                           float(momentum), float(eps), int(bool(relu)), _lib.ptr(ws), nb,
-                                           _lib.current_stream(x.device)), "tdrn_batch_norm_forward")
+    entry = "tdrn_batch_norm%s_forward" % fmt.infix
+    _lib.check(getattr(lib, entry)(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(out),
+                                   _lib.ptr(save_mean), _lib.ptr(save_invstd), *dims, int(bool(training)), float(momentum), float(eps),
+                                   int(bool(relu)), *fmt.codes(x.dtype), _lib.ptr(ws), nb, _lib.current_stream(x.device)), entry)
     return out, save_mean, save_invstd
+
+
+def _batch_norm_function_forward(ctx, fmt, input, running_mean, running_var, weight, bias, training, momentum, eps, relu):
+    """the forward of both batch norm Functions"""
+    fmt.check(input, "batch_norm" + fmt.infix)
+    _batch_norm_check(input, running_mean, running_var, weight, bias, training)
+    x, w, b = fmt.ready(input), weight.contiguous().float(), bias.contiguous().float()
+    out, save_mean, save_invstd = _batch_norm_forward(fmt, x, running_mean, running_var, w, b, training, momentum, eps, relu)
+    ctx.conf = (bool(training), bool(relu))
+    ctx.save_for_backward(x, w, b, save_mean, save_invstd)
+    return out
+
+
+def _batch_norm_function_backward(ctx, fmt, grad_output):
+    """the backward of both batch norm Functions"""
+    x, w, b, save_mean, save_invstd = ctx.saved_tensors
+    go = fmt.grad_output(grad_output, x.shape, x.dtype, "batch_norm" + fmt.infix)
+    training, relu = ctx.conf
+    need_in, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+    grad_input = gw = gb = None
+    if need_in or need_w or need_b:
+        lib = _lib.lib()
+        dims = tuple(x.shape)
+        ws, nb = _batch_norm_workspace(fmt, lib, dims, x.device)
+        if need_in:
+            grad_input = fmt.empty(x)
+        if need_w or need_b:
+            gw, gb = torch.zeros_like(w), torch.zeros_like(b)
+        entry = "tdrn_batch_norm%s_backward" % fmt.infix
+        _lib.check(getattr(lib, entry)(_lib.ptr(x), _lib.ptr(go), _lib.ptr(w), _lib.ptr(b), _lib.ptr(save_mean), _lib.ptr(save_invstd),
+                                       _lib.ptr(grad_input), _lib.ptr(gw), _lib.ptr(gb), *dims, int(training), int(relu), 1.0,
+                                       *fmt.codes(x.dtype), _lib.ptr(ws), nb, _lib.current_stream(x.device)), entry)
+    return grad_input, None, None, gw if need_w else None, gb if need_b else None, None, None, None, None
+
+
+def _batch_norm(fmt, function, input, running_mean, running_var, weight, bias, training, momentum, eps, relu):
+    """batch_norm and batch_norm_nhwc: the checks, then _dispatch; input, weight and bias count"""
+    fmt.check(input, "batch_norm" + fmt.infix)
+    _batch_norm_check(input, running_mean, running_var, weight, bias, training)
+    return _dispatch(function, (input, running_mean, running_var, weight, bias, training, momentum, eps, relu), (input, weight, bias),
+                     lambda: _batch_norm_forward(fmt, fmt.ready(input.detach()), running_mean, running_var, weight.detach().contiguous().float(),
+                                                 bias.detach().contiguous().float(), training, momentum, eps, relu)[0])
 
 
 class BatchNormFunction(torch.autograd.Function):
@@ -724,34 +843,12 @@ class BatchNormFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, running_mean, running_var, weight, bias, training=True, momentum=0.1, eps=1e-5, relu=False):
-        _batch_norm_check(input, running_mean, running_var, weight, bias, training)
-        x, w, b = input.contiguous().float(), weight.contiguous().float(), bias.contiguous().float()
-        out, save_mean, save_invstd = _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)
-        ctx.conf = (bool(training), bool(relu))
-        ctx.save_for_backward(x, w, b, save_mean, save_invstd)
-        return out
+        return _batch_norm_function_forward(ctx, _NCHW, input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        x, w, b, save_mean, save_invstd = ctx.saved_tensors
-        go = _grad_output(grad_output, x.shape, "batch_norm")
-        training, relu = ctx.conf
-        need_in, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-        grad_input = gw = gb = None
-        if need_in or need_w or need_b:
-            lib = _lib.lib()
-            dims = tuple(x.shape)
-            ws, nb = _batch_norm_workspace(lib, dims, x.device)
-            if need_in:
-                grad_input = torch.empty_like(x)
-            if need_w or need_b:
-                gw, gb = torch.zeros_like(w), torch.zeros_like(b)
-            _lib.check(lib.tdrn_batch_norm_backward(_lib.ptr(x), _lib.ptr(go), _lib.ptr(w), _lib.ptr(b), _lib.ptr(save_mean),
-                                                    _lib.ptr(save_invstd), _lib.ptr(grad_input), _lib.ptr(gw), _lib.ptr(gb), *dims,
-                                                    int(training), int(relu), 1.0, _lib.ptr(ws), nb, _lib.current_stream(x.device)),
-                       "tdrn_batch_norm_backward")
-        return grad_input, None, None, gw if need_w else None, gb if need_b else None, None, None, None, None
+        return _batch_norm_function_backward(ctx, _NCHW, grad_output)
 
 
 def batch_norm(input, running_mean, running_var, weight, bias, training, momentum=0.1, eps=1e-5, relu=False):
@@ -759,11 +856,31 @@ def batch_norm(input, running_mean, running_var, weight, bias, training, momentu
     weight and bias.  In training the running buffers (float32, contiguous; or both None) are updated in place with `momentum`,
     nn.BatchNorm2d's semantics.  With grad mode off, or when nothing requires grad, only the forward runs and the output has no
     grad_fn."""
-    _batch_norm_check(input, running_mean, running_var, weight, bias, training)
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or bias.requires_grad):
-        return BatchNormFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
-    x, w, b = input.detach().contiguous().float(), weight.detach().contiguous().float(), bias.detach().contiguous().float()
-    return _batch_norm_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)[0]
+    return _batch_norm(_NCHW, BatchNormFunction, input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+
+
+class BatchNormNhwcFunction(torch.autograd.Function):
+    """BatchNormFunction on resident tensors: tdrn_batch_norm_nhwc_forward / _backward.  Saves the 16-bit input and the fp32
+    statistics; the backward recomputes the ReLU mask from the input.
+
+        y = BatchNormNhwcFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+    """
+
+    @staticmethod
+    def forward(ctx, input, running_mean, running_var, weight, bias, training=True, momentum=0.1, eps=1e-5, relu=False):
+        return _batch_norm_function_forward(ctx, _NHWC, input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _batch_norm_function_backward(ctx, _NHWC, grad_output)
+
+
+def batch_norm_nhwc(input, running_mean, running_var, weight, bias, training, momentum=0.1, eps=1e-5, relu=False):
+    """batch_norm above from a resident tensor to a resident tensor: the same semantics, fp32 parameters, buffers and statistics,
+    the output rounded once to the input's dtype.  With grad mode off, or when nothing requires grad, only the forward runs and the
+    output has no grad_fn."""
+    return _batch_norm(_NHWC, BatchNormNhwcFunction, input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
 
 
 class BatchNorm2d(nn.Module):
@@ -819,11 +936,13 @@ def _square(v, name):
     return int(a)
 
 
-def _max_pool_check(input, kernel_size, stride, padding, ceil_mode):
-    """-> (kernel, stride, pad, ceil, Ho, Wo) of a call the library covers"""
+def _max_pool_check(fmt, input, kernel_size, stride, padding, ceil_mode):
+    """-> (kernel, stride, pad, ceil, Ho, Wo) + the format's type codes, of a call the library covers"""
+    op = "max_pool2d" + fmt.infix
+    fmt.check(input, op)
     if input.dim() != 4:
         raise ValueError("expected 4D input (got {}D input)".format(input.dim()))
-    if input.dtype != torch.float32:
+    if fmt is _NCHW and input.dtype != torch.float32:          # the fp32 op casts nothing; a resident input's type is settled above
         raise ValueError("max_pool2d: input must be float32 (got %s)" % input.dtype)
     _lib.require_cuda(input, "input")
     k = _square(kernel_size, "kernel_size")
@@ -831,21 +950,54 @@ def _max_pool_check(input, kernel_size, stride, padding, ceil_mode):
     lib = _lib.lib()
     Ho, Wo = (lib.tdrn_max_pool_output_size(int(n), *geo) for n in input.shape[2:])
     if geo[:3] not in ((2, 2, 0), (3, 1, 1)):
-        raise NotImplementedError("max_pool2d: kernel_size %d, stride %d, padding %d is not covered; libtdrn_hip covers %s"
-                                  % (geo[0], geo[1], geo[2], _POOL_GEOMETRIES))
+        raise NotImplementedError("%s: kernel_size %d, stride %d, padding %d is not covered; libtdrn_hip covers %s"
+                                  % (op, geo[0], geo[1], geo[2], _POOL_GEOMETRIES))
     if Ho == 0 or Wo == 0 or input.numel() == 0:
-        raise RuntimeError("max_pool2d: input %r gives an empty output" % (tuple(input.shape),))
-    return geo + (Ho, Wo)
+        raise RuntimeError("%s: input %r gives an empty output" % (op, tuple(input.shape)))
+    return geo + (Ho, Wo) + fmt.codes(input.dtype)
 
 
-def _max_pool_forward(x, conf, with_code):
-    k, s, p, ceil, Ho, Wo = conf
+def _max_pool_forward(fmt, x, conf, with_code):
+    k, s, p, ceil, Ho, Wo, *codes = conf
     N, Ch, H, W = x.shape
-    out = torch.empty((N, Ch, Ho, Wo), dtype=torch.float32, device=x.device)
-    code = torch.empty((N, Ch, Ho, Wo), dtype=torch.uint8, device=x.device) if with_code else None
-    _lib.check(_lib.lib().tdrn_max_pool_forward(_lib.ptr(x), _lib.ptr(out), _lib.ptr(code), N, Ch, H, W, k, s, p, ceil,
-                                                _lib.current_stream(x.device)), "tdrn_max_pool_forward")
+    out = fmt.empty(x, (N, Ch, Ho, Wo))
+    code = torch.empty(fmt.code_shape(N, Ch, Ho, Wo), dtype=torch.uint8, device=x.device) if with_code else None
+    entry = "tdrn_max_pool%s_forward" % fmt.infix
+    _lib.check(getattr(_lib.lib(), entry)(_lib.ptr(x), _lib.ptr(out), _lib.ptr(code), N, Ch, H, W, k, s, p, ceil, *codes,
+                                          _lib.current_stream(x.device)), entry)
     return out, code
+
+
+def _max_pool_function_forward(ctx, fmt, input, kernel_size, stride, padding, ceil_mode):
+    """the forward of both max pool Functions"""
+    conf = _max_pool_check(fmt, input, kernel_size, stride, padding, ceil_mode)
+    x = fmt.ready(input)            # fp32: checked to be float32, so contiguous() and no cast
+    out, code = _max_pool_forward(fmt, x, conf, True)
+    ctx.conf, ctx.in_shape, ctx.dtype = conf, tuple(x.shape), x.dtype
+    ctx.save_for_backward(code)
+    return out
+
+
+def _max_pool_function_backward(ctx, fmt, grad_output):
+    """the backward of both max pool Functions"""
+    code, = ctx.saved_tensors
+    k, s, p, ceil, Ho, Wo, *codes = ctx.conf
+    N, Ch, H, W = ctx.in_shape
+    go = fmt.grad_output(grad_output, (N, Ch, Ho, Wo), ctx.dtype, "max_pool2d" + fmt.infix)
+    grad_input = None
+    if ctx.needs_input_grad[0]:
+        grad_input = fmt.empty(go, ctx.in_shape)
+        entry = "tdrn_max_pool%s_backward" % fmt.infix
+        _lib.check(getattr(_lib.lib(), entry)(_lib.ptr(go), _lib.ptr(code), _lib.ptr(grad_input), N, Ch, H, W, k, s, p, ceil, *codes,
+                                              _lib.current_stream(go.device)), entry)
+    return grad_input, None, None, None, None
+
+
+def _max_pool2d(fmt, function, input, kernel_size, stride, padding, ceil_mode):
+    """max_pool2d and max_pool2d_nhwc: the check, then _dispatch; the input alone counts"""
+    conf = _max_pool_check(fmt, input, kernel_size, stride, padding, ceil_mode)
+    return _dispatch(function, (input, kernel_size, stride, padding, ceil_mode), (input,),
+                     lambda: _max_pool_forward(fmt, fmt.ready(input.detach()), conf, False)[0])
 
 
 class MaxPool2dFunction(torch.autograd.Function):
@@ -857,35 +1009,42 @@ class MaxPool2dFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, kernel_size, stride=None, padding=0, ceil_mode=False):
-        conf = _max_pool_check(input, kernel_size, stride, padding, ceil_mode)
-        x = input.contiguous()
-        out, code = _max_pool_forward(x, conf, True)
-        ctx.conf, ctx.in_shape = conf, tuple(x.shape)
-        ctx.save_for_backward(code)
-        return out
+        return _max_pool_function_forward(ctx, _NCHW, input, kernel_size, stride, padding, ceil_mode)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        code, = ctx.saved_tensors
-        go = _grad_output(grad_output, code.shape, "max_pool2d")
-        grad_input = None
-        if ctx.needs_input_grad[0]:
-            k, s, p, ceil, _, _ = ctx.conf
-            grad_input = torch.empty(ctx.in_shape, dtype=torch.float32, device=go.device)
-            _lib.check(_lib.lib().tdrn_max_pool_backward(_lib.ptr(go), _lib.ptr(code), _lib.ptr(grad_input), *ctx.in_shape, k, s, p, ceil,
-                                                         _lib.current_stream(go.device)), "tdrn_max_pool_backward")
-        return grad_input, None, None, None, None
+        return _max_pool_function_backward(ctx, _NCHW, grad_output)
 
 
 def max_pool2d(input, kernel_size, stride=None, padding=0, ceil_mode=False):
     """F.max_pool2d for NCHW fp32 CUDA tensors on libtdrn_hip, differentiable in input, for the geometries of vgg(): 2 / 2 / 0 with
     either ceil_mode, and 3 / 1 / 1.  With grad mode off, or an input that does not require grad, only the forward runs, no code
     tensor is made and the output has no grad_fn."""
-    conf = _max_pool_check(input, kernel_size, stride, padding, ceil_mode)
-    if torch.is_grad_enabled() and input.requires_grad:
-        return MaxPool2dFunction.apply(input, kernel_size, stride, padding, ceil_mode)
-    return _max_pool_forward(input.detach().contiguous(), conf, False)[0]
+    return _max_pool2d(_NCHW, MaxPool2dFunction, input, kernel_size, stride, padding, ceil_mode)
+
+
+class MaxPool2dNhwcFunction(torch.autograd.Function):
+    """MaxPool2dFunction on resident tensors: tdrn_max_pool_nhwc_forward / _backward.  Saves one uint8 code per output element,
+    (N, Ho, Wo, C).
+
+        y = MaxPool2dNhwcFunction.apply(input, kernel_size, stride, padding, ceil_mode)
+    """
+
+    @staticmethod
+    def forward(ctx, input, kernel_size, stride=None, padding=0, ceil_mode=False):
+        return _max_pool_function_forward(ctx, _NHWC, input, kernel_size, stride, padding, ceil_mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        return _max_pool_function_backward(ctx, _NHWC, grad_output)
+
+
+def max_pool2d_nhwc(input, kernel_size, stride=None, padding=0, ceil_mode=False):
+    """max_pool2d above from a resident tensor to a resident tensor: the same three geometries, the same selection.  With grad mode
+    off, or an input that does not require grad, only the forward runs, no code tensor is made and the output has no grad_fn."""
+    return _max_pool2d(_NHWC, MaxPool2dNhwcFunction, input, kernel_size, stride, padding, ceil_mode)
 
 
 class MaxPool2d(nn.Module):
@@ -972,9 +1131,8 @@ def l2norm(input, weight, eps=1e-10):
     weight.  With grad mode off, or when nothing requires grad, only the forward runs, no norm tensor is made and the output has
     no grad_fn."""
     _l2norm_check(input, weight, eps)
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad):
-        return L2NormFunction.apply(input, weight, eps)
-    return _l2norm_forward(input.detach().contiguous(), weight.detach().contiguous(), eps, False)[0]
+    return _dispatch(L2NormFunction, (input, weight, eps), (input, weight),
+                     lambda: _l2norm_forward(input.detach().contiguous(), weight.detach().contiguous(), eps, False)[0])
 
 
 class L2Norm(nn.Module):
@@ -990,54 +1148,7 @@ class L2Norm(nn.Module):
         return l2norm(x, self.weight, self.eps)
 
 
-# ---- resident tensors (tdrn_hip.h section i-k): activations and their gradients as 16-bit NHWC between layers ----------------------------
-_RESIDENT_DTYPES = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
-_RESIDENT_NAMES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "f16": torch.float16,
-                   "float16": torch.float16, "half": torch.float16}
-RESIDENT_CHANNELS = 64          # kChanPad: a resident tensor holds whole 64-channel blocks
-
-
-def _resident_dtype(dtype):
-    dtype = _RESIDENT_NAMES.get(dtype, dtype)
-    if dtype not in _RESIDENT_DTYPES:
-        raise ValueError("a resident tensor is torch.bfloat16 or torch.float16, got %r" % (dtype,))
-    return dtype
-
-
-def _resident(t, dtype=None):
-    """`t` as a resident tensor: of `dtype` (default: its own), contiguous in channels_last, its data on a 16-byte boundary (a
-    misaligned storage is cloned)"""
-    if dtype is not None and t.dtype != dtype:
-        t = t.to(dtype)
-    t = t.contiguous(memory_format=torch.channels_last)
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.channels_last)
-
-
-def _resident_input(input, op):
-    """the checks every resident op starts with -> the library's type code"""
-    if input.dim() != 4:
-        raise ValueError("Expected 4D tensor as input, got {}D tensor instead.".format(input.dim()))
-    _lib.require_cuda(input, "input")
-    if input.dtype not in _RESIDENT_DTYPES:
-        raise ValueError("%s: input must be torch.bfloat16 or torch.float16 (got %s); to_nhwc makes one" % (op, input.dtype))
-    if input.shape[1] % RESIDENT_CHANNELS:
-        raise RuntimeError("%s: %d channels are outside what libtdrn_hip covers (a multiple of %d)" % (op, input.shape[1], RESIDENT_CHANNELS))
-    return _RESIDENT_DTYPES[input.dtype]
-
-
-def _resident_empty(shape, dtype, device):
-    return torch.empty(tuple(shape), dtype=dtype, device=device, memory_format=torch.channels_last)
-
-
-def _resident_grad_output(grad_output, shape, dtype, op):
-    """what every resident backward does first: a CUDA grad_output of the output's shape, made resident whatever it arrives as"""
-    if not grad_output.is_cuda:
-        raise NotImplementedError("%s backward: grad_output must be a CUDA tensor" % op)
-    if tuple(grad_output.shape) != tuple(shape):
-        raise RuntimeError("grad_output has shape %r, expected %r" % (tuple(grad_output.shape), tuple(shape)))
-    return _resident(grad_output, dtype)
-
-
+# ---- the resident ops that have no fp32 NCHW twin: into the format and out of it, and the conv family on it -------------------------------
 def _to_nhwc_forward(x, dtype):
     out = _resident_empty(x.shape, dtype, x.device)
     _lib.check(_lib.lib().tdrn_nhwc16_from_nchw(_lib.ptr(x), _lib.ptr(out), *x.shape, _RESIDENT_DTYPES[dtype],
@@ -1090,39 +1201,13 @@ def to_nhwc(x, dtype):
     _lib.require_cuda(x, "input")
     if x.shape[1] % RESIDENT_CHANNELS:
         raise RuntimeError("to_nhwc: %d channels are outside what libtdrn_hip covers (a multiple of %d)" % (x.shape[1], RESIDENT_CHANNELS))
-    if torch.is_grad_enabled() and x.requires_grad:
-        return ToNhwcFunction.apply(x, dtype)
-    return _to_nhwc_forward(x.detach().contiguous().float(), dtype)
+    return _dispatch(ToNhwcFunction, (x, dtype), (x,), lambda: _to_nhwc_forward(x.detach().contiguous().float(), dtype))
 
 
 def from_nhwc(x):
     """A resident tensor -> the same values as fp32 NCHW (exact); differentiable (the gradient is rounded once to x's type)."""
     _resident_input(x, "from_nhwc")
-    if torch.is_grad_enabled() and x.requires_grad:
-        return FromNhwcFunction.apply(x)
-    return _from_nhwc_forward(_resident(x.detach()))
-
-
-_CONV2D_NHWC_COVERED = "square k in {1, 3} at stride 1 with 0 <= pad <= dilation * (k - 1), Cin and Cout multiples of 64"
-_CONV2D_NHWC_DIMS = "N, Cin, H, W, Cout, kH, kW, dH, dW, padH, padW, dilH, dilW"
-
-
-def _conv2d_nhwc_workspace(lib, dims, dt, flags, device):
-    return _workspace(lib.tdrn_conv2d_nhwc_workspace_bytes, dims + (dt, flags), device,
-                      "conv2d_nhwc: geometry outside what libtdrn_hip covers (%s): %s = %r", _CONV2D_NHWC_COVERED, _CONV2D_NHWC_DIMS, dims)
-
-
-def _conv2d_nhwc_forward(x, w, b, padding, dilation, flags):
-    lib = _lib.lib()
-    dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
-    if b is not None and tuple(b.shape) != (out_shape[1],):
-        raise RuntimeError("conv2d_nhwc: bias has shape %r, expected (%d,)" % (tuple(b.shape), out_shape[1]))
-    dt = _RESIDENT_DTYPES[x.dtype]
-    ws, nb = _conv2d_nhwc_workspace(lib, dims, dt, flags, x.device)
-    out = _resident_empty(out_shape, x.dtype, x.device)
-    _lib.check(lib.tdrn_conv2d_nhwc_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), *dims, dt, _lib.ptr(ws), nb,
-                                            _lib.current_stream(x.device), flags), "tdrn_conv2d_nhwc_forward")
-    return out
+    return _dispatch(FromNhwcFunction, (x,), (x,), lambda: _from_nhwc_forward(_resident(x.detach())))
 
 
 class Conv2dNhwcFunction(torch.autograd.Function):
@@ -1136,39 +1221,12 @@ class Conv2dNhwcFunction(torch.autograd.Function):
     def forward(ctx, input, weight, bias=None, padding=0, dilation=1, flags=0):
         _resident_input(input, "conv2d_nhwc")
         _conv2d_require_cuda(input, weight, bias)
-        x, w = _resident(input), weight.contiguous().float()
-        b = None if bias is None else bias.contiguous().float()
-        out = _conv2d_nhwc_forward(x, w, b, padding, dilation, flags)
-        ctx.conf = (padding, dilation, flags, bias is not None)
-        ctx.save_for_backward(x, w)
-        return out
+        return _conv_function_forward(ctx, _CONV2D_NHWC, input, weight, bias, (padding, dilation), None, (flags,))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        x, w = ctx.saved_tensors
-        padding, dilation, flags, has_bias = ctx.conf
-        dims, out_shape = _conv2d_geometry(x, w, padding, dilation)
-        go = _resident_grad_output(grad_output, out_shape, x.dtype, "conv2d_nhwc")
-        need_in, need_w = ctx.needs_input_grad[:2]
-        need_b = has_bias and ctx.needs_input_grad[2]
-        grad_input = grad_weight = grad_bias = None
-        if need_in or need_w or need_b:
-            lib, dt = _lib.lib(), _RESIDENT_DTYPES[x.dtype]
-            ws, nb = _conv2d_nhwc_workspace(lib, dims, dt, flags, x.device)
-            stream = _lib.current_stream(x.device)
-        if need_in:
-            grad_input = _resident_empty(x.shape, x.dtype, x.device)
-            _lib.check(lib.tdrn_conv2d_nhwc_backward_input(_lib.ptr(go), _lib.ptr(w), _lib.ptr(grad_input), *dims, dt, _lib.ptr(ws), nb,
-                                                           stream, flags), "tdrn_conv2d_nhwc_backward_input")
-        if need_w or need_b:
-            gw = torch.zeros_like(w)
-            gb = torch.zeros(w.shape[0], dtype=torch.float32, device=x.device) if need_b else None
-            _lib.check(lib.tdrn_conv2d_nhwc_backward_parameters(_lib.ptr(x), _lib.ptr(go), _lib.ptr(gw), _lib.ptr(gb), *dims, 1.0, dt,
-                                                                _lib.ptr(ws), nb, stream, flags), "tdrn_conv2d_nhwc_backward_parameters")
-            grad_weight = gw if need_w else None
-            grad_bias = gb
-        return grad_input, grad_weight, grad_bias, None, None, None
+        return _conv_function_backward(ctx, grad_output) + (None, None, None)
 
 
 def conv2d_nhwc(input, weight, bias=None, padding=0, dilation=1, flags=0):
@@ -1179,144 +1237,5 @@ def conv2d_nhwc(input, weight, bias=None, padding=0, dilation=1, flags=0):
     grad mode off, or when nothing requires grad, only the forward runs and the output has no grad_fn."""
     _resident_input(input, "conv2d_nhwc")
     _conv2d_require_cuda(input, weight, bias)
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return Conv2dNhwcFunction.apply(input, weight, bias, padding, dilation, flags)
-    b = None if bias is None else bias.detach().contiguous().float()
-    return _conv2d_nhwc_forward(_resident(input.detach()), weight.detach().contiguous().float(), b, padding, dilation, flags)
-
-
-def _batch_norm_nhwc_workspace(lib, dims, device):
-    return _workspace(lib.tdrn_batch_norm_nhwc_workspace_bytes, dims, device,
-                      "batch_norm_nhwc: shape outside what libtdrn_hip covers (positive sizes, C a multiple of 64, fewer than 2^31 "
-                      "elements): N, C, H, W = %r", dims)
-
-
-def _batch_norm_nhwc_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu):
-    lib = _lib.lib()
-    dims = tuple(x.shape)
-    ws, nb = _batch_norm_nhwc_workspace(lib, dims, x.device)
-    out = _resident_empty(dims, x.dtype, x.device)
-    save_mean = torch.empty(dims[1], dtype=torch.float32, device=x.device)
-    save_invstd = torch.empty_like(save_mean)
-    _lib.check(lib.tdrn_batch_norm_nhwc_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                                _lib.ptr(out), _lib.ptr(save_mean), _lib.ptr(save_invstd), *dims, int(bool(training)),
-                                                float(momentum), float(eps), int(bool(relu)), _RESIDENT_DTYPES[x.dtype], _lib.ptr(ws), nb,
-                                                _lib.current_stream(x.device)), "tdrn_batch_norm_nhwc_forward")
-    return out, save_mean, save_invstd
-
-
-class BatchNormNhwcFunction(torch.autograd.Function):
-    """BatchNormFunction on resident tensors: tdrn_batch_norm_nhwc_forward / _backward.  Saves the 16-bit input and the fp32
-    statistics; the backward recomputes the ReLU mask from the input.
-
-        y = BatchNormNhwcFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
-    """
-
-    @staticmethod
-    def forward(ctx, input, running_mean, running_var, weight, bias, training=True, momentum=0.1, eps=1e-5, relu=False):
-        _resident_input(input, "batch_norm_nhwc")
-        _batch_norm_check(input, running_mean, running_var, weight, bias, training)
-        x, w, b = _resident(input), weight.contiguous().float(), bias.contiguous().float()
-        out, save_mean, save_invstd = _batch_norm_nhwc_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)
-        ctx.conf = (bool(training), bool(relu))
-        ctx.save_for_backward(x, w, b, save_mean, save_invstd)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        x, w, b, save_mean, save_invstd = ctx.saved_tensors
-        go = _resident_grad_output(grad_output, x.shape, x.dtype, "batch_norm_nhwc")
-        training, relu = ctx.conf
-        need_in, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-        grad_input = gw = gb = None
-        if need_in or need_w or need_b:
-            lib = _lib.lib()
-            dims = tuple(x.shape)
-            ws, nb = _batch_norm_nhwc_workspace(lib, dims, x.device)
-            if need_in:
-                grad_input = _resident_empty(dims, x.dtype, x.device)
-            if need_w or need_b:
-                gw, gb = torch.zeros_like(w), torch.zeros_like(b)
-            _lib.check(lib.tdrn_batch_norm_nhwc_backward(_lib.ptr(x), _lib.ptr(go), _lib.ptr(w), _lib.ptr(b), _lib.ptr(save_mean),
-                                                         _lib.ptr(save_invstd), _lib.ptr(grad_input), _lib.ptr(gw), _lib.ptr(gb), *dims,
-                                                         int(training), int(relu), 1.0, _RESIDENT_DTYPES[x.dtype], _lib.ptr(ws), nb,
-                                                         _lib.current_stream(x.device)), "tdrn_batch_norm_nhwc_backward")
-        return grad_input, None, None, gw if need_w else None, gb if need_b else None, None, None, None, None
-
-
-def batch_norm_nhwc(input, running_mean, running_var, weight, bias, training, momentum=0.1, eps=1e-5, relu=False):
-    """batch_norm above from a resident tensor to a resident tensor: the same semantics, fp32 parameters, buffers and statistics,
-    the output rounded once to the input's dtype.  With grad mode off, or when nothing requires grad, only the forward runs and the
-    output has no grad_fn."""
-    _resident_input(input, "batch_norm_nhwc")
-    _batch_norm_check(input, running_mean, running_var, weight, bias, training)
-    if torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or bias.requires_grad):
-        return BatchNormNhwcFunction.apply(input, running_mean, running_var, weight, bias, training, momentum, eps, relu)
-    x, w, b = _resident(input.detach()), weight.detach().contiguous().float(), bias.detach().contiguous().float()
-    return _batch_norm_nhwc_forward(x, running_mean, running_var, w, b, training, momentum, eps, relu)[0]
-
-
-def _max_pool_nhwc_check(input, kernel_size, stride, padding, ceil_mode):
-    """-> (kernel, stride, pad, ceil, Ho, Wo, the library's type code) of a call the library covers"""
-    dt = _resident_input(input, "max_pool2d_nhwc")
-    k = _square(kernel_size, "kernel_size")
-    geo = (k, k if stride is None else _square(stride, "stride"), _square(padding, "padding"), int(bool(ceil_mode)))
-    lib = _lib.lib()
-    Ho, Wo = (lib.tdrn_max_pool_output_size(int(n), *geo) for n in input.shape[2:])
-    if geo[:3] not in ((2, 2, 0), (3, 1, 1)):
-        raise NotImplementedError("max_pool2d_nhwc: kernel_size %d, stride %d, padding %d is not covered; libtdrn_hip covers %s"
-                                  % (geo[0], geo[1], geo[2], _POOL_GEOMETRIES))
-    if Ho == 0 or Wo == 0 or input.numel() == 0:
-        raise RuntimeError("max_pool2d_nhwc: input %r gives an empty output" % (tuple(input.shape),))
-    return geo + (Ho, Wo, dt)
-
-
-def _max_pool_nhwc_forward(x, conf, with_code):
-    k, s, p, ceil, Ho, Wo, dt = conf
-    N, Ch, H, W = x.shape
-    out = _resident_empty((N, Ch, Ho, Wo), x.dtype, x.device)
-    code = torch.empty((N, Ho, Wo, Ch), dtype=torch.uint8, device=x.device) if with_code else None
-    _lib.check(_lib.lib().tdrn_max_pool_nhwc_forward(_lib.ptr(x), _lib.ptr(out), _lib.ptr(code), N, Ch, H, W, k, s, p, ceil, dt,
-                                                     _lib.current_stream(x.device)), "tdrn_max_pool_nhwc_forward")
-    return out, code
-
-
-class MaxPool2dNhwcFunction(torch.autograd.Function):
-    """MaxPool2dFunction on resident tensors: tdrn_max_pool_nhwc_forward / _backward.  Saves one uint8 code per output element,
-    (N, Ho, Wo, C).
-
-        y = MaxPool2dNhwcFunction.apply(input, kernel_size, stride, padding, ceil_mode)
-    """
-
-    @staticmethod
-    def forward(ctx, input, kernel_size, stride=None, padding=0, ceil_mode=False):
-        conf = _max_pool_nhwc_check(input, kernel_size, stride, padding, ceil_mode)
-        x = _resident(input)
-        out, code = _max_pool_nhwc_forward(x, conf, True)
-        ctx.conf, ctx.in_shape, ctx.dtype = conf, tuple(x.shape), x.dtype
-        ctx.save_for_backward(code)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        code, = ctx.saved_tensors
-        k, s, p, ceil, Ho, Wo, dt = ctx.conf
-        N, Ch, H, W = ctx.in_shape
-        go = _resident_grad_output(grad_output, (N, Ch, Ho, Wo), ctx.dtype, "max_pool2d_nhwc")
-        grad_input = None
-        if ctx.needs_input_grad[0]:
-            grad_input = _resident_empty(ctx.in_shape, ctx.dtype, go.device)
-            _lib.check(_lib.lib().tdrn_max_pool_nhwc_backward(_lib.ptr(go), _lib.ptr(code), _lib.ptr(grad_input), N, Ch, H, W, k, s, p, ceil,
-                                                              dt, _lib.current_stream(go.device)), "tdrn_max_pool_nhwc_backward")
-        return grad_input, None, None, None, None
-
-
-def max_pool2d_nhwc(input, kernel_size, stride=None, padding=0, ceil_mode=False):
-    """max_pool2d above from a resident tensor to a resident tensor: the same three geometries, the same selection.  With grad mode
-    off, or an input that does not require grad, only the forward runs, no code tensor is made and the output has no grad_fn."""
-    conf = _max_pool_nhwc_check(input, kernel_size, stride, padding, ceil_mode)
-    if torch.is_grad_enabled() and input.requires_grad:
-        return MaxPool2dNhwcFunction.apply(input, kernel_size, stride, padding, ceil_mode)
-    return _max_pool_nhwc_forward(_resident(input.detach()), conf, False)[0]
+    return _conv_dispatch(Conv2dNhwcFunction, _CONV2D_NHWC, input, weight, bias, (padding, dilation), None, padding, dilation, flags,
+                          extra=(flags,))
