@@ -353,14 +353,9 @@ int launch_batch_norm_backward(const float *input, const float *grad_output, con
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cblocks), dim3(kT), 0, s, rec, sums, grad_weight, grad_bias, g, scale);
     }
     if (grad_input) {
-#define TDRN_BN_BWD_APPLY(R, T)                                                                                                      \
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<R, T>), dim3(groups), dim3(kT), 0, s, input, grad_output, weight, bias, save_mean, save_invstd, \
-                       sums, grad_input, g)
-        if (relu && training) TDRN_BN_BWD_APPLY(true, true);
-        else if (relu) TDRN_BN_BWD_APPLY(true, false);
-        else if (training) TDRN_BN_BWD_APPLY(false, true);
-        else TDRN_BN_BWD_APPLY(false, false);
-#undef TDRN_BN_BWD_APPLY
+        auto k = relu ? (training ? bn_bwd_apply_kernel<true, true> : bn_bwd_apply_kernel<true, false>)
+                      : (training ? bn_bwd_apply_kernel<false, true> : bn_bwd_apply_kernel<false, false>);
+        hipLaunchKernelGGL(k, dim3(groups), dim3(kT), 0, s, input, grad_output, weight, bias, save_mean, save_invstd, sums, grad_input, g);
     }
     return hip_status(hipGetLastError());
 }

@@ -289,24 +289,22 @@ int launch_batch_norm_nhwc_forward(const void *input, const float *weight, const
                                    void *output, float *save_mean, float *save_invstd, int N, int C, int HW, int training, float momentum,
                                    float eps, int relu, int dtype, void *ws, hipStream_t s)
 {
-    if (C % kCB || (dtype != TDRN_BF16 && dtype != TDRN_F16)) return TDRN_E_UNSUPPORTED;
+    if (C % kCB) return TDRN_E_UNSUPPORTED;
     const BnNhwcGeom g = bn_nhwc_geom(N, C, HW);
     float *rec = (float *)ws;
     const dim3 grid(g.C / kCB * g.S), block(kT);
     const char *x = (const char *)input;
-    char *y = (char *)output;
-    if (training) {
-        if (dtype == TDRN_BF16) hipLaunchKernelGGL(bn_nhwc_stats_kernel<bf16_t>, grid, block, 0, s, x, rec, g);
-        else hipLaunchKernelGGL(bn_nhwc_stats_kernel<f16_t>, grid, block, 0, s, x, rec, g);
-        TDRN_HIP_TRY(hipGetLastError());
-    }
-    TDRN_TRY(launch_bn_stats_finalize(rec, running_mean, running_var, save_mean, save_invstd, C, g.M, (int)g.S, training, momentum, eps, s));
-#define TDRN_BN_APPLY(DT, R) \
-    hipLaunchKernelGGL((bn_nhwc_apply_kernel<DT, R>), grid, block, 0, s, x, weight, bias, save_mean, save_invstd, y, g)
-    if (dtype == TDRN_BF16) { if (relu) TDRN_BN_APPLY(bf16_t, true); else TDRN_BN_APPLY(bf16_t, false); }
-    else { if (relu) TDRN_BN_APPLY(f16_t, true); else TDRN_BN_APPLY(f16_t, false); }
-#undef TDRN_BN_APPLY
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        if (training) {
+            hipLaunchKernelGGL(bn_nhwc_stats_kernel<DT>, grid, block, 0, s, x, rec, g);
+            TDRN_HIP_TRY(hipGetLastError());
+        }
+        TDRN_TRY(launch_bn_stats_finalize(rec, running_mean, running_var, save_mean, save_invstd, C, g.M, (int)g.S, training, momentum, eps, s));
+        hipLaunchKernelGGL((relu ? bn_nhwc_apply_kernel<DT, true> : bn_nhwc_apply_kernel<DT, false>), grid, block, 0, s, x, weight, bias,
+                           save_mean, save_invstd, (char *)output, g);
+        return hip_status(hipGetLastError());
+    });
 }
 
 namespace {
@@ -320,21 +318,15 @@ int bn_nhwc_backward_dt(const BnNhwcGeom &g, const char *x, const char *dy, cons
     const dim3 grid(g.C / kCB * g.S), block(kT);
     // the sums serve the parameter gradients and, with batch statistics, the input gradient
     if (grad_weight || (dx && training)) {
-        if (relu)
-            hipLaunchKernelGGL((bn_nhwc_bwd_reduce_kernel<DT, true>), grid, block, 0, s, x, dy, weight, bias, save_mean, save_invstd, rec, g);
-        else
-            hipLaunchKernelGGL((bn_nhwc_bwd_reduce_kernel<DT, false>), grid, block, 0, s, x, dy, weight, bias, save_mean, save_invstd, rec, g);
+        hipLaunchKernelGGL((relu ? bn_nhwc_bwd_reduce_kernel<DT, true> : bn_nhwc_bwd_reduce_kernel<DT, false>), grid, block, 0, s, x, dy, weight,
+                           bias, save_mean, save_invstd, rec, g);
         TDRN_HIP_TRY(hipGetLastError());
         TDRN_TRY(launch_bn_bwd_finalize(rec, sums, grad_weight, grad_bias, (int)g.C, g.M, (int)g.S, scale, s));
     }
     if (dx) {
-#define TDRN_BN_BWD_APPLY(R, T) \
-    hipLaunchKernelGGL((bn_nhwc_bwd_apply_kernel<DT, R, T>), grid, block, 0, s, x, dy, weight, bias, save_mean, save_invstd, sums, dx, g)
-        if (relu && training) TDRN_BN_BWD_APPLY(true, true);
-        else if (relu) TDRN_BN_BWD_APPLY(true, false);
-        else if (training) TDRN_BN_BWD_APPLY(false, true);
-        else TDRN_BN_BWD_APPLY(false, false);
-#undef TDRN_BN_BWD_APPLY
+        auto k = relu ? (training ? bn_nhwc_bwd_apply_kernel<DT, true, true> : bn_nhwc_bwd_apply_kernel<DT, true, false>)
+                      : (training ? bn_nhwc_bwd_apply_kernel<DT, false, true> : bn_nhwc_bwd_apply_kernel<DT, false, false>);
+        hipLaunchKernelGGL(k, grid, block, 0, s, x, dy, weight, bias, save_mean, save_invstd, sums, dx, g);
     }
     return hip_status(hipGetLastError());
 }
@@ -346,13 +338,14 @@ int launch_batch_norm_nhwc_backward(const void *input, const void *grad_output, 
                                     float *grad_bias, int N, int C, int HW, int training, int relu, float scale, int dtype, void *ws,
                                     hipStream_t s)
 {
-    if (C % kCB || (dtype != TDRN_BF16 && dtype != TDRN_F16)) return TDRN_E_UNSUPPORTED;
+    if (C % kCB) return TDRN_E_UNSUPPORTED;
     const BnNhwcGeom g = bn_nhwc_geom(N, C, HW);
     const char *x = (const char *)input, *dy = (const char *)grad_output;
     char *dx = (char *)grad_input;
-    if (dtype == TDRN_BF16)
-        return bn_nhwc_backward_dt<bf16_t>(g, x, dy, weight, bias, save_mean, save_invstd, dx, grad_weight, grad_bias, training, relu, scale, ws, s);
-    return bn_nhwc_backward_dt<f16_t>(g, x, dy, weight, bias, save_mean, save_invstd, dx, grad_weight, grad_bias, training, relu, scale, ws, s);
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        return bn_nhwc_backward_dt<DT>(g, x, dy, weight, bias, save_mean, save_invstd, dx, grad_weight, grad_bias, training, relu, scale, ws, s);
+    });
 }
 
 }  // namespace tdrn

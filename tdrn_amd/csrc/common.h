@@ -6,6 +6,7 @@
 #include "../../include/tdrn_hip.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace tdrn {
 
@@ -139,6 +140,36 @@ inline int hip_status(hipError_t e) { return e == hipSuccess ? TDRN_OK : (int)e;
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int dtype_bytes(int dt) { return dt == TDRN_F32 ? 4 : 2; }
+
+// The one place a tdrn_dtype code picks a template instantiation: f(type_tag<DT>{}) is called with the element type and its int is
+// returned.  A code outside the set calls nothing (no launch): TDRN_E_ARG for a value that is no tdrn_dtype, TDRN_E_UNSUPPORTED for
+// TDRN_F32 at a launcher of the 16-bit types only.  A second compile-time choice (relu, a tile width, ...) is a
+// conditional between two instantiations inside f.
+template <typename T> struct type_tag { using type = T; };
+template <typename F> int dispatch_dtype16(int dtype, F &&f)
+{
+    switch (dtype) {
+        case TDRN_F32: return TDRN_E_UNSUPPORTED;
+        case TDRN_BF16: return f(type_tag<bf16_t>{});
+        case TDRN_F16: return f(type_tag<f16_t>{});
+    }
+    return TDRN_E_ARG;
+}
+template <typename F> int dispatch_dtype(int dtype, F &&f)
+{
+    return dtype == TDRN_F32 ? f(type_tag<float>{}) : dispatch_dtype16(dtype, f);
+}
+// ... and a count of 1..4 (32-column tiles, columns per lane) as a compile-time value: f(std::integral_constant<int, n>{})
+template <typename F> int dispatch_1to4(int n, F &&f)
+{
+    switch (n) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+    }
+    return TDRN_E_UNSUPPORTED;
+}
 
 // host fp32 -> bf16 / fp16 bit patterns (round to nearest even) for weight packing
 unsigned short host_f32_to_bf16(float f);

@@ -1026,15 +1026,10 @@ int launch_conv3x3_patch(const ConvArgs &a, void *out_pool, hipStream_t s)
         }
     } report{p, s, BN, (int)(p.Cin * dtype_bytes(a.dtype) / 128)};
 #endif
-#define LP(DT)                                                    \
-    return BN == 128 ? launch_patch_cfg<DT, 128>(p, s) : launch_patch_cfg<DT, 64>(p, s)
-    switch (a.dtype) {
-        case TDRN_F32: LP(float);
-        case TDRN_BF16: LP(bf16_t);
-        case TDRN_F16: LP(f16_t);
-    }
-#undef LP
-    return TDRN_E_ARG;
+    return dispatch_dtype(a.dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        return BN == 128 ? launch_patch_cfg<DT, 128>(p, s) : launch_patch_cfg<DT, 64>(p, s);
+    });
 }
 
 }  // namespace tdrn

@@ -673,16 +673,12 @@ int launch_conv3x3_pp(const ConvArgs &a, hipStream_t s)
         p.sk_slab = (float *)((char *)a.sk_ws + 1024);
         if (!a.sk_flags_zero) TDRN_HIP_TRY(hipMemsetAsync(p.sk_flag, 0, 1024, s));
     }
-#define PP_LAUNCH(DT)                                                                                                  \
-    do {                                                                                                               \
-        if (tw == 0) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 0>), dim3(grid), dim3(512), 0, s, p);                  \
-        else if (tw == 32) hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 32>), dim3(grid), dim3(512), 0, s, p);           \
-        else hipLaunchKernelGGL((conv3x3_pp_kernel<DT, 16>), dim3(grid), dim3(512), 0, s, p);                          \
-    } while (0)
-    if (a.dtype == TDRN_BF16) PP_LAUNCH(bf16_t);
-    else PP_LAUNCH(f16_t);
-#undef PP_LAUNCH
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(a.dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((tw == 0 ? conv3x3_pp_kernel<DT, 0> : tw == 32 ? conv3x3_pp_kernel<DT, 32> : conv3x3_pp_kernel<DT, 16>), dim3(grid),
+                           dim3(512), 0, s, p);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

@@ -705,16 +705,12 @@ int launch_conv3x3_ws(const ConvArgs &a, void *out_pool, hipStream_t s)
         }
     } report{p, s, grid};
 #endif
-#define WS_LAUNCH(DT)                                                                                              \
-    do {                                                                                                           \
-        if (a.fuse_x8) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, true, true>), dim3(grid), dim3(512), 0, s, p);    \
-        else if (a.fuse_x) hipLaunchKernelGGL((conv3x3_ws_kernel<DT, true>), dim3(grid), dim3(512), 0, s, p);      \
-        else hipLaunchKernelGGL((conv3x3_ws_kernel<DT, false>), dim3(grid), dim3(512), 0, s, p);                   \
-    } while (0)
-    if (a.dtype == TDRN_BF16) WS_LAUNCH(bf16_t);
-    else WS_LAUNCH(f16_t);
-#undef WS_LAUNCH
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(a.dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((a.fuse_x8 ? conv3x3_ws_kernel<DT, true, true> : a.fuse_x ? conv3x3_ws_kernel<DT, true> : conv3x3_ws_kernel<DT, false>),
+                           dim3(grid), dim3(512), 0, s, p);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

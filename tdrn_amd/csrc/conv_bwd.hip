@@ -1,9 +1,9 @@
 // conv_bwd.hip -- the gradients of the dense convolution (tdrn_hip.h section i-c; with the output pixel stepped by ConvBwdGeom::stride
 // also section i-g's weight gradient) that no inference kernel computes:
-//   grad_weight[co][ci][i][j] += scale * sum_p GO[p][co] * X[p (+) tap][ci]      (wgrad: conv_wgrad_kernel + conv_wgrad_reduce_kernel)
+//   grad_weight[co][ci][i][j] += scale * sum_p GO[p][co] * X[p (+) tap][ci]      (wgrad: conv_wgrad_kernel + slab_reduce_kernel)
 //   grad_bias[co]             += scale * sum_p GO[p][co]                         (the same two kernels)
 // and the weight packing of the input gradient, which is launch_conv over grad_output with the kernel rotated by 180 degrees
-// and its two channel axes exchanged (repack_oihw_dgrad_kernel).
+// and its two channel axes exchanged (RepackOihwDgradMap).  slab_reduce_kernel also serves ConvTranspose2d's and deform_ts's slabs.
 //
 // wgrad is a GEMM whose contraction index is the PIXEL: K = N*Ho*Wo, the output is taps x Cout x Cin.  Both operands arrive NHWC
 // (pixel rows of contiguous channels, in the compute type, channel-padded to kChanPad), so the contraction index is the row.
@@ -223,48 +223,47 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams g)
     wgrad_store<NT, ROWS>(g, acc, bacc, split, tap0, ci0, co0, lane, wm, wn, with_bias);
 }
 
-// grad_weight[co][ci][tap] += scale * sum_{s = 0..S-1} slab[s][tap][co][ci] (thread index: ci fastest -> coalesced slab reads), then
-// grad_bias[co] += scale * sum_s bslab[s][co]
-__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__restrict__ slab, const float *__restrict__ bslab,
-                                                                float *__restrict__ gw, float *__restrict__ gb, int Cout, int Cin, int taps,
-                                                                int CoPad, int CiPad, int S, float scale)
+// The one reduce of the split-K slabs [split][row(t, co) = t * pitch + co][CiPad] (SlabReduce, kernels.h; thread index: ci fastest ->
+// coalesced slab reads): the sum over the S splits in split order, in fp32, lands at gw[co * d_co + ci * d_ci + t * d_t] as
+// fmaf(scale, sum, *d) (accumulate) or as a plain store that never reads the destination.  Then, with gb:
+// grad_bias[co] += scale * sum_s sum_{z < bias_rows} bslab[s][z * pitch + co], the split outer and the row inner.
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restrict__ slab, const float *__restrict__ bslab,
+                                                          float *__restrict__ gw, float *__restrict__ gb, const SlabReduce r, int S)
 {
-    const long long total = (long long)taps * Cout * Cin;
-    const size_t sstride = (size_t)taps * CoPad * CiPad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total + (gb ? Cout : 0); i += (long long)gridDim.x * blockDim.x) {
+    const long long total = (long long)r.taps * r.Cout * r.Cin;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total + (gb ? r.Cout : 0); i += (long long)gridDim.x * blockDim.x) {
         if (i >= total) {
             const int co = (int)(i - total);
             float s = 0.f;
-            for (int k = 0; k < S; ++k) s += bslab[(size_t)k * CoPad + co];
-            gb[co] = fmaf(scale, s, gb[co]);
+            for (int k = 0; k < S; ++k)
+                for (int z = 0; z < r.bias_rows; ++z) s += bslab[((size_t)k * r.bias_rows + z) * r.pitch + co];
+            gb[co] = fmaf(r.scale, s, gb[co]);
             continue;
         }
-        const int c = (int)(i % Cin);
-        const long long r = i / Cin;
-        const int co = (int)(r % Cout), tap = (int)(r / Cout);
-        const float *sp = slab + ((size_t)tap * CoPad + co) * CiPad + c;
+        const int c = (int)(i % r.Cin);
+        const long long q = i / r.Cin;
+        const int co = (int)(q % r.Cout), t = (int)(q / r.Cout);
+        const float *sp = slab + ((size_t)t * r.pitch + co) * r.CiPad + c;
         float s = 0.f;
-        for (int k = 0; k < S; ++k) s += sp[k * sstride];
-        float *d = gw + ((size_t)co * Cin + c) * taps + tap;
-        *d = fmaf(scale, s, *d);
+        for (int k = 0; k < S; ++k) s += sp[k * r.sstride];
+        float *d = gw + (size_t)co * r.d_co + (size_t)c * r.d_ci + (size_t)t * r.d_t;
+        if (r.accumulate) *d = fmaf(r.scale, s, *d);
+        else *d = s;
     }
 }
 
 // OIHW fp32 -> the forward packing of the dgrad conv: out[ci][taps - 1 - tap][co] = w[co][ci][tap], rows >= Cin and channels >= Cout zero
-template <typename DT>
-__global__ __launch_bounds__(256) void repack_oihw_dgrad_kernel(const float *__restrict__ w, char *__restrict__ out, int Cout, int Cin,
-                                                                int Npad, int taps, int CoPad)
-{
-    constexpr int ES = elem_traits<DT>::bytes;
-    const long long total = (long long)Npad * taps * CoPad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+struct RepackOihwDgradMap {
+    const float *w;
+    int Cout, Cin, taps, CoPad;
+    __device__ float operator()(long long i) const
+    {
         const int co = (int)(i % CoPad);
         const long long r = i / CoPad;
         const int tp = (int)(r % taps), ci = (int)(r / taps);
-        const float v = (ci < Cin && co < Cout) ? w[((size_t)co * Cin + ci) * taps + (taps - 1 - tp)] : 0.f;
-        *(DT *)(out + (size_t)i * ES) = from_f32<DT>(v);
+        return (ci < Cin && co < Cout) ? w[((size_t)co * Cin + ci) * taps + (taps - 1 - tp)] : 0.f;
     }
-}
+};
 
 template <typename DT> int launch_wgrad_dt(const WgradParams &p, int taps, dim3 grid, hipStream_t s)
 {
@@ -302,12 +301,13 @@ size_t conv_wgrad_slab_bytes(const ConvBwdGeom &g)
 int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int Npad, int taps, int dtype, hipStream_t s)
 {
     const int CoPad = conv_bwd_cpad(Cout);
-    const long long total = (long long)Npad * taps * CoPad;
-    if (total <= 0) return TDRN_OK;
-    dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((repack_oihw_dgrad_kernel<DT>), grid, dim3(256), 0, s, w, (char *)out, Cout, Cin, Npad, taps, CoPad)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
+    return launch_pack(dtype, out, (long long)Npad * taps * CoPad, RepackOihwDgradMap{w, Cout, Cin, taps, CoPad}, s);
+}
+
+int launch_slab_reduce(const SlabReduce &r, const float *slab, const float *bslab, float *gw, float *gb, int S, hipStream_t s)
+{
+    const long long total = (long long)r.taps * r.Cout * r.Cin + (gb ? r.Cout : 0);
+    hipLaunchKernelGGL(slab_reduce_kernel, stride_grid(total, 4096), dim3(256), 0, s, slab, bslab, gw, gb, r, S);
     return hip_status(hipGetLastError());
 }
 
@@ -326,15 +326,9 @@ int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void
     p.M = g.N * g.Ho * g.Wo; p.H = g.H; p.W = g.W; p.Ho = g.Ho; p.Wo = g.Wo; p.HoWo = g.Ho * g.Wo;
     p.pad = g.pad; p.dil = g.dil; p.per_split = per_split; p.stride = g.stride;
     const dim3 grid((unsigned)S, (unsigned)(p.CiPad / kWgTile), (unsigned)(p.CoPad / kWgTile));
-    int rc = TDRN_E_ARG;
-    switch (dtype) {
-        case TDRN_F32: rc = launch_wgrad_dt<float>(p, taps, grid, s); break;
-        case TDRN_BF16: rc = launch_wgrad_dt<bf16_t>(p, taps, grid, s); break;
-        case TDRN_F16: rc = launch_wgrad_dt<f16_t>(p, taps, grid, s); break;
-    }
     splits = S;
     bias_slab = p.bslab;
-    return rc;
+    return dispatch_dtype(dtype, [&](auto tag) { return launch_wgrad_dt<typename decltype(tag)::type>(p, taps, grid, s); });
 }
 
 int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, float *grad_weight,
@@ -345,11 +339,12 @@ int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_n
     const float *bslab;
     TDRN_TRY(launch_conv_wgrad_slabs(g, x_nhwc, go_nhwc, zero_page, slab, dtype, s, S, bslab));
     const int taps = g.k * g.k, CoPad = conv_bwd_cpad(g.Cout), CiPad = conv_bwd_cpad(g.Cin);
-    const long long total = (long long)taps * g.Cout * g.Cin + (grad_bias ? g.Cout : 0);
-    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float *)slab, bslab, grad_weight, grad_bias,
-                       g.Cout, g.Cin, taps, CoPad, CiPad, S, scale);
-    return hip_status(hipGetLastError());
+    SlabReduce r;
+    r.Cout = g.Cout; r.Cin = g.Cin; r.taps = taps;
+    r.d_co = (long long)g.Cin * taps; r.d_ci = taps; r.d_t = 1;                 // OIHW
+    r.pitch = CoPad; r.CiPad = CiPad; r.sstride = (size_t)taps * CoPad * CiPad;
+    r.bias_rows = 1; r.scale = scale; r.accumulate = true;
+    return launch_slab_reduce(r, (const float *)slab, bslab, grad_weight, grad_bias, S, s);
 }
 
 }  // namespace tdrn

@@ -569,21 +569,14 @@ int launch_conv_igemm(const ConvArgs &a, hipStream_t s)
     ConvParams p;
     TDRN_TRY(make_params(a, p));
     if (p.M <= 0) return TDRN_OK;
-    int rc = TDRN_E_ARG;
-    switch (a.dtype) {
-        case TDRN_F32: rc = launch_dt<float>(p, a.phases, s); break;
-        case TDRN_BF16: rc = launch_dt<bf16_t>(p, a.phases, s); break;
-        case TDRN_F16: rc = launch_dt<f16_t>(p, a.phases, s); break;
-    }
-    if (rc != TDRN_OK || p.splits == 1) return rc;
-    const long long total = (long long)a.phases * p.M * ((p.Cout + 3) / 4);
-    dim3 grid((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256));
-    switch (a.dtype) {
-        case TDRN_F32: hipLaunchKernelGGL((splitk_reduce_kernel<float>), grid, dim3(256), 0, s, p, a.phases); break;
-        case TDRN_BF16: hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), grid, dim3(256), 0, s, p, a.phases); break;
-        case TDRN_F16: hipLaunchKernelGGL((splitk_reduce_kernel<f16_t>), grid, dim3(256), 0, s, p, a.phases); break;
-    }
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(a.dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        const int rc = launch_dt<DT>(p, a.phases, s);
+        if (rc != TDRN_OK || p.splits == 1) return rc;
+        const long long total = (long long)a.phases * p.M * ((p.Cout + 3) / 4);
+        hipLaunchKernelGGL((splitk_reduce_kernel<DT>), stride_grid(total, 4096), dim3(256), 0, s, p, a.phases);
+        return hip_status(hipGetLastError());
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -744,13 +737,10 @@ int launch_conv_chain(const ChainLayer *layers, int n, unsigned *ctr, hipStream_
     cp.total = task0;
     if (cp.total <= 0) return TDRN_OK;
     const int grid = cp.total < 512 ? cp.total : 512;             // two 66-KiB workgroups per CU
-    switch (dtype) {
-        case TDRN_F32: hipLaunchKernelGGL((conv_chain_kernel<float>), dim3(grid), dim3(256), 0, s, cp); break;
-        case TDRN_BF16: hipLaunchKernelGGL((conv_chain_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, cp); break;
-        case TDRN_F16: hipLaunchKernelGGL((conv_chain_kernel<f16_t>), dim3(grid), dim3(256), 0, s, cp); break;
-        default: return TDRN_E_ARG;
-    }
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((conv_chain_kernel<typename decltype(tag)::type>), dim3(grid), dim3(256), 0, s, cp);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

@@ -93,18 +93,6 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_dilate2_kernel(const float *
     }
 }
 
-template <typename DT>
-int launch_dilate2_dt(const float *in, void *out, int N, int Cout, int Ho, int Wo, int Hd, int Wd, hipStream_t s)
-{
-    const int CoPad = conv_bwd_cpad(Cout), wtiles = cdiv(Wo, kDilPx), ctiles = CoPad / kDilCh;
-    const dim3 grid((unsigned)((long long)N * Ho * wtiles * ctiles));
-    if (Wo % 4 == 0)
-        hipLaunchKernelGGL((nchw_to_nhwc_dilate2_kernel<DT, true>), grid, dim3(256), 0, s, in, (char *)out, Cout, Ho, Wo, Hd, Wd, CoPad, wtiles, ctiles);
-    else
-        hipLaunchKernelGGL((nchw_to_nhwc_dilate2_kernel<DT, false>), grid, dim3(256), 0, s, in, (char *)out, Cout, Ho, Wo, Hd, Wd, CoPad, wtiles, ctiles);
-    return hip_status(hipGetLastError());
-}
-
 }  // namespace
 
 int launch_nchw_to_nhwc_dilate2(const float *in, void *out, int N, int Cout, int Ho, int Wo, int Hd, int Wd, int dtype, hipStream_t s)
@@ -113,10 +101,15 @@ int launch_nchw_to_nhwc_dilate2(const float *in, void *out, int N, int Cout, int
     // every row and column of D must belong to a grad_output pixel: the kernel writes rows 2ho, 2ho + 1 and columns 2wo, 2wo + 1 only
     if (Hd < 2 * Ho - 1 || Hd > 2 * Ho || Wd < 2 * Wo - 1 || Wd > 2 * Wo) return TDRN_E_UNSUPPORTED;
     // one workgroup per (grad_output row, 16 pixels, 64 channels): fewer than the N Hd Wd CoPad / 64 the caller keeps under 2^31
-    if ((long long)N * Ho * cdiv(Wo, kDilPx) * (conv_bwd_cpad(Cout) / kDilCh) >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    if (dtype == TDRN_F32) return launch_dilate2_dt<float>(in, out, N, Cout, Ho, Wo, Hd, Wd, s);
-    if (dtype == TDRN_BF16) return launch_dilate2_dt<bf16_t>(in, out, N, Cout, Ho, Wo, Hd, Wd, s);
-    return launch_dilate2_dt<f16_t>(in, out, N, Cout, Ho, Wo, Hd, Wd, s);
+    const int CoPad = conv_bwd_cpad(Cout), wtiles = cdiv(Wo, kDilPx), ctiles = CoPad / kDilCh;
+    if ((long long)N * Ho * wtiles * ctiles >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((long long)N * Ho * wtiles * ctiles));
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((Wo % 4 == 0 ? nchw_to_nhwc_dilate2_kernel<DT, true> : nchw_to_nhwc_dilate2_kernel<DT, false>), grid, dim3(256), 0, s,
+                           in, (char *)out, Cout, Ho, Wo, Hd, Wd, CoPad, wtiles, ctiles);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

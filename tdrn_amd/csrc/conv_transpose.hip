@@ -14,8 +14,8 @@
 //     The read-back is ds_read_b128 over 64 consecutive dwords per 16 lanes.
 //   * which elements a thread takes depends on (n, h, tile, thread) alone, never on an address, and nothing is summed: a caller's
 //     buffer on any 4-byte boundary gives the same bits (the 16-byte loads then run on a 4-byte boundary, which global loads allow).
-// The packers and the reduce are small grid-stride kernels, siblings of repack_oihw_dgrad_kernel / conv_wgrad_reduce_kernel
-// (conv_bwd.hip) for the (Cin, Cout, 2, 2) weight layout.  No float atomics: every gradient is bitwise reproducible.
+// The packers are index maps of pack_kernel (kernels.h) and the reduce is slab_reduce_kernel (conv_bwd.hip) with the strides of
+// the (Cin, Cout, 2, 2) weight layout.  No float atomics: every gradient is bitwise reproducible.
 #include <algorithm>
 
 #include "kernels.h"
@@ -85,77 +85,31 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_s2d_kernel(const float *__re
 }
 
 // (Cin, Cout, 2, 2) fp32 -> out[z][co][ci] ([4][Npad][CiPad]): launch_conv's phases = 4 packing; rows >= Cout and channels >= Cin zero
-template <typename DT>
-__global__ __launch_bounds__(256) void repack_iohw_phases_kernel(const float *__restrict__ w, char *__restrict__ out, int Cin, int Cout,
-                                                                 int Npad, int CiPad)
-{
-    constexpr int ES = elem_traits<DT>::bytes;
-    const long long total = 4ll * Npad * CiPad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+struct RepackIohwPhasesMap {
+    const float *w;
+    int Cin, Cout, Npad, CiPad;
+    __device__ float operator()(long long i) const
+    {
         const int ci = (int)(i % CiPad);
         const long long r = i / CiPad;
         const int co = (int)(r % Npad), z = (int)(r / Npad);
-        const float v = (ci < Cin && co < Cout) ? w[((size_t)ci * Cout + co) * 4 + z] : 0.f;
-        *(DT *)(out + (size_t)i * ES) = from_f32<DT>(v);
+        return (ci < Cin && co < Cout) ? w[((size_t)ci * Cout + co) * 4 + z] : 0.f;
     }
-}
+};
 
 // (Cin, Cout, 2, 2) fp32 -> out[ci][z * CoPad + co] ([Npad][4 CoPad]): the 1x1 conv over the space-to-depth image; rows >= Cin and
 // channels >= Cout of every phase zero
-template <typename DT>
-__global__ __launch_bounds__(256) void repack_iohw_dgrad_kernel(const float *__restrict__ w, char *__restrict__ out, int Cin, int Cout,
-                                                                int Npad, int CoPad)
-{
-    constexpr int ES = elem_traits<DT>::bytes;
-    const long long total = 4ll * Npad * CoPad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+struct RepackIohwDgradMap {
+    const float *w;
+    int Cin, Cout, CoPad;
+    __device__ float operator()(long long i) const
+    {
         const int co = (int)(i % CoPad);
         const long long r = i / CoPad;
         const int z = (int)(r & 3), ci = (int)(r >> 2);
-        const float v = (ci < Cin && co < Cout) ? w[((size_t)ci * Cout + co) * 4 + z] : 0.f;
-        *(DT *)(out + (size_t)i * ES) = from_f32<DT>(v);
+        return (ci < Cin && co < Cout) ? w[((size_t)ci * Cout + co) * 4 + z] : 0.f;
     }
-}
-
-// grad_weight[ci][co][z] += scale * sum_{s = 0..S-1} slab[s][z * CoPad + co][ci] (thread index: ci fastest -> coalesced slab reads), then
-// grad_bias[co] += scale * sum_s sum_z bslab[s][z * CoPad + co]
-__global__ __launch_bounds__(256) void convt_wgrad_reduce_kernel(const float *__restrict__ slab, const float *__restrict__ bslab,
-                                                                 float *__restrict__ gw, float *__restrict__ gb, int Cin, int Cout, int CoPad,
-                                                                 int CiPad, int S, float scale)
-{
-    const long long total = 4ll * Cout * Cin;
-    const size_t sstride = (size_t)4 * CoPad * CiPad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total + (gb ? Cout : 0); i += (long long)gridDim.x * blockDim.x) {
-        if (i >= total) {
-            const int co = (int)(i - total);
-            float s = 0.f;
-            for (int k = 0; k < S; ++k)
-                for (int z = 0; z < 4; ++z) s += bslab[((size_t)k * 4 + z) * CoPad + co];
-            gb[co] = fmaf(scale, s, gb[co]);
-            continue;
-        }
-        const int c = (int)(i % Cin);
-        const long long r = i / Cin;
-        const int co = (int)(r % Cout), z = (int)(r / Cout);
-        const float *sp = slab + ((size_t)z * CoPad + co) * CiPad + c;
-        float s = 0.f;
-        for (int k = 0; k < S; ++k) s += sp[k * sstride];
-        float *d = gw + ((size_t)c * Cout + co) * 4 + z;
-        *d = fmaf(scale, s, *d);
-    }
-}
-
-template <typename DT>
-int launch_s2d_dt(const float *in, void *out, int N, int Cout, int H, int W, hipStream_t s)
-{
-    const int CoPad = conv_bwd_cpad(Cout), wtiles = cdiv(W, kS2dPx), ctiles = CoPad / kS2dCh;
-    const dim3 grid((unsigned)((long long)N * H * wtiles * ctiles));
-    if (W % 2 == 0) hipLaunchKernelGGL((nchw_to_nhwc_s2d_kernel<DT, true>), grid, dim3(256), 0, s, in, (char *)out, Cout, H, W, CoPad, wtiles, ctiles);
-    else hipLaunchKernelGGL((nchw_to_nhwc_s2d_kernel<DT, false>), grid, dim3(256), 0, s, in, (char *)out, Cout, H, W, CoPad, wtiles, ctiles);
-    return hip_status(hipGetLastError());
-}
-
-dim3 stride_grid(long long total) { return dim3((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256)); }
+};
 
 }  // namespace
 
@@ -163,40 +117,39 @@ int launch_nchw_to_nhwc_s2d(const float *in, void *out, int N, int Cout, int H, 
 {
     if (N <= 0 || Cout <= 0 || H <= 0 || W <= 0) return TDRN_OK;
     // one workgroup per (image row, 16 pixels, 64 channels): the count stays below N H W 4 CoPad / 4096, which the caller keeps under 2^31
-    if ((long long)N * H * cdiv(W, kS2dPx) * (conv_bwd_cpad(Cout) / kS2dCh) >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
-    if (dtype == TDRN_F32) return launch_s2d_dt<float>(in, out, N, Cout, H, W, s);
-    if (dtype == TDRN_BF16) return launch_s2d_dt<bf16_t>(in, out, N, Cout, H, W, s);
-    return launch_s2d_dt<f16_t>(in, out, N, Cout, H, W, s);
+    const int CoPad = conv_bwd_cpad(Cout), wtiles = cdiv(W, kS2dPx), ctiles = CoPad / kS2dCh;
+    if ((long long)N * H * wtiles * ctiles >= (1ll << 31)) return TDRN_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((long long)N * H * wtiles * ctiles));
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((W % 2 == 0 ? nchw_to_nhwc_s2d_kernel<DT, true> : nchw_to_nhwc_s2d_kernel<DT, false>), grid, dim3(256), 0, s, in,
+                           (char *)out, Cout, H, W, CoPad, wtiles, ctiles);
+        return hip_status(hipGetLastError());
+    });
 }
 
 int launch_repack_iohw_phases(const float *w, void *out, int Cin, int Cout, int Npad, int dtype, hipStream_t s)
 {
     const int CiPad = conv_bwd_cpad(Cin);
-    const dim3 grid = stride_grid(4ll * Npad * CiPad);
-#define L(DT) hipLaunchKernelGGL((repack_iohw_phases_kernel<DT>), grid, dim3(256), 0, s, w, (char *)out, Cin, Cout, Npad, CiPad)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return launch_pack(dtype, out, 4ll * Npad * CiPad, RepackIohwPhasesMap{w, Cin, Cout, Npad, CiPad}, s);
 }
 
 int launch_repack_iohw_dgrad(const float *w, void *out, int Cin, int Cout, int Npad, int dtype, hipStream_t s)
 {
     const int CoPad = conv_bwd_cpad(Cout);
-    const dim3 grid = stride_grid(4ll * Npad * CoPad);
-#define L(DT) hipLaunchKernelGGL((repack_iohw_dgrad_kernel<DT>), grid, dim3(256), 0, s, w, (char *)out, Cin, Cout, Npad, CoPad)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return launch_pack(dtype, out, 4ll * Npad * CoPad, RepackIohwDgradMap{w, Cin, Cout, CoPad}, s);
 }
 
 int launch_convt_wgrad_reduce(const float *slab, const float *bias_slab, float *grad_weight, float *grad_bias, int Cin, int Cout, int splits,
                               float scale, hipStream_t s)
 {
-    const long long total = 4ll * Cout * Cin + (grad_bias ? Cout : 0);
-    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(convt_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slab, bias_slab, grad_weight, grad_bias, Cin, Cout,
-                       conv_bwd_cpad(Cout), conv_bwd_cpad(Cin), splits, scale);
-    return hip_status(hipGetLastError());
+    const int CoPad = conv_bwd_cpad(Cout), CiPad = conv_bwd_cpad(Cin);
+    SlabReduce r;
+    r.Cout = Cout; r.Cin = Cin; r.taps = 4;
+    r.d_co = 4; r.d_ci = 4ll * Cout; r.d_t = 1;                                 // (Cin, Cout, 2, 2)
+    r.pitch = CoPad; r.CiPad = CiPad; r.sstride = (size_t)4 * CoPad * CiPad;
+    r.bias_rows = 4; r.scale = scale; r.accumulate = true;
+    return launch_slab_reduce(r, slab, bias_slab, grad_weight, grad_bias, splits, s);
 }
 
 }  // namespace tdrn

@@ -285,19 +285,6 @@ __global__ __launch_bounds__(256) void deform_gemm_kernel(const DeformMulti mp)
 
 int deform_n_pad(int cout) { return (int)align_up((size_t)cout, 32); }
 
-template <typename DT> static int launch_deform_dt(const DeformMulti &mp, int ntl, hipStream_t s)
-{
-    dim3 grid((unsigned)(8 * ((mp.block_start[mp.n] + 7) / 8)));
-    switch (ntl) {
-        case 1: hipLaunchKernelGGL((deform_gemm_kernel<DT, 1>), grid, dim3(256), 0, s, mp); break;
-        case 2: hipLaunchKernelGGL((deform_gemm_kernel<DT, 2>), grid, dim3(256), 0, s, mp); break;
-        case 3: hipLaunchKernelGGL((deform_gemm_kernel<DT, 3>), grid, dim3(256), 0, s, mp); break;
-        case 4: hipLaunchKernelGGL((deform_gemm_kernel<DT, 4>), grid, dim3(256), 0, s, mp); break;
-        default: return TDRN_E_UNSUPPORTED;
-    }
-    return hip_status(hipGetLastError());
-}
-
 static int fill_params(const DeformArgs &a, DeformParams &p)
 {
     if (!a.in || !a.out0 || a.n_branches < 1 || a.n_branches > 2) return TDRN_E_ARG;
@@ -372,12 +359,14 @@ int launch_deform_multi(const DeformArgs *args, int n, hipStream_t s, int split_
     }
     if (mp.n == 0) return TDRN_OK;
     for (int i = mp.n; i < kMaxDeformProblems; ++i) { mp.p[i] = mp.p[0]; mp.block_start[i + 1] = mp.block_start[mp.n]; }
-    switch (args[0].dtype) {
-        case TDRN_F32: return launch_deform_dt<float>(mp, args[0].Npad / 32, s);
-        case TDRN_BF16: return launch_deform_dt<bf16_t>(mp, args[0].Npad / 32, s);
-        case TDRN_F16: return launch_deform_dt<f16_t>(mp, args[0].Npad / 32, s);
-    }
-    return TDRN_E_ARG;
+    const dim3 grid((unsigned)(8 * ((mp.block_start[mp.n] + 7) / 8)));
+    return dispatch_dtype(args[0].dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        return dispatch_1to4(args[0].Npad / 32, [&](auto ntl) {
+            hipLaunchKernelGGL((deform_gemm_kernel<DT, decltype(ntl)::value>), grid, dim3(256), 0, s, mp);
+            return hip_status(hipGetLastError());
+        });
+    });
 }
 
 int launch_deform(const DeformArgs &a, hipStream_t s) { return launch_deform_multi(&a, 1, s, 0); }
@@ -392,8 +381,8 @@ int launch_deform(const DeformArgs &a, hipStream_t s) { return launch_deform_mul
 // kernel's, at dense-GEMM rate, fp32 accumulation, rounded once to the net dtype); the bilinear blend then gathers 160-byte
 // rows instead of 512-byte ones and blends 75 values per corner instead of 256 -- 3.4x less of exactly the two things that
 // bound deform_gemm_kernel above (gathered bytes, vector-ALU blend: profiles/r02_final).  The sampling rule -- which taps
-// are rejected, the (H-1, H) clamp, fp32 offsets and weights -- is the same code as tap_params() there
-// (deform_conv_cuda_kernel.cu:15-51, 189-203); no atomics, no zero-fill: one wave owns one output pixel and both branches.
+// are rejected, the (H-1, H) clamp, fp32 offsets and weights -- is deform_sample() (deform_sampler.h), the function the fused
+// kernel and the backward kernels call; no atomics, no zero-fill: one wave owns one output pixel and both branches.
 // Where the rounding sits differs from the fused kernel (Y is rounded to 16 bits, there the blended columns are); the fp32
 // mode and the fp32 C-ABI entry keep the fused kernel.
 // =============================================================================================
@@ -450,24 +439,13 @@ __global__ __launch_bounds__(256) void deform_sample_kernel(const SampleMulti mp
         const int ti = tl / B.kw, tj = tl - ti * B.kw;
         const int orow = B.off_rows ? (m + B.off_row0) % B.off_rows : m;
         const float *op = B.off + (size_t)orow * B.off_stride + 2 * tl;
-        const float offset_h = op[0], offset_w = op[1];
         float w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f;
         int q1 = 0, q2 = 0, q3 = 0, q4 = 0;
-        const int h_in = ho - B.pad_h, w_in = wo - B.pad_w;
-        const float h_im = (float)(h_in + ti * B.dil_h) + offset_h;
-        const float w_im = (float)(w_in + tj * B.dil_w) + offset_w;
-        if (h_im >= 0.f && w_im >= 0.f && h_im < (float)p.H && w_im < (float)p.W) {
-            float h = (float)(ti * B.dil_h) + offset_h;     // map_h, relative to h_in
-            float w = (float)(tj * B.dil_w) + offset_w;
-            const int height = p.H - h_in, width = p.W - w_in;
-            int h_low = (int)floorf(h), w_low = (int)floorf(w), h_high, w_high;
-            if (h_low >= height - 1) { h_high = h_low = height - 1; h = (float)h_low; } else { h_high = h_low + 1; }
-            if (w_low >= width - 1) { w_high = w_low = width - 1; w = (float)w_low; } else { w_high = w_low + 1; }
-            const float lh = h - (float)h_low, lw = w - (float)w_low;
+        int r0, r1, c0, c1;
+        float lh, lw;
+        if (deform_sample(p.H, p.W, ho - B.pad_h, wo - B.pad_w, ti * B.dil_h, tj * B.dil_w, op[0], op[1], r0, r1, c0, c1, lh, lw)) {
             const float hh = 1.f - lh, hw = 1.f - lw;
             w1 = hh * hw; w2 = hh * lw; w3 = lh * hw; w4 = lh * lw;
-            const int r0 = min(max(h_in + h_low, 0), p.H - 1), r1 = min(max(h_in + h_high, 0), p.H - 1);
-            const int c0 = min(max(w_in + w_low, 0), p.W - 1), c1 = min(max(w_in + w_high, 0), p.W - 1);
             q1 = r0 * p.W + c0; q2 = r0 * p.W + c1; q3 = r1 * p.W + c0; q4 = r1 * p.W + c1;
         }
         const unsigned colb = p.tap_major ? (unsigned)(B.col0 + tl) * (unsigned)p.M * (unsigned)(kSampleCols * 2) : (unsigned)(deform_y_col(B.col0 + tl) * 2);
@@ -950,14 +928,12 @@ int launch_ygemm_multi(const YGemmProblem *pr, int n, int dtype, hipStream_t s, 
 #endif
     bool tapmajor = true;
     for (int i = 0; i < mp.n; ++i) tapmajor = tapmajor && mp.p[i].taps > 0;
-    if (!(kdisable & KOFF_YGEMM_V2) && tapmajor) {
-        if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_v2_kernel<bf16_t>), grid, dim3(512), 0, s, mp);
-        else hipLaunchKernelGGL((ygemm_k256_v2_kernel<f16_t>), grid, dim3(512), 0, s, mp);
-    } else {
-        if (dtype == TDRN_BF16) hipLaunchKernelGGL((ygemm_k256_kernel<bf16_t>), grid, dim3(512), 0, s, mp);
-        else hipLaunchKernelGGL((ygemm_k256_kernel<f16_t>), grid, dim3(512), 0, s, mp);
-    }
-    return hip_status(hipGetLastError());
+    const bool v2 = !(kdisable & KOFF_YGEMM_V2) && tapmajor;
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((v2 ? ygemm_k256_v2_kernel<DT> : ygemm_k256_kernel<DT>), grid, dim3(512), 0, s, mp);
+        return hip_status(hipGetLastError());
+    });
 }
 
 int launch_ygemm(const void *x, const void *w, void *y, long long M, int N, int ycs, int dtype, hipStream_t s, int taps)
@@ -1024,9 +1000,10 @@ int launch_deform_sample_multi(const DeformArgs *args, const void *const *y, con
     if (mp.n == 0) return TDRN_OK;
     for (int i = mp.n; i < 4; ++i) { mp.p[i] = mp.p[0]; mp.block_start[i + 1] = mp.block_start[mp.n]; }
     dim3 grid((unsigned)mp.block_start[mp.n]);
-    if (args[0].dtype == TDRN_BF16) hipLaunchKernelGGL((deform_sample_kernel<bf16_t>), grid, dim3(256), 0, s, mp);
-    else hipLaunchKernelGGL((deform_sample_kernel<f16_t>), grid, dim3(256), 0, s, mp);
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(args[0].dtype, [&](auto tag) {
+        hipLaunchKernelGGL((deform_sample_kernel<typename decltype(tag)::type>), grid, dim3(256), 0, s, mp);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

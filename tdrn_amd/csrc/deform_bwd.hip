@@ -362,8 +362,7 @@ int launch_deform_bwd_weight(const DeformBwdGeom &g, const float *in_nhwc, const
         hipLaunchKernelGGL((deform_bwd_weight_kernel<32>), grid, dim3(256), 0, s, in_nhwc, off, gout, slab, k, per_split);
     TDRN_HIP_TRY(hipGetLastError());
     const long long total = (long long)k.taps * g.Cout * g.Cin;
-    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(deform_bwd_weight_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slab, grad_weight, k, S, scale);
+    hipLaunchKernelGGL(deform_bwd_weight_reduce_kernel, stride_grid(total, 4096), dim3(256), 0, s, slab, grad_weight, k, S, scale);
     return hip_status(hipGetLastError());
 }
 

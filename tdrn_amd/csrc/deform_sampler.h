@@ -1,5 +1,5 @@
-// deform_sampler.h -- the bilinear sampling rule of deformable conv v1, shared by the forward gather (deform.hip
-// deform_gemm_kernel) and the backward kernels (deform_bwd.hip).
+// deform_sampler.h -- the bilinear sampling rule of deformable conv v1, shared by the forward kernels (deform.hip
+// deform_gemm_kernel and deform_sample_kernel), the backward kernels (deform_bwd.hip) and the transform-domain op (deform_ts.hip).
 //
 // utils/deformconv/deform_conv_cuda_kernel.cu:15-51 and :189-203, including the asymmetric border rule: a sample
 // coordinate < 0 or >= H (W) is rejected (returns false); a coordinate in [H-1, H) clamps to row H-1 with fraction 0.

@@ -21,10 +21,8 @@
 //                              zero inside the clamp band (the corners coincide there), stored once; Z[q][t][.] += b gO[p][.], one
 //                              contiguous fp32 atomic wave-instruction per corner row with a non-zero coefficient.
 //   deform_ts_round_kernel     Z fp32 -> 16 bit, one rounding to nearest even
-//   deform_ts_repack_kernel    OIHW fp32 -> the two 1x1 matrices: [t Cp + co][c] (Y) and [c][t Cp + co] (grad_input)
-//   deform_ts_wgrad_reduce     grad_weight[co][c][t] = the slabs' rows t Cp + co summed in split order (overwrites)
-#include <algorithm>
-
+//   TsRepackMap (pack_kernel)  OIHW fp32 -> the two 1x1 matrices: [t Cp + co][c] (Y) and [c][t Cp + co] (grad_input)
+//   deform_ts_wgrad_reduce     grad_weight[co][c][t] = the slabs' rows t Cp + co summed in split order (overwrites): slab_reduce_kernel
 #include "deform_sampler.h"
 #include "kernels.h"
 
@@ -177,70 +175,17 @@ __global__ __launch_bounds__(256) void deform_ts_round_kernel(const float *__res
 }
 
 // OIHW fp32 -> DGRAD ? out[c][t Cp + co] ([Npad][YC]) : out[t Cp + co][c] ([Npad][Cin]); everything that is no weight is zero
-template <typename DT, bool DGRAD>
-__global__ __launch_bounds__(256) void deform_ts_repack_kernel(const float *__restrict__ w, char *__restrict__ out, int Cout, int Cin,
-                                                               int taps, int Cp, int YC, int Npad)
-{
-    constexpr int ES = elem_traits<DT>::bytes;
-    const int inner = DGRAD ? YC : Cin;
-    const long long total = (long long)Npad * inner;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+template <bool DGRAD> struct TsRepackMap {
+    const float *w;
+    int Cout, Cin, taps, Cp, inner;      // inner = DGRAD ? YC : Cin
+    __device__ float operator()(long long i) const
+    {
         const int a = (int)(i % inner), r = (int)(i / inner);
         const int col = DGRAD ? a : r, c = DGRAD ? r : a;
         const int t = col / Cp, co = col - t * Cp;
-        const float v = (t < taps && co < Cout && c < Cin) ? w[((size_t)co * Cin + c) * taps + t] : 0.f;
-        *(DT *)(out + (size_t)i * ES) = from_f32<DT>(v);
+        return (t < taps && co < Cout && c < Cin) ? w[((size_t)co * Cin + c) * taps + t] : 0.f;
     }
-}
-
-// grad_weight[co][c][t] = sum_{s = 0..S-1} slab[s][t Cp + co][c]   (thread index: c fastest -> coalesced slab reads)
-__global__ __launch_bounds__(256) void deform_ts_wgrad_reduce_kernel(const float *__restrict__ slab, float *__restrict__ gw, int Cout,
-                                                                     int Cin, int taps, int Cp, int YC, int S)
-{
-    const long long total = (long long)taps * Cout * Cin;
-    const size_t sstride = (size_t)YC * Cin;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % Cin);
-        const long long r = i / Cin;
-        const int co = (int)(r % Cout), t = (int)(r / Cout);
-        const float *sp = slab + ((size_t)t * Cp + co) * Cin + c;
-        float s = 0.f;
-        for (int k = 0; k < S; ++k) s += sp[k * sstride];
-        gw[((size_t)co * Cin + c) * taps + t] = s;
-    }
-}
-
-dim3 ts_stride_grid(long long total) { return dim3((unsigned)std::min<long long>((total + 255) / 256, 16384)); }
-
-template <typename DT>
-int sample_dt(const TsGeomK &k, const void *y, const float *off, float *out, hipStream_t s)
-{
-    const dim3 grid((unsigned)cdiv(k.M, 4));
-    const DT *yp = (const DT *)y;
-    switch (cdiv(k.Cout, 64)) {
-        case 1: hipLaunchKernelGGL((deform_ts_sample_kernel<DT, 1>), grid, dim3(256), 0, s, yp, off, out, k); break;
-        case 2: hipLaunchKernelGGL((deform_ts_sample_kernel<DT, 2>), grid, dim3(256), 0, s, yp, off, out, k); break;
-        case 3: hipLaunchKernelGGL((deform_ts_sample_kernel<DT, 3>), grid, dim3(256), 0, s, yp, off, out, k); break;
-        case 4: hipLaunchKernelGGL((deform_ts_sample_kernel<DT, 4>), grid, dim3(256), 0, s, yp, off, out, k); break;
-        default: return TDRN_E_UNSUPPORTED;
-    }
-    return hip_status(hipGetLastError());
-}
-
-template <typename DT>
-int backward_dt(const TsGeomK &k, const void *y, const float *off, const float *go, float *z, float *goff, hipStream_t s)
-{
-    const dim3 grid((unsigned)cdiv(k.M, 4));
-    const DT *yp = (const DT *)y;
-    switch (cdiv(k.Cout, 64)) {
-        case 1: hipLaunchKernelGGL((deform_ts_backward_kernel<DT, 1>), grid, dim3(256), 0, s, yp, off, go, z, goff, k); break;
-        case 2: hipLaunchKernelGGL((deform_ts_backward_kernel<DT, 2>), grid, dim3(256), 0, s, yp, off, go, z, goff, k); break;
-        case 3: hipLaunchKernelGGL((deform_ts_backward_kernel<DT, 3>), grid, dim3(256), 0, s, yp, off, go, z, goff, k); break;
-        case 4: hipLaunchKernelGGL((deform_ts_backward_kernel<DT, 4>), grid, dim3(256), 0, s, yp, off, go, z, goff, k); break;
-        default: return TDRN_E_UNSUPPORTED;
-    }
-    return hip_status(hipGetLastError());
-}
+};
 
 }  // namespace
 
@@ -252,9 +197,14 @@ int launch_deform_ts_sample(const DeformBwdGeom &g, const void *y, const float *
 {
     if (g.G != 1 || g.Cout < 1 || g.Cout > 256 || !y || !off || !out_nhwc) return TDRN_E_UNSUPPORTED;
     const TsGeomK k = ts_kgeom(g);
-    if (dtype == TDRN_BF16) return sample_dt<bf16_t>(k, y, off, out_nhwc, s);
-    if (dtype == TDRN_F16) return sample_dt<f16_t>(k, y, off, out_nhwc, s);
-    return TDRN_E_UNSUPPORTED;
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        return dispatch_1to4(cdiv(k.Cout, 64), [&](auto nj) {       // NJ: columns per lane
+            hipLaunchKernelGGL((deform_ts_sample_kernel<DT, decltype(nj)::value>), dim3((unsigned)cdiv(k.M, 4)), dim3(256), 0, s, (const DT *)y, off,
+                               out_nhwc, k);
+            return hip_status(hipGetLastError());
+        });
+    });
 }
 
 int launch_deform_ts_backward(const DeformBwdGeom &g, const void *y, const float *off, const float *go_nhwc, float *z, float *goff,
@@ -263,41 +213,44 @@ int launch_deform_ts_backward(const DeformBwdGeom &g, const void *y, const float
     if (g.G != 1 || g.Cout < 1 || g.Cout > 256 || !off || !go_nhwc || (y == nullptr) != (goff == nullptr)) return TDRN_E_UNSUPPORTED;
     if (!y && !z) return TDRN_OK;
     const TsGeomK k = ts_kgeom(g);
-    if (dtype == TDRN_BF16) return backward_dt<bf16_t>(k, y, off, go_nhwc, z, goff, s);
-    if (dtype == TDRN_F16) return backward_dt<f16_t>(k, y, off, go_nhwc, z, goff, s);
-    return TDRN_E_UNSUPPORTED;
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        return dispatch_1to4(cdiv(k.Cout, 64), [&](auto nj) {       // NJ: columns per lane
+            hipLaunchKernelGGL((deform_ts_backward_kernel<DT, decltype(nj)::value>), dim3((unsigned)cdiv(k.M, 4)), dim3(256), 0, s, (const DT *)y,
+                               off, go_nhwc, z, goff, k);
+            return hip_status(hipGetLastError());
+        });
+    });
 }
 
 int launch_deform_ts_round(const float *in, void *out, long long elems, int dtype, hipStream_t s)
 {
-    if (elems % 8 || (dtype != TDRN_BF16 && dtype != TDRN_F16)) return TDRN_E_UNSUPPORTED;
+    if (elems % 8 || dtype == TDRN_F32) return TDRN_E_UNSUPPORTED;
     if (elems == 0) return TDRN_OK;
-    const dim3 grid = ts_stride_grid(elems / 8);
-    if (dtype == TDRN_BF16) hipLaunchKernelGGL((deform_ts_round_kernel<bf16_t>), grid, dim3(256), 0, s, in, (char *)out, elems / 8);
-    else hipLaunchKernelGGL((deform_ts_round_kernel<f16_t>), grid, dim3(256), 0, s, in, (char *)out, elems / 8);
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((deform_ts_round_kernel<DT>), stride_grid(elems / 8), dim3(256), 0, s, in, (char *)out, elems / 8);
+        return hip_status(hipGetLastError());
+    });
 }
 
 int launch_deform_ts_repack(const DeformBwdGeom &g, const float *w, void *out, int Npad, int dgrad, int dtype, hipStream_t s)
 {
-    if (dtype != TDRN_BF16 && dtype != TDRN_F16) return TDRN_E_UNSUPPORTED;
+    if (dtype == TDRN_F32) return TDRN_E_UNSUPPORTED;       // (16-bit types only)
     const int taps = g.kh * g.kw, Cp = deform_ts_cp(g.Cout), YC = deform_ts_cols(g);
-    const dim3 grid = ts_stride_grid((long long)Npad * (dgrad ? YC : g.Cin));
-#define L(DT, D) hipLaunchKernelGGL((deform_ts_repack_kernel<DT, D>), grid, dim3(256), 0, s, w, (char *)out, g.Cout, g.Cin, taps, Cp, YC, Npad)
-    if (dtype == TDRN_BF16) { if (dgrad) L(bf16_t, true); else L(bf16_t, false); }
-    else { if (dgrad) L(f16_t, true); else L(f16_t, false); }
-#undef L
-    return hip_status(hipGetLastError());
+    if (dgrad) return launch_pack(dtype, out, (long long)Npad * YC, TsRepackMap<true>{w, g.Cout, g.Cin, taps, Cp, YC}, s);
+    return launch_pack(dtype, out, (long long)Npad * g.Cin, TsRepackMap<false>{w, g.Cout, g.Cin, taps, Cp, g.Cin}, s);
 }
 
 int launch_deform_ts_wgrad_reduce(const DeformBwdGeom &g, const float *slab, float *grad_weight, int splits, hipStream_t s)
 {
     const int taps = g.kh * g.kw;
-    const long long total = (long long)taps * g.Cout * g.Cin;
-    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(deform_ts_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slab, grad_weight, g.Cout, g.Cin, taps,
-                       deform_ts_cp(g.Cout), deform_ts_cols(g), splits);
-    return hip_status(hipGetLastError());
+    SlabReduce r;
+    r.Cout = g.Cout; r.Cin = g.Cin; r.taps = taps;
+    r.d_co = (long long)g.Cin * taps; r.d_ci = taps; r.d_t = 1;                 // OIHW
+    r.pitch = deform_ts_cp(g.Cout); r.CiPad = g.Cin; r.sstride = (size_t)deform_ts_cols(g) * g.Cin;
+    r.bias_rows = 0; r.accumulate = false;                                       // overwrites; grad_weight is not read
+    return launch_slab_reduce(r, slab, nullptr, grad_weight, nullptr, splits, s);
 }
 
 }  // namespace tdrn

@@ -883,8 +883,7 @@ int launch_roi_resample(const float *feat, int C, int H, int W, const int32_t *c
     if (!feat || !cells || !out || C < 1 || H < 1 || W < 1 || S < 1) return TDRN_E_ARG;
     if (n <= 0) return TDRN_OK;
     const long long total = (long long)n * C * S * S;
-    dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
-    hipLaunchKernelGGL(roi_resample_kernel, grid, dim3(256), 0, s, feat, C, H, W, cells, n, S, out);
+    hipLaunchKernelGGL(roi_resample_kernel, stride_grid(total, 8192), dim3(256), 0, s, feat, C, H, W, cells, n, S, out);
     return hip_status(hipGetLastError());
 }
 

@@ -754,16 +754,11 @@ int launch_dwpw(const DwPwArgs &a, hipStream_t s)
     p.items = p.m_tiles * p.n_tiles;
     if (p.items <= 0) return TDRN_OK;
     const int grid = persistent_grid(p.items);
-#define DP_LAUNCH(DT)                                                                                        \
-    do {                                                                                                     \
-        if (tw == 0) hipLaunchKernelGGL((dwpw_kernel<DT, 0>), dim3(grid), dim3(512), 0, s, p);              \
-        else if (tw == 32) hipLaunchKernelGGL((dwpw_kernel<DT, 32>), dim3(grid), dim3(512), 0, s, p);      \
-        else hipLaunchKernelGGL((dwpw_kernel<DT, 16>), dim3(grid), dim3(512), 0, s, p);                     \
-    } while (0)
-    if (a.dtype == TDRN_BF16) DP_LAUNCH(bf16_t);
-    else DP_LAUNCH(f16_t);
-#undef DP_LAUNCH
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(a.dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((tw == 0 ? dwpw_kernel<DT, 0> : tw == 32 ? dwpw_kernel<DT, 32> : dwpw_kernel<DT, 16>), dim3(grid), dim3(512), 0, s, p);
+        return hip_status(hipGetLastError());
+    });
 }
 
 
@@ -803,9 +798,10 @@ int launch_pw1x1(const ConvArgs &a, hipStream_t s)
     p.ablate = ablate;
     p.tail_split = !(a.kdisable & KOFF_PATCH_TAIL);             // (TDRN_PLAN_NO_PATCH_TAIL)
     const int grid = persistent_grid(p.items);
-    if (a.dtype == TDRN_BF16) hipLaunchKernelGGL((pw1x1_kernel<bf16_t>), dim3(grid), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((pw1x1_kernel<f16_t>), dim3(grid), dim3(512), 0, s, p);
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(a.dtype, [&](auto tag) {
+        hipLaunchKernelGGL((pw1x1_kernel<typename decltype(tag)::type>), dim3(grid), dim3(512), 0, s, p);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

@@ -176,9 +176,10 @@ int launch_head3x3(const ConvArgs &a, hipStream_t s)
     p.tiles_per_img = (a.H * a.W + 255) / 256;
     const long long blocks = (long long)a.B * p.tiles_per_img;
     if (blocks <= 0) return TDRN_OK;
-    if (a.dtype == TDRN_BF16) hipLaunchKernelGGL((head3x3_kernel<bf16_t>), dim3((unsigned)blocks), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((head3x3_kernel<f16_t>), dim3((unsigned)blocks), dim3(512), 0, s, p);
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(a.dtype, [&](auto tag) {
+        hipLaunchKernelGGL((head3x3_kernel<typename decltype(tag)::type>), dim3((unsigned)blocks), dim3(512), 0, s, p);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn

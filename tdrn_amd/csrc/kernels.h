@@ -1,5 +1,6 @@
 // kernels.h -- launch interfaces of the HIP kernels (internal to libtdrn_hip).
 #pragma once
+#include <algorithm>
 #include <cmath>
 
 #include "common.h"
@@ -31,6 +32,27 @@ enum KernelOff {
     KOFF_TS_RANGES = 512,      // TDRN_PLAN_TS_ONE_RANGE: transform-then-sample heads take the whole batch as one range
     KOFF_PATCH_TAIL = 1024,    // TDRN_PLAN_NO_PATCH_TAIL: conv3x3_patch.hip and pw1x1_kernel run whole items only (no tail split)
 };
+
+// Launch glue of the grid-stride kernels: workgroups of 256 threads for `total` elements, at most `cap` of them
+inline dim3 stride_grid(long long total, int cap = 16384) { return dim3((unsigned)std::min<long long>((total + 255) / 256, cap)); }
+
+// The one packing kernel: out[i] = map(i) rounded once to DT, i < total.  A packer is its Map: a struct passed by value whose
+// __device__ float operator()(long long i) const holds the index map and the range test (zero outside the source).
+template <typename DT, typename Map>
+__global__ __launch_bounds__(256) void pack_kernel(char *__restrict__ out, long long total, const Map map)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        *(DT *)(out + (size_t)i * elem_traits<DT>::bytes) = from_f32<DT>(map(i));
+}
+template <typename Map> int launch_pack(int dtype, void *out, long long total, const Map &map, hipStream_t s)
+{
+    if (total <= 0) return TDRN_OK;
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((pack_kernel<DT, Map>), stride_grid(total), dim3(256), 0, s, (char *)out, total, map);
+        return hip_status(hipGetLastError());
+    });
+}
 
 // ---------------------------------------------------------------------------------------------
 // Dense convolution as implicit GEMM on MFMA (conv_igemm.hip).
@@ -279,6 +301,20 @@ int launch_conv_wgrad(const ConvBwdGeom &g, const void *x_nhwc, const void *go_n
 // for the caller's own reduce (conv_transpose.hip)
 int launch_conv_wgrad_slabs(const ConvBwdGeom &g, const void *x_nhwc, const void *go_nhwc, const void *zero_page, void *slab, int dtype,
                             hipStream_t s, int &splits, const float *&bias_slab);
+// The reduce behind the three weight gradients (conv_bwd.hip slab_reduce_kernel): the fp32 slabs [split][row t * pitch + co][CiPad],
+// `sstride` floats apart, are summed in split order into gw[co * d_co + ci * d_ci + t * d_t], co < Cout, ci < Cin, t < taps.
+// accumulate: gw += scale * sum, else gw = sum and gw is never read (scale unused).  gb (or null) += scale * the sum over the splits
+// (outer) and the bias_rows rows (inner) of bslab[split][z * pitch + co].
+struct SlabReduce {
+    int Cout = 0, Cin = 0, taps = 0;
+    long long d_co = 0, d_ci = 0, d_t = 0;
+    int pitch = 0, CiPad = 0;
+    size_t sstride = 0;
+    int bias_rows = 0;
+    float scale = 1.f;
+    bool accumulate = true;
+};
+int launch_slab_reduce(const SlabReduce &r, const float *slab, const float *bslab, float *gw, float *gb, int S, hipStream_t s);
 // OIHW fp32 -> launch_conv's packing of the input-gradient conv: out[ci][taps-1-tap][co] = w[co][ci][tap] ([Npad][taps][conv_bwd_cpad(Cout)])
 int launch_repack_oihw_dgrad(const float *w, void *out, int Cout, int Cin, int Npad, int taps, int dtype, hipStream_t s);
 // ConvTranspose2d(k = 2, s = 2) with gradients (conv_transpose.hip; tdrn_hip.h section i-f).  z = 2i + j names the kernel tap (i, j) = the

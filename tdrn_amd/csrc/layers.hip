@@ -261,28 +261,26 @@ int launch_first_conv(const float *x, const float *w, const float *bias, void *o
     if (Cpad == 64 && (stride == 1 || stride == 2)) {
         const int tiles_x = (So + 31) / 32, tiles_y = (So + 7) / 8;
         const long long n_tiles = (long long)B * tiles_x * tiles_y;
-#define LM(DT)                                                                                                              \
-    do {                                                                                                                    \
-        auto k1 = first_conv_mfma_kernel<DT, 1>;                                                                            \
-        auto k2 = first_conv_mfma_kernel<DT, 2>;                                                                            \
-        static int fit[2] = {0, 0};   /* persistent grid = what fits at once (register-limited: 3-4 workgroups per CU) */   \
-        int &per_cu = fit[stride - 1];                                                                                      \
-        if (per_cu == 0) TDRN_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stride == 1 ? k1 : k2, 256, 0)); \
-        const long long cap = 256ll * (per_cu > 0 ? per_cu : 1);                                                            \
-        dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap));                                                               \
-        if (stride == 1) hipLaunchKernelGGL(k1, grid, dim3(256), 0, s, x, w, bias, (char *)out, B, S, So, Cout, relu, tiles_x, tiles_y); \
-        else hipLaunchKernelGGL(k2, grid, dim3(256), 0, s, x, w, bias, (char *)out, B, S, So, Cout, relu, tiles_x, tiles_y);             \
-    } while (0)
-        if (dtype == TDRN_F32) LM(float); else if (dtype == TDRN_BF16) LM(bf16_t); else LM(f16_t);
-#undef LM
-        return hip_status(hipGetLastError());
+        return dispatch_dtype(dtype, [&](auto tag) {
+            using DT = typename decltype(tag)::type;
+            auto k1 = first_conv_mfma_kernel<DT, 1>;
+            auto k2 = first_conv_mfma_kernel<DT, 2>;
+            static int fit[2] = {0, 0};   // persistent grid = what fits at once (register-limited: 3-4 workgroups per CU)
+            int &per_cu = fit[stride - 1];
+            if (per_cu == 0) TDRN_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stride == 1 ? k1 : k2, 256, 0));
+            const long long cap = 256ll * (per_cu > 0 ? per_cu : 1);
+            dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap));
+            hipLaunchKernelGGL(stride == 1 ? k1 : k2, grid, dim3(256), 0, s, x, w, bias, (char *)out, B, S, So, Cout, relu, tiles_x, tiles_y);
+            return hip_status(hipGetLastError());
+        });
     }
     const long long total = (long long)B * So * So;
     dim3 grid((unsigned)((total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((first_conv_kernel<DT>), grid, dim3(256), 0, s, x, w, bias, (char *)out, B, S, So, stride, Cout, Cpad, relu)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((first_conv_kernel<DT>), grid, dim3(256), 0, s, x, w, bias, (char *)out, B, S, So, stride, Cout, Cpad, relu);
+        return hip_status(hipGetLastError());
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -328,11 +326,11 @@ int launch_maxpool2(const void *in, void *out, int B, int H, int W, int C, int c
     const int per16 = 16 / dtype_bytes(dtype);
     if (C % per16) return TDRN_E_UNSUPPORTED;
     const long long total = (long long)B * Ho * Wo * (C / per16);
-    dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((maxpool2_kernel<DT>), grid, dim3(256), 0, s, (const char *)in, (char *)out, B, H, W, Ho, Wo, C)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((maxpool2_kernel<DT>), stride_grid(total, 8192), dim3(256), 0, s, (const char *)in, (char *)out, B, H, W, Ho, Wo, C);
+        return hip_status(hipGetLastError());
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -382,10 +380,11 @@ int launch_l2norm(const void *in, const float *w, void *out, long long pixels, i
     const int per16 = 16 / dtype_bytes(dtype);
     if (C % per16 || C / per16 > 64 * 8) return TDRN_E_UNSUPPORTED;
     dim3 grid((unsigned)((pixels + 3) / 4));
-#define L(DT) hipLaunchKernelGGL((l2norm_kernel<DT>), grid, dim3(256), 0, s, (const char *)in, w, (char *)out, pixels, C)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((l2norm_kernel<DT>), grid, dim3(256), 0, s, (const char *)in, w, (char *)out, pixels, C);
+        return hip_status(hipGetLastError());
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -645,34 +644,29 @@ int launch_dwconv3(const void *in, const float *w, const float *bias, void *out,
         if (th) {
             const int nseg = (Ho + th - 1) / th;
             dim3 grid((unsigned)((per_row * nseg + 255) / 256));
-#define LD(DT)                                                                                                                          \
-    do {                                                                                                                                \
-        if (stride == 1) hipLaunchKernelGGL((dwconv3_slide_kernel<DT, 1, 4>), grid, dim3(256), 0, s, (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, relu, th, nseg); \
-        else hipLaunchKernelGGL((dwconv3_slide_kernel<DT, 2, 2>), grid, dim3(256), 0, s, (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, relu, th, nseg);             \
-    } while (0)
-            if (dtype == TDRN_F32) LD(float); else if (dtype == TDRN_BF16) LD(bf16_t); else LD(f16_t);
-#undef LD
-            return hip_status(hipGetLastError());
+            return dispatch_dtype(dtype, [&](auto tag) {
+                using DT = typename decltype(tag)::type;
+                hipLaunchKernelGGL((stride == 1 ? dwconv3_slide_kernel<DT, 1, 4> : dwconv3_slide_kernel<DT, 2, 2>), grid, dim3(256), 0, s,
+                                   (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, relu, th, nseg);
+                return hip_status(hipGetLastError());
+            });
         }
     }
     if ((stride == 1 || stride == 2) && Wo >= 4) {
         const long long total = (long long)B * Ho * ((Wo + 3) / 4) * (C / per16);
-        dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
-#define LS(DT)                                                                                                                         \
-    do {                                                                                                                               \
-        if (stride == 1) hipLaunchKernelGGL((dwconv3_strip_kernel<DT, 1>), grid, dim3(256), 0, s, (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, relu); \
-        else hipLaunchKernelGGL((dwconv3_strip_kernel<DT, 2>), grid, dim3(256), 0, s, (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, relu);             \
-    } while (0)
-        if (dtype == TDRN_F32) LS(float); else if (dtype == TDRN_BF16) LS(bf16_t); else LS(f16_t);
-#undef LS
-        return hip_status(hipGetLastError());
+        return dispatch_dtype(dtype, [&](auto tag) {
+            using DT = typename decltype(tag)::type;
+            hipLaunchKernelGGL((stride == 1 ? dwconv3_strip_kernel<DT, 1> : dwconv3_strip_kernel<DT, 2>), stride_grid(total, 8192), dim3(256), 0, s,
+                               (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, relu);
+            return hip_status(hipGetLastError());
+        });
     }
     const long long total = (long long)B * Ho * Wo * (C / per16);
-    dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((dwconv3_kernel<DT>), grid, dim3(256), 0, s, (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, stride, relu)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((dwconv3_kernel<DT>), stride_grid(total), dim3(256), 0, s, (const char *)in, w, bias, (char *)out, B, H, W, Ho, Wo, C, stride, relu);
+        return hip_status(hipGetLastError());
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -841,22 +835,18 @@ int launch_offset_conv_multi(const OffsetProblem *pr, int n, hipStream_t s)
 // layout conversions (API surfaces are NCHW fp32)
 // ---------------------------------------------------------------------------------------------
 // channel c of group g = c / cpg lands at g*cpg_pad + (c - g*cpg); pad channels are zero
-template <typename DT>
-__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float *__restrict__ in, char *__restrict__ out, int B,
-                                                           int C, int HW, int G, int cpg_pad)
-{
-    constexpr int ES = elem_traits<DT>::bytes;
-    const int Cpad = G * cpg_pad, cpg = C / G;
-    const long long total = (long long)B * HW * Cpad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+struct NchwToNhwcMap {
+    const float *in;
+    int C, HW, Cpad, cpg, cpg_pad;
+    __device__ float operator()(long long i) const
+    {
         const int cp = (int)(i % Cpad);
         const long long m = i / Cpad;
         const int b = (int)(m / HW), pix = (int)(m - (long long)b * HW);
         const int g = cp / cpg_pad, cl = cp - g * cpg_pad;
-        const float v = cl < cpg ? in[((size_t)b * C + g * cpg + cl) * HW + pix] : 0.f;
-        *(DT *)(out + (size_t)i * ES) = from_f32<DT>(v);
+        return cl < cpg ? in[((size_t)b * C + g * cpg + cl) * HW + pix] : 0.f;
     }
-}
+};
 
 int launch_nchw_to_nhwc_grouped(const float *in, void *out, int B, int C, int HW, int G, int cpg_pad, int dtype,
                                 hipStream_t s)
@@ -864,11 +854,7 @@ int launch_nchw_to_nhwc_grouped(const float *in, void *out, int B, int C, int HW
     const long long total = (long long)B * HW * G * cpg_pad;
     if (total <= 0) return TDRN_OK;
     if (G < 1 || C % G) return TDRN_E_ARG;
-    dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((nchw_to_nhwc_kernel<DT>), grid, dim3(256), 0, s, in, (char *)out, B, C, HW, G, cpg_pad)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return launch_pack(dtype, out, total, NchwToNhwcMap{in, C, HW, G * cpg_pad, C / G, cpg_pad}, s);
 }
 
 int launch_nchw_to_nhwc(const float *in, void *out, int B, int C, int HW, int Cpad, int dtype, hipStream_t s)
@@ -877,33 +863,25 @@ int launch_nchw_to_nhwc(const float *in, void *out, int B, int C, int HW, int Cp
 }
 
 // OIHW fp32 -> [Npad][tap][G*cpg_pad] DT (rows >= Cout and pad channels zero)
-template <typename DT>
-__global__ __launch_bounds__(256) void repack_oihw_kernel(const float *__restrict__ w, char *__restrict__ out, int Cout,
-                                                          int Npad, int Cin, int taps, int G, int cpg_pad)
-{
-    constexpr int ES = elem_traits<DT>::bytes;
-    const int Cpad = G * cpg_pad, cpg = Cin / G;
-    const long long total = (long long)Npad * taps * Cpad;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+struct RepackOihwMap {
+    const float *w;
+    int Cout, Cin, taps, Cpad, cpg, cpg_pad;
+    __device__ float operator()(long long i) const
+    {
         const int cp = (int)(i % Cpad);
         const long long r = i / Cpad;
         const int t = (int)(r % taps), co = (int)(r / taps);
         const int g = cp / cpg_pad, cl = cp - g * cpg_pad;
-        const float v = (co < Cout && cl < cpg) ? w[((size_t)co * Cin + g * cpg + cl) * taps + t] : 0.f;
-        *(DT *)(out + (size_t)i * ES) = from_f32<DT>(v);
+        return (co < Cout && cl < cpg) ? w[((size_t)co * Cin + g * cpg + cl) * taps + t] : 0.f;
     }
-}
+};
 
 int launch_repack_oihw(const float *w, void *out, int Cout, int Npad, int Cin, int taps, int G, int cpg_pad, int dtype,
                        hipStream_t s)
 {
     const long long total = (long long)Npad * taps * G * cpg_pad;
     if (total <= 0) return TDRN_OK;
-    dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((repack_oihw_kernel<DT>), grid, dim3(256), 0, s, w, (char *)out, Cout, Npad, Cin, taps, G, cpg_pad)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return launch_pack(dtype, out, total, RepackOihwMap{w, Cout, Cin, taps, G * cpg_pad, Cin / G, cpg_pad}, s);
 }
 
 __global__ __launch_bounds__(256) void nhwc_to_nchw_f32_kernel(const float *__restrict__ in, long long in_bs,
@@ -924,7 +902,7 @@ int launch_nhwc_to_nchw_f32(const float *in, long long in_bs, long long in_ps, f
 {
     const long long total = (long long)B * C * HW;
     if (total <= 0) return TDRN_OK;
-    dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
+    const dim3 grid = stride_grid(total, 8192);
     hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, grid, dim3(256), 0, s, in, in_bs, in_ps, out, B, C, HW);
     return hip_status(hipGetLastError());
 }
@@ -947,11 +925,11 @@ int launch_nhwc_any_to_nchw_f32(const void *in, int dtype, int Cpad, float *out,
 {
     const long long total = (long long)B * C * HW;
     if (total <= 0) return TDRN_OK;
-    dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
-#define L(DT) hipLaunchKernelGGL((nhwc_any_to_nchw_kernel<DT>), grid, dim3(256), 0, s, (const char *)in, Cpad, out, B, C, HW)
-    if (dtype == TDRN_F32) L(float); else if (dtype == TDRN_BF16) L(bf16_t); else L(f16_t);
-#undef L
-    return hip_status(hipGetLastError());
+    return dispatch_dtype(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((nhwc_any_to_nchw_kernel<DT>), stride_grid(total), dim3(256), 0, s, (const char *)in, Cpad, out, B, C, HW);
+        return hip_status(hipGetLastError());
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1002,7 +980,7 @@ int launch_preprocess(const unsigned char *in, int B, int H0, int W0, int S, con
 {
     const long long total = (long long)B * S * S;
     if (total <= 0) return TDRN_OK;
-    dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
+    const dim3 grid = stride_grid(total, 8192);
     hipLaunchKernelGGL(preprocess_kernel, grid, dim3(256), 0, s, in, B, H0, W0, S, mean_bgr[0], mean_bgr[1], mean_bgr[2], to_rgb, out);
     return hip_status(hipGetLastError());
 }
@@ -1036,7 +1014,7 @@ int launch_preprocess_u8(const unsigned char *in, int B, int H0, int W0, int S, 
 {
     const long long total = (long long)B * S * S;
     if (total <= 0) return TDRN_OK;
-    dim3 grid((unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256));
+    const dim3 grid = stride_grid(total, 8192);
     hipLaunchKernelGGL(preprocess_u8_kernel, grid, dim3(256), 0, s, in, B, H0, W0, S, to_rgb, out);
     return hip_status(hipGetLastError());
 }
@@ -1060,7 +1038,7 @@ int launch_u8_planes_to_f32(const unsigned char *in, int B, int S, const float *
     if (total <= 0) return TDRN_OK;
     if (plane % 4) return TDRN_E_UNSUPPORTED;
     const long long th = total / 4;
-    dim3 grid((unsigned)((th + 255) / 256 > 8192 ? 8192 : (th + 255) / 256));
+    const dim3 grid = stride_grid(th, 8192);
     hipLaunchKernelGGL(u8_planes_to_f32_kernel, grid, dim3(256), 0, s, in, plane, total, mean[0], mean[1], mean[2], out);
     return hip_status(hipGetLastError());
 }
@@ -1081,7 +1059,7 @@ int launch_fill_zero(void *p, size_t bytes, hipStream_t s)
     if (!p || (((uintptr_t)p | bytes) & 3)) return TDRN_E_ARG;
     const bool vec = (((uintptr_t)p | bytes) & 15) == 0;
     const size_t n = vec ? bytes / 16 : bytes / 4;
-    dim3 grid((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256));
+    const dim3 grid = stride_grid(n, 4096);
     if (vec) hipLaunchKernelGGL((fill_zero_kernel<uint4>), grid, dim3(256), 0, s, (uint4 *)p, n);
     else hipLaunchKernelGGL((fill_zero_kernel<unsigned>), grid, dim3(256), 0, s, (unsigned *)p, n);
     return hip_status(hipGetLastError());

@@ -129,35 +129,30 @@ unsigned pool_nhwc_grid(unsigned items)
 int launch_max_pool_nhwc_forward(const void *input, void *output, unsigned char *code, int N, int C, int H, int W, int Ho, int Wo, int kernel,
                                  int dtype, hipStream_t s)
 {
-    if (C % 8 || (kernel != 2 && kernel != 3) || (dtype != TDRN_BF16 && dtype != TDRN_F16)) return TDRN_E_UNSUPPORTED;
+    if (C % 8 || (kernel != 2 && kernel != 3)) return TDRN_E_UNSUPPORTED;
     const PoolNhwcGeom g{(unsigned)N, (unsigned)H, (unsigned)W, (unsigned)Ho, (unsigned)Wo, (unsigned)C / 8};
     const dim3 grid(pool_nhwc_grid(g.N * g.Ho * g.Wo * g.CG)), block(kT);
-    const char *x = (const char *)input;
-    char *y = (char *)output;
-#define TDRN_POOL_FWD(DT, K) \
-    do { \
-        if (code) hipLaunchKernelGGL((pool_nhwc_fwd_kernel<DT, K, true>), grid, block, 0, s, x, y, code, g); \
-        else hipLaunchKernelGGL((pool_nhwc_fwd_kernel<DT, K, false>), grid, block, 0, s, x, y, code, g); \
-    } while (0)
-    if (dtype == TDRN_BF16) { if (kernel == 2) TDRN_POOL_FWD(bf16_t, 2); else TDRN_POOL_FWD(bf16_t, 3); }
-    else { if (kernel == 2) TDRN_POOL_FWD(f16_t, 2); else TDRN_POOL_FWD(f16_t, 3); }
-#undef TDRN_POOL_FWD
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        auto k = kernel == 2 ? (code ? pool_nhwc_fwd_kernel<DT, 2, true> : pool_nhwc_fwd_kernel<DT, 2, false>)
+                             : (code ? pool_nhwc_fwd_kernel<DT, 3, true> : pool_nhwc_fwd_kernel<DT, 3, false>);
+        hipLaunchKernelGGL(k, grid, block, 0, s, (const char *)input, (char *)output, code, g);
+        return hip_status(hipGetLastError());
+    });
 }
 
 int launch_max_pool_nhwc_backward(const void *grad_output, const unsigned char *code, void *grad_input, int N, int C, int H, int W, int Ho,
                                   int Wo, int kernel, int dtype, hipStream_t s)
 {
-    if (C % 8 || (kernel != 2 && kernel != 3) || (dtype != TDRN_BF16 && dtype != TDRN_F16)) return TDRN_E_UNSUPPORTED;
+    if (C % 8 || (kernel != 2 && kernel != 3)) return TDRN_E_UNSUPPORTED;
     const PoolNhwcGeom g{(unsigned)N, (unsigned)H, (unsigned)W, (unsigned)Ho, (unsigned)Wo, (unsigned)C / 8};
     const dim3 grid(pool_nhwc_grid(g.N * g.H * g.W * g.CG)), block(kT);
-    const char *go = (const char *)grad_output;
-    char *gi = (char *)grad_input;
-#define TDRN_POOL_BWD(DT, K) hipLaunchKernelGGL((pool_nhwc_bwd_kernel<DT, K>), grid, block, 0, s, go, code, gi, g)
-    if (dtype == TDRN_BF16) { if (kernel == 2) TDRN_POOL_BWD(bf16_t, 2); else TDRN_POOL_BWD(bf16_t, 3); }
-    else { if (kernel == 2) TDRN_POOL_BWD(f16_t, 2); else TDRN_POOL_BWD(f16_t, 3); }
-#undef TDRN_POOL_BWD
-    return hip_status(hipGetLastError());
+    return dispatch_dtype16(dtype, [&](auto tag) {
+        using DT = typename decltype(tag)::type;
+        hipLaunchKernelGGL((kernel == 2 ? pool_nhwc_bwd_kernel<DT, 2> : pool_nhwc_bwd_kernel<DT, 3>), grid, block, 0, s,
+                           (const char *)grad_output, code, (char *)grad_input, g);
+        return hip_status(hipGetLastError());
+    });
 }
 
 }  // namespace tdrn
