@@ -14,7 +14,12 @@ and the conv3x3_pp case (conv3_2 at batch 8: 200 items, 29 GMAC) is gated on a f
 Split-K of launch_conv, by igemm_splitk_choice: fewer than 160 blocks of 128 pixels x the cout tile and nk = taps Cin / 64 >= 8 steps
 give min(ceil(384 / blocks), nk / 4, 16) slices: 9 for `splitk` (1 block, nk = 36), 2 for the 64-channel 3x3 cases, none for `k1`
 (nk = 2).  Weight-gradient K splits, by conv_wgrad_splits: min(ceil(512 / tiles), ceil(M / 256)): 2 for the 512-pixel cases, 1 below
-257 pixels."""
+257 pixels.
+
+The direct-conv cases here run one image (conv3x3_patch: 64-cout items, at most one per workgroup, no tail split) or one item per
+workgroup (conv3x3_pp: 16 x 16 tiles, bf16, one cout tile), and Cout = Npad throughout.  test_gpu_nhwc_direct.py holds the variants
+they do not reach: 128-cout items, the tail split, several items per workgroup, two cout tiles, flat and 8 x 32 tiles on
+conv3x3_pp, fp16 there, and Cout < Npad on every direct route."""
 import pytest
 import torch
 import torch.nn.functional as F
