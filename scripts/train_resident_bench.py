@@ -3,7 +3,7 @@
     python scripts/train_resident_bench.py OUT_DIR [--batches 8,32] [--reps 7] [--skip-step] [--skip-layers]
 
 Step: one forward_train + backward of dualrefinedet_vggbn at 320 px in bf16 (synthetic weights and frames, the smooth loss of
-tests/_train_net_ref.py: mean squared distance of the three outputs to fixed targets), resident=False and resident=True ALTERNATING,
+tests/_train_model_ref.py: mean squared distance of the three outputs to fixed targets), resident=False and resident=True ALTERNATING,
 each sample timed between two device events after a discarded warm-up pair; the median of `reps` samples, their spread, and
 torch.cuda.max_memory_allocated of a step of each kind (the peak statistics reset before it).
 Layers: the conv3_2 and conv4_2 forward, backward_input (dgrad) and backward_parameters (wgrad) entries of both ABIs on the same

@@ -32,7 +32,7 @@ References (float64, CPU, from the stage's recorded inputs and grad_output) and 
              same op on absolute values (_conv_train_harness.compare).
   cancelling bias gradients
              the one cancellation the net contains: the bias of a conv that feeds a training-mode BatchNorm has the gradient
-             sum(grad_output), and the BatchNorm backward makes that sum 0 exactly (_train_net_ref.bn_after_conv lists the 17).
+             sum(grad_output), and the BatchNorm backward makes that sum 0 exactly (_train_model_ref.bn_after_conv lists the 17).
              Bound C_ACC["bf16"] S with S = sum|grad_output|: 2e-6 is the project's constant for plain fp32 accumulation noise
              relative to the absolute sum, and a bias sum has no products, so it applies in every mode.
   batch_norm (fused ReLU)
@@ -373,7 +373,7 @@ def _check_conv_offset(st, shares):
 
 def check_stage(st, cancelling=()):
     """-> [(tensor, worst share of its bound)]; raises AssertionError at the first tensor outside its bound.  `cancelling`: the names
-    of the conv biases in front of a training-mode BatchNorm (_train_net_ref.bn_after_conv), empty in eval mode."""
+    of the conv biases in front of a training-mode BatchNorm (_train_model_ref.bn_after_conv), empty in eval mode."""
     shares = []
     if st.kind in CONV_TYPE:
         _check_conv(st, cancelling, shares)

@@ -7,22 +7,19 @@ tests/test_gpu_train_resident.py.
     path fills, net(x) moves after an SGD step;
   * arm_loc sits in front of the heads: it equals the default path's bit for bit;
   * the yardstick of odm_loc and conf is the existing path: their relative L2 distance to the float64 restatement
-    (tests/_train_net_ref.py) under "transform" is at most 2 x that under "gather", both computed here (the 192 px layout).  The
+    (tests/_train_model_ref.py) under "transform" is at most 2 x that under "gather", both computed here (the 192 px layout).  The
     transform rounds X and Y where the gather path rounds the sampled columns: one more rounding, sqrt(2) expected, 2 leaves room
     (as in DESIGN.md section 22); measured: odm_loc 1.2797e-1 -> 1.2798e-1, conf 1.1879e-1 -> 1.1879e-1, ratio 1.000;
     both distances are dominated by the 16-bit trunk in front of the discontinuous sampling;
   * the relative L2 difference between the two paths of the head weights' gradients and of the gradient at the ODM sources is printed,
     not gated: the op-level test (tests/test_gpu_deform_ts.py) is the gate.
 dualrefinedet_mobilenet: plumbing only.  In eval mode deform_algo="gather" and the omitted argument give equal bits."""
-import functools
-
 import pytest
 import torch
 
-import _train_net_ref as T
+import _train_model_harness as H
+import _train_model_ref as T
 from tdrn_amd.model.dualrefinedet_mobilenet import build_net as build_mobilenet
-from tdrn_amd.model.dualrefinedet_vggbn import build_net
-from tdrn_amd.optim import SGD
 from tdrn_amd.utils import synth
 
 from _conv_train_harness import DEV
@@ -33,44 +30,29 @@ torch.set_num_threads(min(16, torch.get_num_threads()))
 # layout runs at 320 px, as in tests/test_gpu_train_mobilenet.py; its float64 restatement would take several times as long and is left out
 CONFIG = {False: (192, (24, 12, 6, 3)), True: (320, (40, 20, 10, 5))}
 COMPUTE = "bf16"
+SEED, STATE_SEED, TARGET_SEED = 5, 0, 77
 
 
 def _priors(multihead):
-    return 3 * sum(f * f for f in CONFIG[multihead][1])
-
-
-def _build(multihead):
-    return build_net("train", 320, 21, 1024, 1, True, multihead)
-
-
-@functools.lru_cache(maxsize=None)
-def _state(multihead):
-    net = _build(multihead)
-    return synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
+    return H.priors_count(CONFIG[multihead][1])
 
 
 def _net(multihead):
-    net = _build(multihead)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in _state(multihead).items()})
-    return net.to(DEV)
+    return H.net(H.drn_vgg(True, multihead), STATE_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _frames(multihead=False):
-    return synth.synth_frames(1, CONFIG[multihead][0], seed=5)
+    return H.frames(1, CONFIG[multihead][0], SEED)
 
 
-@functools.lru_cache(maxsize=None)
-def _float64_outputs(multihead):
-    """the float64 restatement's training-mode forward on the CPU, computed once per head layout"""
-    params, buffers = T.split_state(_state(multihead), torch.float64)
-    with torch.no_grad():
-        return T.forward(params, buffers, torch.as_tensor(_frames()).double(), multihead, True)
+def _float64_outputs():
+    """the float64 restatement's training-mode forward of the single-head net on the CPU, computed once (and shared with
+    test_gpu_train_resident.py)"""
+    return H.forward_outputs(H.drn_vgg(True, False), STATE_SEED, SEED, CONFIG[False][0], torch.float64)
 
 
 def _targets(priors):
-    gen = torch.Generator().manual_seed(77)
-    return tuple(torch.randn(1, priors, w, generator=gen) for w in (4, 4, 21))
+    return H.targets(priors, (4, 4, 21), TARGET_SEED)
 
 
 def _keep_odm_sources(net):
@@ -96,27 +78,6 @@ def _step(net, resident, **kw):
     return out
 
 
-def _plumbing(net, out, reference_net):
-    priors = _priors(net.multihead)
-    assert len(out) == 4 and out[1] is None
-    assert tuple(out[0].shape) == (1, priors, 4) and tuple(out[2].shape) == (1, priors, 4) and tuple(out[3].shape) == (1, priors, 21)
-    assert all(o.dtype == torch.float32 and bool(torch.isfinite(o).all()) for o in (out[0], out[2], out[3]))
-    want = {n for n, p in reference_net.named_parameters() if p.grad is not None}
-    assert want
-    for n, p in net.named_parameters():
-        if n in want:
-            assert p.grad is not None and p.grad.dtype == torch.float32 and bool(torch.isfinite(p.grad).all()), n
-        else:
-            assert p.grad is None, n
-
-
-def _moves_after_a_step(net, before, x):
-    SGD(net.parameters(), lr=1e-3, momentum=0.9).step()
-    with torch.no_grad():
-        after = [t.clone() for t in net(x) if t is not None]
-    assert all(float((a - b).abs().max()) > 0 for a, b in zip(before, after))
-
-
 @pytest.mark.parametrize("resident", [False, True], ids=["nchw", "resident"])
 @pytest.mark.parametrize("multihead", [False, True], ids=["one-head", "multihead"])
 def test_transform_against_the_gather_path(multihead, resident):
@@ -129,11 +90,11 @@ def test_transform_against_the_gather_path(multihead, resident):
     src_g, src_t = _keep_odm_sources(gather), _keep_odm_sources(transform)
     out_g = _step(gather, resident)
     out_t = _step(transform, resident, deform_algo="transform")
-    _plumbing(transform, out_t, gather)
+    H.plumbing(transform, out_t, gather, _priors(multihead), counters=False, exact=True)
     assert torch.equal(out_g[0], out_t[0]), "arm_loc sits in front of the heads"
     what = "multihead=%s resident=%s %s" % (multihead, resident, COMPUTE)
     if not resident and not multihead:
-        ref = _float64_outputs(multihead)
+        ref = _float64_outputs()
         for name, i, j in (("odm_loc", 2, 1), ("conf", 3, 2)):
             d_g, d_t = rel(out_g[i], ref[j]), rel(out_t[i], ref[j])
             print("%s, %s relative L2 to float64: gather %.4e, transform %.4e (ratio %.3f)" % (what, name, d_g, d_t, d_t / d_g))
@@ -148,7 +109,7 @@ def test_transform_against_the_gather_path(multihead, resident):
     assert len(src_g) == len(src_t) == 4
     print("%s, gradient at the ODM sources transform vs gather, relative L2: %s"
           % (what, " ".join("%.3e" % rel(a.grad, b.grad) for a, b in zip(src_t, src_g))))
-    _moves_after_a_step(transform, before, x)
+    H.moves_after_a_step(transform, before, x)
 
 
 def test_mobilenet_plumbing():
@@ -164,9 +125,9 @@ def test_mobilenet_plumbing():
         before = [t.clone() for t in transform(x) if t is not None]
     out_g = _step(gather, False)
     out_t = _step(transform, False, deform_algo="transform")
-    _plumbing(transform, out_t, gather)                # the same four maps at 192 px: 24, 12, 6, 3
+    H.plumbing(transform, out_t, gather, _priors(False), counters=False, exact=True)       # the same four maps at 192 px: 24, 12, 6, 3
     assert torch.equal(out_g[0], out_t[0])
-    _moves_after_a_step(transform, before, x)
+    H.moves_after_a_step(transform, before, x)
 
 
 def test_gather_is_the_default_bit_for_bit():

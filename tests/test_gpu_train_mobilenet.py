@@ -3,8 +3,8 @@ through the library's differentiable ops (the depthwise 3x3 conv of conv_dw amon
 
 References.  Eval mode: oracle.net_ref.drn_mobilenet_forward(phase='train') with test_gpu_net.py's rule (atol 1e-3; behind the
 deformable heads every prior row but those net_ref.border_rows finds on a sampling discontinuity, at most 30 of them; the oracle
-alone gives 0 such rows at this input).  Training mode: tests/_train_mobilenet_ref.py, the same walk on torch's functional ops with
-F.batch_norm(training=True), on the CPU in float64.
+alone gives 0 such rows at this input).  Training mode: drn_forward of tests/_train_model_ref.py, the same walk on torch's functional
+ops with F.batch_norm(training=True), on the CPU in float64.  Fixtures and checks: tests/_train_model_harness.py.
 
 Inputs: test_gpu_train_net.py's (single head 192 px, pyramid 24 / 12 / 6 / 3, P = 2295; multihead 320 px).  The float64 tests run
 ONE image of frame seed 4; eval mode and the drop-in step run two of frame seed 5.
@@ -18,63 +18,54 @@ gives errors >= 0.1.  The sharp gate is tests/test_gpu_train_stages_mobilenet.py
 BatchNorm (extras.0.0.bias, extras.1.0.bias) have a float64 gradient of 1e-17: they are judged by |g| <= 2e-6 sum|grad_output| of
 their conv, per channel, as tests/_train_stage_ref.py judges a cancelling sum.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
-import _train_mobilenet_ref as T
+import _train_model_harness as H
+import _train_model_ref as T
 from oracle import net_ref
-from tdrn_amd.data import mb_cfg
-from tdrn_amd.layers import PriorBox, RefineMultiBoxLoss
+from tdrn_amd.layers import RefineMultiBoxLoss
 from tdrn_amd.model.dualrefinedet_mobilenet import build_net
 from tdrn_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = H.DEV
 torch.set_num_threads(min(16, torch.get_num_threads()))
 
 CONFIG = {False: (192, (24, 12, 6, 3)), True: (320, (40, 20, 10, 5))}
 LR, STEPS = 0.01, 3
 SEED64, SEED = 4, 5            # frame seeds: the float64 tests' one image; eval mode's and the drop-in step's two
+STATE_SEED, TARGET_SEED = 0, 77
+CAP = 0.1                      # on 10 x yardstick, strict (header)
 IDS = {False: "singlehead", True: "multihead"}
 MH = pytest.mark.parametrize("mh", [False, True], ids=lambda v: IDS[v])
 
 
 def _priors_count(mh):
-    return 3 * sum(f * f for f in CONFIG[mh][1])
+    return H.priors_count(CONFIG[mh][1])
 
 
-@functools.lru_cache(maxsize=None)
 def _state(mh):
-    net = build_net("train", 320, 21, 1, mh)
-    return synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
+    return H.state(H.drn_mobilenet(mh), STATE_SEED)
 
 
 def _net(mh):
-    """a fresh module with the synthetic weights, in training mode as build_net leaves it"""
-    net = build_net("train", 320, 21, 1, mh)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in _state(mh).items()})
-    return net.to(DEV)
+    return H.net(H.drn_mobilenet(mh), STATE_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _frames(mh, B, seed):
-    return synth.synth_frames(B, CONFIG[mh][0], seed=seed)
+    return H.frames(B, CONFIG[mh][0], seed)
 
 
-@functools.lru_cache(maxsize=None)
 def _targets(mh):
-    gen = torch.Generator().manual_seed(77)
-    return tuple(torch.randn(1, _priors_count(mh), w, generator=gen) for w in (4, 4, 21))
+    return H.targets(_priors_count(mh), (4, 4, 21), TARGET_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _reference(mh, dtype):
     """the restatement's SGD run on the CPU, computed once and never changed: STEPS steps for the single-head net (its first step
     serves the forward and gradient tests), one step for the other"""
-    return T.sgd_run(_state(mh), _frames(mh, 1, SEED64), _targets(mh), mh, dtype, 1 if mh else STEPS, LR)
+    return H.reference(H.drn_mobilenet(mh), STATE_SEED, SEED64, *CONFIG[mh], TARGET_SEED, dtype, 1 if mh else STEPS, LR, True)
 
 
 def _ours(net, mh, compute="fp32"):
@@ -83,22 +74,10 @@ def _ours(net, mh, compute="fp32"):
     return out, T.smooth_loss((out[0], out[2], out[3]), _targets(mh))
 
 
-def _buffers(net):
-    return {k: v.detach().clone() for k, v in net.state_dict().items() if "running_" in k or k.endswith("num_batches_tracked")}
-
-
-def _rows_off(got, ref, allowed, atol=1e-3):
-    """test_gpu_net.py's rule for outputs behind the deformable heads: (rows over atol that are on no discontinuity, max |d| elsewhere)"""
-    d = (got.detach().cpu().double() - ref.double()).abs().reshape(-1, got.shape[-1]).numpy()
-    bad = (d > atol).any(1)
-    assert int(allowed.sum()) <= 30, "suspiciously many pixels on a discontinuity: %d rows" % int(allowed.sum())
-    return int((bad & ~allowed).sum()), float(d[~bad].max())
-
-
 @MH
 def test_eval_mode_matches_the_oracle(mh):
     net = _net(mh).eval()
-    before = _buffers(net)
+    before = H.buffers(net)
     assert len(before) == 3 * 33
     x = _frames(mh, 2, SEED)
     with torch.no_grad():
@@ -110,11 +89,11 @@ def test_eval_mode_matches_the_oracle(mh):
     r_arm, _, r_odm, r_conf = net_ref.drn_mobilenet_forward(_state(mh), x, 21, mh, phase="train", taps=taps)
     allowed = net_ref.border_rows(taps, mh)
     d_arm = float((out[0].cpu() - r_arm).abs().max())
-    bad_odm, d_odm = _rows_off(out[2], r_odm, allowed)
-    bad_conf, d_conf = _rows_off(out[3], r_conf, allowed)
+    bad_odm, d_odm = H.rows_off(out[2], r_odm, allowed, 1e-3)
+    bad_conf, d_conf = H.rows_off(out[3], r_conf, allowed, 1e-3)
     print("eval %s: max|d| arm %.3e odm %.3e conf %.3e (atol 1e-3), rows on a discontinuity %d" % (IDS[mh], d_arm, d_odm, d_conf, int(allowed.sum())))
     assert d_arm <= 1e-3 and bad_odm == 0 and bad_conf == 0
-    after = _buffers(net)
+    after = H.buffers(net)
     assert all(torch.equal(before[k], after[k]) for k in before), "eval mode changed a running buffer"
     # with an autograd graph when asked for one, in eval mode too
     out = net.forward_train(torch.from_numpy(x).to(DEV))
@@ -130,20 +109,11 @@ def test_train_mode_forward_and_running_statistics(mh):
     ref = _reference(mh, torch.float64)[0][0]
     allowed = net_ref.border_rows(ref["taps"], mh)
     d_arm = float((out[0].cpu().double() - ref["outs"][0]).abs().max())
-    bad_odm, d_odm = _rows_off(out[2], ref["outs"][1], allowed)
-    bad_conf, d_conf = _rows_off(out[3], ref["outs"][2], allowed)
+    bad_odm, d_odm = H.rows_off(out[2], ref["outs"][1], allowed, 1e-3)
+    bad_conf, d_conf = H.rows_off(out[3], ref["outs"][2], allowed, 1e-3)
     print("train %s: max|d| arm %.3e odm %.3e conf %.3e (atol 1e-3), rows on a discontinuity %d" % (IDS[mh], d_arm, d_odm, d_conf, int(allowed.sum())))
     assert out[1] is None and d_arm <= 1e-3 and bad_odm == 0 and bad_conf == 0
-    worst = 0.0
-    for k, v in _buffers(net).items():
-        r = ref["buffers"][k]
-        if k.endswith("num_batches_tracked"):
-            assert int(v) == 1 and int(r) == 1, k
-            continue
-        d, bound = float((v.cpu().double() - r).abs().max()), 1e-4 * max(1.0, float(r.abs().max()))
-        worst = max(worst, d / bound)
-        assert d <= bound, (k, d, bound)
-    print("train %s: running statistics, worst |d| / bound %.3e" % (IDS[mh], worst))
+    H.running_statistics_check(IDS[mh], H.buffers(net), ref["buffers"])
 
 
 def test_train_mode_gradients():
@@ -153,29 +123,10 @@ def test_train_mode_gradients():
     loss.backward()
     ref = _reference(mh, torch.float64)[0][0]
     yard = _reference(mh, torch.float32)[0][0]
-    grads = dict(net.named_parameters())
-    assert set(grads) == set(ref["grads"]) and set(T.CANCELLING) <= set(grads)
+    grads = {n: p.grad for n, p in net.named_parameters()}
+    assert set(grads) == set(ref["grads"]) and set(T.CANCELLING) <= set(grads) and set(ref["abs_go"]) == set(T.CANCELLING)
     assert abs(float(loss.detach()) - ref["loss"]) <= 1e-4 * max(1.0, abs(ref["loss"]))
-    rel = lambda g, r: float((g.double() - r).norm() / r.norm())
-    names = [n for n in ref["grads"] if n not in T.CANCELLING]
-    yardstick = {n: rel(yard["grads"][n], ref["grads"][n]) for n in names}
-    ours = {}
-    for n in names:
-        assert grads[n].grad is not None and bool(torch.isfinite(grads[n].grad).all()), n
-        ours[n] = rel(grads[n].grad.cpu(), ref["grads"][n])
-    y_name, o_name = max(yardstick, key=yardstick.get), max(ours, key=ours.get)
-    bound = 10 * yardstick[y_name]
-    print("gradients: ours worst %.3e (%s), float32 yardstick worst %.3e (%s), bound %.3e"
-          % (ours[o_name], o_name, yardstick[y_name], y_name, bound))
-    assert bound < 0.1, "uninformative: the float32 yardstick itself is at %.3e; change the input, not the factor" % yardstick[y_name]
-    bad = {n: v for n, v in ours.items() if not v <= bound}
-    assert not bad, bad
-    # the two cancelling biases: the batch mean removes the bias, what is left is the fp32 noise of a sum of grad_output
-    for n in T.CANCELLING:
-        g, s = grads[n].grad.cpu().double().abs(), ref["abs_go"][n]
-        assert float(ref["grads"][n].abs().max()) <= 1e-12, n
-        print("gradients: %s worst |g| / (2e-6 sum|grad_output|) %.3e" % (n, float((g / (2e-6 * s)).max())))
-        assert bool((g <= 2e-6 * s).all()), (n, float((g / (2e-6 * s)).max()))
+    H.gradient_check("", grads, ref, [yard], (), CAP, False, H.AbsGoRule(T.CANCELLING, each=True))
 
 
 def test_short_sgd_run_follows_float64():
@@ -183,31 +134,10 @@ def test_short_sgd_run_follows_float64():
     the losses fall, in ours and in float64, and ours stays within 10 x the float32 yardstick's own distance from float64 at every
     step (floor: 1e-5 of the loss, the float32 evaluation of its three means)."""
     mh = False
-    net = _net(mh)
     want = [l["loss"] for l in _reference(mh, torch.float64)[0]]
     yard = [l["loss"] for l in _reference(mh, torch.float32)[0]]
-    losses = []
-    for _ in range(STEPS):
-        net.zero_grad()
-        _, loss = _ours(net, mh)
-        loss.backward()
-        losses.append(float(loss.detach()))
-        with torch.no_grad():
-            for p in net.parameters():
-                p -= LR * p.grad
-    print("short run: losses ours %r, float64 %r, float32 yardstick %r" % (losses, want, yard))
-    assert len(want) == len(yard) == STEPS
-    assert all(b < a for a, b in zip(want, want[1:])) and all(b < a for a, b in zip(losses, losses[1:]))
-    for k, (a, b, y) in enumerate(zip(losses, want, yard)):
-        bound = max(10 * abs(y - b), 1e-5 * max(1.0, abs(b)))
-        print("short run: step %d |ours - float64| %.3e, yardstick %.3e, bound %.3e" % (k, abs(a - b), abs(y - b), bound))
-        assert abs(a - b) <= bound, (k, a, b, bound)
-
-
-def _priors(mh):
-    S, maps = CONFIG[mh]
-    cfg = dict(mb_cfg["VOC_320"], min_dim=S, feature_maps=list(maps), name="VOC_%d" % S)
-    return PriorBox(cfg).forward().to(DEV)
+    losses = H.short_run(_net(mh), lambda net: _ours(net, mh)[1], STEPS, LR)
+    H.short_run_check(losses, want, yard, STEPS)
 
 
 def _drop_in_step(net, mh, compute, targets, priors, opt):
@@ -229,32 +159,15 @@ def test_drop_in_training_step(mh):
     import _loss_ref as R
     B = 2
     net = _net(mh)
-    priors = _priors(mh)
-    assert priors.shape[0] == _priors_count(mh)
+    priors = H.priors(*CONFIG[mh])
     targets = [torch.from_numpy(np.ascontiguousarray(t)).to(DEV) for t in R.synth_targets(synth._rng("train_net_dropin", 0), B, 3, 20, 21)]
     x = torch.from_numpy(_frames(mh, B, SEED)).to(DEV)
-    with torch.no_grad():
-        before = [t.clone() for t in net(x) if t is not None]
-    opt = torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9)
-    out32, losses = _drop_in_step(net, mh, "fp32", targets, priors, opt)
-    assert all(np.isfinite(l) for l in losses), losses
-    for n, p in net.named_parameters():
-        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), n
-    opt.step()
-    with torch.no_grad():
-        after = [t.clone() for t in net(x) if t is not None]
-    # the engine re-packed by itself: no repack() call between the step and net(x)
-    assert all(float((a - b).abs().max()) > 0 for a, b in zip(before, after))
-    # the 16-bit compute types: the same pass is finite; their drift against fp32 is reported, not gated
+    step = lambda n, compute, opt: _drop_in_step(n, mh, compute, targets, priors, opt)
+    H.drop_in_fp32(net, lambda n: n(x), step, torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9))
     with torch.no_grad():
         ref = _net(mh).forward_train(x)
-    for compute in ("bf16", "fp16"):
-        fresh = _net(mh)
-        out, losses = _drop_in_step(fresh, mh, compute, targets, priors, torch.optim.SGD(fresh.parameters(), lr=1e-3))
-        assert all(np.isfinite(l) for l in losses), (compute, losses)
-        assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in fresh.parameters()), compute
-        print("drop-in %s %s: losses %r, output drift against fp32: arm %.3e odm %.3e conf %.3e" % (
-            IDS[mh], compute, losses, *(float((a.detach() - b.detach()).abs().max()) for a, b in zip((out[0], out[2], out[3]), (ref[0], ref[2], ref[3])))))
+    H.drop_in_16bit(lambda: _net(mh), step, ref, lambda compute, losses, drift: print(
+        "drop-in %s %s: losses %r, output drift against fp32: arm %.3e odm %.3e conf %.3e" % (IDS[mh], compute, losses, *drift)))
 
 
 def test_cpu_input_raises_and_the_engine_is_left_alone():

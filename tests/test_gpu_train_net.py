@@ -3,8 +3,8 @@ the library's differentiable ops, so that loss.backward() fills their .grad.
 
 References.  Eval mode: oracle.net_ref.drn_vggbn_forward(phase='train') with test_gpu_net.py's tolerance for this model's fp32
 outputs (arm_loc: atol 1e-3; odm_loc / conf, behind the deformable heads: atol 1e-3 on every prior row but those net_ref.border_rows
-finds on a sampling discontinuity).  Training mode: tests/_train_net_ref.py, the same walk on torch's functional ops with
-F.batch_norm(training=True), on the CPU in float64.
+finds on a sampling discontinuity).  Training mode: drn_forward of tests/_train_model_ref.py, the same walk on torch's functional ops
+with F.batch_norm(training=True), on the CPU in float64.  Fixtures and checks: tests/_train_model_harness.py.
 
 Inputs.  The deformable heads keep the reference's shape check (a map no smaller than the kernel), which the oracle and the library
 both enforce: the 3x3 heads need a last pyramid level of 3 x 3 (192 px), the 5x5 heads of `multihead` one of 5 x 5 (320 px).  A
@@ -18,66 +18,57 @@ Gradients are compared per tensor by relative L2 against float64, never elementw
 decision, which shifts all upstream gradients by a small discrete amount.  The yardstick is the same restatement evaluated by torch in
 float32 on the CPU; the bound for every tensor is 10 x the yardstick's worst tensor (two correct fp32 implementations differ in
 summation order and in which decisions flip, so a per-tensor ratio is noise), and a bound above 5e-2 fails the test as uninformative:
-wiring mistakes (a wrong source, a missing ReLU, a wrong BN mode) give errors >= 0.1.
+wiring mistakes (a wrong source, a missing ReLU, a wrong BN mode) give errors >= 0.1.  A conv that feeds a training-mode BatchNorm
+has an exactly zero bias gradient (the batch mean removes the bias): the 17 such biases are judged by |g| <= 1e-4 max(1, |g(bn.bias)|).
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
-import _train_net_ref as T
+import _train_model_harness as H
+import _train_model_ref as T
 from oracle import net_ref
-from tdrn_amd.data import mb_cfg
-from tdrn_amd.layers import PriorBox, RefineMultiBoxLoss
+from tdrn_amd.layers import RefineMultiBoxLoss
 from tdrn_amd.model.dualrefinedet_vggbn import build_net
 from tdrn_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = H.DEV
 torch.set_num_threads(min(16, torch.get_num_threads()))
 
 # multihead -> (input size, pyramid maps): the smallest input whose last level holds the largest head kernel
 CONFIG = {False: (192, (24, 12, 6, 3)), True: (320, (40, 20, 10, 5))}
 LR, STEPS = 0.01, 3
+SEED, STATE_SEED, TARGET_SEED = 5, 0, 77
+CAP = 5e-2                             # on 10 x yardstick, inclusive (header)
 IDS = {False: "singlehead", True: "multihead"}
 MH = pytest.mark.parametrize("mh", [False, True], ids=lambda v: IDS[v])
 
 
 def _priors_count(mh):
-    return 3 * sum(f * f for f in CONFIG[mh][1])
+    return H.priors_count(CONFIG[mh][1])
 
 
-@functools.lru_cache(maxsize=None)
 def _state(mh):
-    net = build_net("train", 320, 21, 1024, 1, True, mh)
-    return synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
+    return H.state(H.drn_vgg(True, mh), STATE_SEED)
 
 
 def _net(mh):
-    """a fresh module with the synthetic weights, in training mode as build_net leaves it"""
-    net = build_net("train", 320, 21, 1024, 1, True, mh)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in _state(mh).items()})
-    return net.to(DEV)
+    return H.net(H.drn_vgg(True, mh), STATE_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _frames(mh, B=1):
-    return synth.synth_frames(B, CONFIG[mh][0], seed=5)
+    return H.frames(B, CONFIG[mh][0], SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _targets(mh):
-    gen = torch.Generator().manual_seed(77)
-    return tuple(torch.randn(1, _priors_count(mh), w, generator=gen) for w in (4, 4, 21))
+    return H.targets(_priors_count(mh), (4, 4, 21), TARGET_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _reference(mh, dtype):
     """the restatement's SGD run on the CPU, computed once and never changed: STEPS steps for the single-head net (the short run;
     its first step serves the forward and gradient tests), one step for the other"""
-    steps = 1 if mh else STEPS
-    return T.sgd_run(_state(mh), _frames(mh), _targets(mh), mh, dtype, steps, LR)
+    return H.reference(H.drn_vgg(True, mh), STATE_SEED, SEED, *CONFIG[mh], TARGET_SEED, dtype, 1 if mh else STEPS, LR, True)
 
 
 def _ours(net, mh, compute="fp32"):
@@ -87,22 +78,10 @@ def _ours(net, mh, compute="fp32"):
     return out, loss
 
 
-def _buffers(net):
-    return {k: v.detach().clone() for k, v in net.state_dict().items() if "running_" in k or k.endswith("num_batches_tracked")}
-
-
-def _rows_off(got, ref, allowed, atol=1e-3):
-    """test_gpu_net.py's rule for outputs behind the deformable heads: (rows over atol that are on no discontinuity, max |d| elsewhere)"""
-    d = (got.detach().cpu().double() - ref.double()).abs().reshape(-1, got.shape[-1]).numpy()
-    bad = (d > atol).any(1)
-    assert int(allowed.sum()) <= 30, "suspiciously many pixels on a discontinuity: %d rows" % int(allowed.sum())
-    return int((bad & ~allowed).sum()), float(d[~bad].max())
-
-
 @MH
 def test_eval_mode_matches_the_oracle(mh):
     net = _net(mh).eval()
-    before = _buffers(net)
+    before = H.buffers(net)
     x = _frames(mh, 2)
     with torch.no_grad():
         out = net.forward_train(torch.from_numpy(x).to(DEV))
@@ -113,11 +92,11 @@ def test_eval_mode_matches_the_oracle(mh):
     r_arm, _, r_odm, r_conf = net_ref.drn_vggbn_forward(_state(mh), x, 21, True, mh, phase="train", taps=taps)
     allowed = net_ref.border_rows(taps, mh)
     d_arm = float((out[0].cpu() - r_arm).abs().max())
-    bad_odm, d_odm = _rows_off(out[2], r_odm, allowed)
-    bad_conf, d_conf = _rows_off(out[3], r_conf, allowed)
+    bad_odm, d_odm = H.rows_off(out[2], r_odm, allowed, 1e-3)
+    bad_conf, d_conf = H.rows_off(out[3], r_conf, allowed, 1e-3)
     print("eval %s: max|d| arm %.3e odm %.3e conf %.3e (atol 1e-3), rows on a discontinuity %d" % (IDS[mh], d_arm, d_odm, d_conf, int(allowed.sum())))
     assert d_arm <= 1e-3 and bad_odm == 0 and bad_conf == 0
-    after = _buffers(net)
+    after = H.buffers(net)
     assert all(torch.equal(before[k], after[k]) for k in before), "eval mode changed a running buffer"
     # with an autograd graph when asked for one, in eval mode too
     out = net.forward_train(torch.from_numpy(x).to(DEV))
@@ -134,20 +113,11 @@ def test_train_mode_forward_and_running_statistics(mh):
     ref = log[0]
     allowed = net_ref.border_rows(ref["taps"], mh)
     d_arm = float((out[0].cpu().double() - ref["outs"][0]).abs().max())
-    bad_odm, d_odm = _rows_off(out[2], ref["outs"][1], allowed)
-    bad_conf, d_conf = _rows_off(out[3], ref["outs"][2], allowed)
+    bad_odm, d_odm = H.rows_off(out[2], ref["outs"][1], allowed, 1e-3)
+    bad_conf, d_conf = H.rows_off(out[3], ref["outs"][2], allowed, 1e-3)
     print("train %s: max|d| arm %.3e odm %.3e conf %.3e (atol 1e-3), rows on a discontinuity %d" % (IDS[mh], d_arm, d_odm, d_conf, int(allowed.sum())))
     assert out[1] is None and d_arm <= 1e-3 and bad_odm == 0 and bad_conf == 0
-    worst = 0.0
-    for k, v in _buffers(net).items():
-        r = ref["buffers"][k]
-        if k.endswith("num_batches_tracked"):
-            assert int(v) == 1 and int(r) == 1, k
-            continue
-        d, bound = float((v.cpu().double() - r).abs().max()), 1e-4 * max(1.0, float(r.abs().max()))
-        worst = max(worst, d / bound)
-        assert d <= bound, (k, d, bound)
-    print("train %s: running statistics, worst |d| / bound %.3e" % (IDS[mh], worst))
+    H.running_statistics_check(IDS[mh], H.buffers(net), ref["buffers"])
 
 
 @MH
@@ -159,30 +129,10 @@ def test_train_mode_gradients(mh):
     yard = _reference(mh, torch.float32)[0][0]
     zero_bias = T.bn_after_conv(_state(mh).keys())
     assert len(zero_bias) == 17
-    grads = dict(net.named_parameters())
+    grads = {n: p.grad for n, p in net.named_parameters()}
     assert set(grads) == set(ref["grads"])
     assert abs(float(loss.detach()) - ref["loss"]) <= 1e-4 * max(1.0, abs(ref["loss"]))
-    rel = lambda g, r: float((g.double() - r).norm() / r.norm())
-    names = [n for n in ref["grads"] if n not in zero_bias]
-    yardstick = {n: rel(yard["grads"][n], ref["grads"][n]) for n in names}
-    ours = {}
-    for n in names:
-        assert grads[n].grad is not None and bool(torch.isfinite(grads[n].grad).all()), n
-        ours[n] = rel(grads[n].grad.cpu(), ref["grads"][n])
-    y_name, o_name = max(yardstick, key=yardstick.get), max(ours, key=ours.get)
-    bound = 10 * yardstick[y_name]
-    print("gradients %s: ours worst %.3e (%s), float32 yardstick worst %.3e (%s), bound %.3e"
-          % (IDS[mh], ours[o_name], o_name, yardstick[y_name], y_name, bound))
-    assert bound <= 5e-2, "uninformative: the float32 yardstick itself is at %.3e" % yardstick[y_name]
-    bad = {n: v for n, v in ours.items() if not v <= bound}
-    assert not bad, bad
-    # a conv that feeds a training-mode BatchNorm has an exactly zero bias gradient: the batch mean removes the bias
-    worst = 0.0
-    for n, bn in zero_bias.items():
-        g, scale = float(grads[n].grad.abs().max()), max(1.0, float(ref["grads"][bn + ".bias"].abs().max()))
-        worst = max(worst, g / scale)
-        assert g <= 1e-4 * scale, (n, g, scale)
-    print("gradients %s: zero-gradient biases, worst |g| / max(1, |g(bn.bias)|) %.3e (bound 1e-4)" % (IDS[mh], worst))
+    H.gradient_check(IDS[mh], grads, ref, [yard], (), CAP, True, H.BnBiasRule(zero_bias))
 
 
 def test_short_sgd_run_follows_float64():
@@ -194,31 +144,10 @@ def test_short_sgd_run_follows_float64():
     and in float64, and ours stays within 10 x the float32 yardstick's own distance from float64 at every step (floor: 1e-5 of the
     loss, the float32 evaluation of its three means)."""
     mh = False
-    net = _net(mh)
     want = [l["loss"] for l in _reference(mh, torch.float64)[0]]
     yard = [l["loss"] for l in _reference(mh, torch.float32)[0]]
-    losses = []
-    for _ in range(STEPS):
-        net.zero_grad()
-        _, loss = _ours(net, mh)
-        loss.backward()
-        losses.append(float(loss.detach()))
-        with torch.no_grad():
-            for p in net.parameters():
-                p -= LR * p.grad
-    print("short run: losses ours %r, float64 %r, float32 yardstick %r" % (losses, want, yard))
-    assert len(want) == len(yard) == STEPS
-    assert all(b < a for a, b in zip(want, want[1:])) and all(b < a for a, b in zip(losses, losses[1:]))
-    for k, (a, b, y) in enumerate(zip(losses, want, yard)):
-        bound = max(10 * abs(y - b), 1e-5 * max(1.0, abs(b)))
-        print("short run: step %d |ours - float64| %.3e, yardstick %.3e, bound %.3e" % (k, abs(a - b), abs(y - b), bound))
-        assert abs(a - b) <= bound, (k, a, b, bound)
-
-
-def _priors(mh):
-    S, maps = CONFIG[mh]
-    cfg = dict(mb_cfg["VOC_320"], min_dim=S, feature_maps=list(maps), name="VOC_%d" % S)
-    return PriorBox(cfg).forward().to(DEV)
+    losses = H.short_run(_net(mh), lambda net: _ours(net, mh)[1], STEPS, LR)
+    H.short_run_check(losses, want, yard, STEPS)
 
 
 def _drop_in_step(net, mh, compute, targets, priors, opt):
@@ -240,32 +169,15 @@ def test_drop_in_training_step(mh):
     import _loss_ref as R
     B = 2
     net = _net(mh)
-    priors = _priors(mh)
-    assert priors.shape[0] == _priors_count(mh)
+    priors = H.priors(*CONFIG[mh])
     targets = [torch.from_numpy(np.ascontiguousarray(t)).to(DEV) for t in R.synth_targets(synth._rng("train_net_dropin", 0), B, 3, 20, 21)]
     x = torch.from_numpy(_frames(mh, B)).to(DEV)
-    with torch.no_grad():
-        before = [t.clone() for t in net(x) if t is not None]
-    opt = torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9)
-    out32, losses = _drop_in_step(net, mh, "fp32", targets, priors, opt)
-    assert all(np.isfinite(l) for l in losses), losses
-    for n, p in net.named_parameters():
-        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), n
-    opt.step()
-    with torch.no_grad():
-        after = [t.clone() for t in net(x) if t is not None]
-    # the engine re-packed by itself: no repack() call between the step and net(x)
-    assert all(float((a - b).abs().max()) > 0 for a, b in zip(before, after))
-    # the 16-bit compute types: the same pass is finite; their drift against fp32 is reported, not gated
+    step = lambda n, compute, opt: _drop_in_step(n, mh, compute, targets, priors, opt)
+    H.drop_in_fp32(net, lambda n: n(x), step, torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9))
     with torch.no_grad():
         ref = _net(mh).forward_train(x)
-    for compute in ("bf16", "fp16"):
-        fresh = _net(mh)
-        out, losses = _drop_in_step(fresh, mh, compute, targets, priors, torch.optim.SGD(fresh.parameters(), lr=1e-3))
-        assert all(np.isfinite(l) for l in losses), (compute, losses)
-        assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in fresh.parameters()), compute
-        print("drop-in %s %s: losses %r, output drift against fp32: arm %.3e odm %.3e conf %.3e" % (
-            IDS[mh], compute, losses, *(float((a.detach() - b.detach()).abs().max()) for a, b in zip((out[0], out[2], out[3]), (ref[0], ref[2], ref[3])))))
+    H.drop_in_16bit(lambda: _net(mh), step, ref, lambda compute, losses, drift: print(
+        "drop-in %s %s: losses %r, output drift against fp32: arm %.3e odm %.3e conf %.3e" % (IDS[mh], compute, losses, *drift)))
 
 
 def test_cpu_input_raises_and_the_engine_is_left_alone():

@@ -2,9 +2,9 @@
 by entry through the C ABI, bit for bit; forward_train(x, compute, resident=True) of dualrefinedet_vggbn; and one captured training
 step.
 
-Net test.  The yardstick is the existing path, not the code under test: with the float64 restatement of tests/_train_net_ref.py, the
-relative L2 distance of arm_loc to float64 under resident=True is at most 2 x that of resident=False at the same compute type, both
-computed here, with BatchNorm and without (tests/_train_resident_ref.py restates the part of the net in front of the heads for both).
+Net test.  The yardstick is the existing path, not the code under test: with the float64 restatement of tests/_train_model_ref.py,
+the relative L2 distance of arm_loc to float64 under resident=True is at most 2 x that of resident=False at the same compute type, both
+computed here, with BatchNorm and without (that module's arm_loc restates the part of the net in front of the heads for both).
 Why 2: the resident path rounds twice per layer (the conv output and the BatchNorm output) where the existing path
 rounds once (the conv's input); two independent errors of equal size give sqrt(2), and 2 leaves room.  arm_loc is gated because it sits
 in front of the discontinuous deformable sampling; odm_loc and conf, behind it, are printed.  Frame seed 5 at 192 px: the test
@@ -17,14 +17,12 @@ import numpy as np
 import pytest
 import torch
 
-import _train_net_ref as T
-import _train_resident_ref as R
-from tdrn_amd.data import mb_cfg
-from tdrn_amd.layers import PriorBox, RefineMultiBoxLoss
+import _train_model_harness as H
+import _train_model_ref as T
+from tdrn_amd.layers import RefineMultiBoxLoss
 from tdrn_amd.layers.box_utils import PackedTargets
 from tdrn_amd.model import networks
 from tdrn_amd.model.dualrefinedet_mobilenet import build_net as build_mobilenet
-from tdrn_amd.model.dualrefinedet_vggbn import build_net
 from tdrn_amd.optim import SGD
 from tdrn_amd.utils import synth
 
@@ -34,7 +32,8 @@ from _nhwc_harness import (ConvAbi, TYPES, bn_backward, bn_forward, exact, pool_
 pytestmark = pytest.mark.gpu
 torch.set_num_threads(min(16, torch.get_num_threads()))
 SIZE, MAPS = 192, (24, 12, 6, 3)
-PRIORS = 3 * sum(f * f for f in MAPS)
+PRIORS = H.priors_count(MAPS)
+SEED, STATE_SEED, TARGET_SEED = 5, 0, 77
 
 
 # ---- chain ---------------------------------------------------------------------------------------------------------------------------
@@ -98,34 +97,25 @@ def test_chain_python_ops_equal_the_entries_bit_for_bit():
 
 
 # ---- net -----------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
 def _state(bn):
-    net = build_net("train", 320, 21, 1024, 1, bn, False)
-    return synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
+    return H.state(H.drn_vgg(bn, False), STATE_SEED)
 
 
 def _net(bn=True):
-    net = build_net("train", 320, 21, 1024, 1, bn, False)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in _state(bn).items()})
-    return net.to(DEV)
+    return H.net(H.drn_vgg(bn, False), STATE_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _frames(B=1):
-    return synth.synth_frames(B, SIZE, seed=5)
+    return H.frames(B, SIZE, SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _float64_outputs():
-    """the float64 restatement's training-mode forward on the CPU, computed once"""
-    params, buffers = T.split_state(_state(True), torch.float64)
-    with torch.no_grad():
-        return T.forward(params, buffers, torch.as_tensor(_frames()).double(), False, True)
+    """the float64 restatement's training-mode forward on the CPU, computed once (and shared with test_gpu_train_deform_ts.py)"""
+    return H.forward_outputs(H.drn_vgg(True, False), STATE_SEED, SEED, SIZE, torch.float64)
 
 
 def _targets():
-    gen = torch.Generator().manual_seed(77)
-    return tuple(torch.randn(1, PRIORS, w, generator=gen) for w in (4, 4, 21))
+    return H.targets(PRIORS, (4, 4, 21), TARGET_SEED)
 
 
 def _step(net, compute, resident_path):
@@ -136,40 +126,18 @@ def _step(net, compute, resident_path):
     return out
 
 
-def _plumbing(net, out, reference_net):
-    assert len(out) == 4 and out[1] is None
-    assert tuple(out[0].shape) == (1, PRIORS, 4) and tuple(out[2].shape) == (1, PRIORS, 4) and tuple(out[3].shape) == (1, PRIORS, 21)
-    assert all(o.dtype == torch.float32 and bool(torch.isfinite(o).all()) for o in (out[0], out[2], out[3]))
-    want = {n for n, p in reference_net.named_parameters() if p.grad is not None}
-    assert want
-    for n, p in net.named_parameters():
-        if n in want:
-            assert p.grad is not None and p.grad.dtype == torch.float32 and bool(torch.isfinite(p.grad).all()), n
-    for k, v in net.state_dict().items():
-        if k.endswith("num_batches_tracked"):
-            assert int(v) == 1, k
-
-
 @functools.lru_cache(maxsize=None)
 def _arm_loc_reference(bn):
-    """arm_loc of the CPU restatement (tests/_train_resident_ref.py) in float64 and float32, computed once -> (float64 arm_loc, the
-    float32 one's relative L2 distance to it)"""
-    a64 = R.arm_loc(_state(bn), _frames(), bn, torch.float64)
-    a32 = R.arm_loc(_state(bn), _frames(), bn, torch.float32)
+    """arm_loc of the CPU restatement (T.arm_loc: the trunk and the ARM loc heads alone) in float64 and float32, computed once ->
+    (float64 arm_loc, the float32 one's relative L2 distance to it)"""
+    a64 = T.arm_loc(_state(bn), _frames(), bn, torch.float64)
+    a32 = T.arm_loc(_state(bn), _frames(), bn, torch.float32)
     return a64, float((a32.double() - a64).norm() / a64.norm())
 
 
 def test_bn_restatement_is_the_existing_one():
-    """(no device work) with bn=True the new restatement is tests/_train_net_ref.py's arm_loc, exactly"""
+    """(no device work) with bn=True the no_grad walk of the trunk and the ARM loc heads alone gives the full forward's arm_loc, exactly"""
     assert torch.equal(_arm_loc_reference(True)[0], _float64_outputs()[0])
-
-
-def _moves_after_a_step(net, before, x):
-    """the engine re-packs by itself: net(x) differs after an SGD step on the gradients of _step"""
-    SGD(net.parameters(), lr=1e-3, momentum=0.9).step()
-    with torch.no_grad():
-        after = [t.clone() for t in net(x) if t is not None]
-    assert all(float((a - b).abs().max()) > 0 for a, b in zip(before, after))
 
 
 @pytest.mark.parametrize("bn,compute", [(True, "bf16"), (True, "fp16"), (False, "bf16"), (False, "fp16")],
@@ -186,7 +154,7 @@ def test_net_resident_against_the_existing_path(bn, compute):
         before = [t.clone() for t in res(x) if t is not None]
     out_plain = _step(plain, compute, False)
     out_res = _step(res, compute, True)
-    _plumbing(res, out_res, plain)
+    H.plumbing(res, out_res, plain, PRIORS, counters=True, exact=False)
     d_plain, d_res = rel(out_plain[0], a64), rel(out_res[0], a64)
     print("bn=%s %s, arm_loc relative L2 to float64: resident=False %.4e, resident=True %.4e (ratio %.3f); float32 restatement %.3e"
           % (bn, compute, d_plain, d_res, d_res / d_plain, d32))
@@ -199,7 +167,7 @@ def test_net_resident_against_the_existing_path(bn, compute):
     assert d32 <= 0.01 * d_plain, (d32, d_plain)
     if compute == "bf16":
         assert d_res <= 2 * d_plain, (d_res, d_plain)
-    _moves_after_a_step(res, before, x)
+    H.moves_after_a_step(res, before, x)
 
 
 def test_resident_switch_refusals_and_default():
@@ -236,11 +204,7 @@ class Run(object):
 
     def __init__(self):
         import _loss_ref as R
-        from tdrn_amd.model.refinedet_vgg import build_net as build_dense
-        net = build_dense("train", 320, 21, True, 1024, True, False)
-        sd = synth.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, 0)
-        net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-        self.net = net.to(DEV)
+        self.net = H.net(H.refinedet(True, False), STATE_SEED)
         self.start = {k: v.clone() for k, v in self.net.state_dict().items()}
         self.params = list(self.net.parameters())
         self.opt = SGD(self.params, lr=1e-3, momentum=0.9, weight_decay=5e-4)
@@ -248,8 +212,7 @@ class Run(object):
             p.grad = torch.zeros_like(p)
             self.opt.state[p]["momentum_buffer"] = torch.zeros_like(p)
         self.x = torch.from_numpy(_frames()).to(DEV)
-        cfg = dict(mb_cfg["VOC_320"], min_dim=SIZE, feature_maps=list(MAPS), name="VOC_%d" % SIZE)
-        self.priors = PriorBox(cfg).forward().to(DEV)
+        self.priors = H.priors(SIZE, MAPS)
         rows = [torch.from_numpy(np.ascontiguousarray(t)).float() for t in R.synth_targets(synth._rng("train_resident", 0), 1, 3, 20, 21)]
         # already on the device in tdrn_match's layout: nothing goes up from the host inside the captured step
         self.targets = PackedTargets(torch.cat(rows).to(DEV), torch.tensor([0, rows[0].size(0)], dtype=torch.int32, device=DEV),

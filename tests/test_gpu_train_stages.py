@@ -21,7 +21,7 @@ import functools
 import pytest
 import torch
 
-import _train_net_ref as T
+import _train_model_ref as T
 import _train_stage_ref as R
 from tdrn_amd.model.dualrefinedet_vggbn import build_net
 from tdrn_amd.utils import synth

@@ -16,7 +16,7 @@ import functools
 import pytest
 import torch
 
-import _train_mobilenet_ref as T
+import _train_model_ref as T
 import _train_stage_dw as W
 import _train_stage_ref as R
 from tdrn_amd.model.dualrefinedet_mobilenet import build_net

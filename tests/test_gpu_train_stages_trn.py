@@ -2,7 +2,7 @@
 use_refine, multihead; fp32) pinned op by op on the device: tests/_train_stage_ref.py's method through tests/_train_stage_k5.py, which
 adds conv5x5 as a kind.  Every stage is judged from its OWN recorded inputs and grad_output against float64 on the CPU, elementwise;
 tests/test_train_stage_k5_ref.py proves the checker on the CPU at this very input (192 px, batch 1, synthetic weights seed 0, frames
-seed 5, ref_loc test_gpu_train_trn.py's constant) and shows that float32 torch ops stay inside its caps there.
+seed 5, ref_loc test_gpu_train_trn.py's constant, from tests/_train_model_harness.py) and shows that float32 torch ops stay inside its caps there.
 
 The SSD4Scale net is recorded with separate loc / conf heads (_train_stage_k5.py says why).  In the bf16 step the conv-type and
 deformable stages are checked; BatchNorm, pools and L2Norm run the same fp32 code as in the fp32 step.
@@ -12,10 +12,10 @@ import functools
 import pytest
 import torch
 
-import _train_net_ref as N
+import _train_model_harness as H
+import _train_model_ref as N
 import _train_stage_k5 as K
 import _train_stage_ref as R
-import test_gpu_train_trn as A
 from tdrn_amd.model import refinedet_vgg, ssd4scale_vgg
 from tdrn_amd.utils import synth
 
@@ -57,7 +57,7 @@ def _recorded(which, compute):
             out = net.forward_train(x, compute)
             out, widths = (out[0], out[2], out[3]), (4, 4, 21)
         else:
-            out = net.forward_train(x, [torch.from_numpy(m).to(DEV) for m in A._ref_loc("vgg", 1, SEED)], compute)
+            out = net.forward_train(x, [torch.from_numpy(m).to(DEV) for m in H.ref_loc("vgg", 1, SEED, SIZE, MAPS, 1)], compute)
             widths = (4, 21)
         N.smooth_loss(out, tuple(torch.randn(1, P, w, generator=gen) for w in widths)).backward()
     torch.cuda.synchronize()

@@ -4,9 +4,10 @@ differentiable ops, so that loss.backward() fills their .grad: train_trn.py's lo
 
 References.  Eval mode: oracle.net_ref.ssd4scale_*_forward(phase='train') under test_gpu_net.py's rule for these models (atol 1e-3;
 behind the deformable heads every prior row but those net_ref.border_rows finds on a sampling discontinuity).  Training mode:
-tests/_train_trn_ref.py, the same walks on torch's functional ops with F.batch_norm(training=True), on the CPU in float64.  ref_loc of
-the temporal nets is a constant of the test: the loc maps of the static net of the same architecture (synthetic weights of seed 1) on
-the same frames, from oracle.net_ref.ssd4scale_*_forward(ret_loc=True).
+ssd4scale_forward of tests/_train_model_ref.py, the same walks on torch's functional ops with F.batch_norm(training=True), on the CPU in
+float64.  ref_loc of the temporal nets is a constant of the test: the loc maps of the static net of the same architecture (synthetic
+weights of seed 1) on the same frames, from oracle.net_ref.ssd4scale_*_forward(ret_loc=True).  Fixtures and checks:
+tests/_train_model_harness.py.
 
 Inputs: 192 px, the smallest frame the 3x3 deformable heads accept (pyramid 24 / 12 / 6 / 3, P = 2295).  The float64 tests run ONE
 image, eval mode and the drop-in steps two.
@@ -25,23 +26,20 @@ as test_gpu_train_mobilenet.py does.
 Train-mode outputs against float64: |d| <= 1e-4 max(1, max|ref|) per output, on every prior row but those on a sampling
 discontinuity behind the deformable heads; eval mode against the oracle keeps test_gpu_net.py's atol 1e-3.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import _augment_ref as A
-import _train_trn_ref as T
+import _train_model_harness as H
+import _train_model_ref as T
 from oracle import net_ref
-from tdrn_amd.data import mb_cfg
-from tdrn_amd.layers import PriorBox, RefineMultiBoxLoss
-from tdrn_amd.model import ssd4scale_mobile, ssd4scale_vgg
+from tdrn_amd.layers import RefineMultiBoxLoss
 from tdrn_amd.utils import synth
 from tdrn_amd.utils.augmentations import PairSSDAugmentation
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = H.DEV
 torch.set_num_threads(min(16, torch.get_num_threads()))
 
 SIZE, MAPS = 192, (24, 12, 6, 3)
@@ -49,62 +47,48 @@ P = 3 * sum(f * f for f in MAPS)
 LR, STEPS = 0.01, 3
 SEED64 = {("vgg", False): 5, ("vgg", True): 5, ("mobile", False): 15, ("mobile", True): 1}   # the float64 tests' one image (header)
 SEED = 5                               # eval mode's and the drop-in steps' two images
+STATE_SEED, STATIC_SEED, TARGET_SEED = 0, 1, 77      # the nets' synthetic weights; those of the static net behind ref_loc; the targets
+CAP = 0.1                              # on 10 x yardstick, inclusive (header)
 CASES = [("vgg", False), ("vgg", True), ("mobile", False), ("mobile", True)]
 CASE = pytest.mark.parametrize("arch,deform", CASES, ids=["%s-%s" % (a, "temporal" if d else "static") for a, d in CASES])
-ORACLE = {"vgg": functools.partial(net_ref.ssd4scale_vgg_forward, bn=True), "mobile": net_ref.ssd4scale_mobile_forward}
 
 
 def _build(arch, deform):
-    if arch == "vgg":
-        return ssd4scale_vgg.build_net("train", 320, 21, 1024, True, deform)
-    return ssd4scale_mobile.build_net("train", 320, 21, 1024, deform)
+    return H.build(H.ssd4scale(arch, deform))
 
 
-@functools.lru_cache(maxsize=None)
-def _state(arch, deform, seed=0):
-    return synth.synth_state_dict({k: tuple(v.shape) for k, v in _build(arch, deform).state_dict().items()}, seed)
+def _state(arch, deform, seed=STATE_SEED):
+    return H.state(H.ssd4scale(arch, deform), seed)
 
 
-def _net(arch, deform, seed=0):
-    """a fresh module with the synthetic weights, in training mode as build_net leaves it"""
-    net = _build(arch, deform)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in _state(arch, deform, seed).items()})
-    return net.to(DEV)
+def _net(arch, deform, seed=STATE_SEED):
+    return H.net(H.ssd4scale(arch, deform), seed)
 
 
-@functools.lru_cache(maxsize=None)
 def _frames(B, seed):
-    return synth.synth_frames(B, SIZE, seed=seed)
+    return H.frames(B, SIZE, seed)
 
 
-@functools.lru_cache(maxsize=None)
 def _ref_loc(arch, B, seed):
-    """the static net's loc maps on the same frames, from the oracle: a constant of the test"""
-    maps = ORACLE[arch](_state(arch, False, 1), _frames(B, seed), 21, "train", ret_loc=True)[2]
-    assert [tuple(m.shape) for m in maps] == [(B, 12, f, f) for f in MAPS]
-    return tuple(np.ascontiguousarray(np.asarray(m, dtype=np.float32)) for m in maps)
+    return H.ref_loc(arch, B, seed, SIZE, MAPS, STATIC_SEED)
 
 
 def _ref_loc_dev(arch, deform, B, seed):
     return [torch.from_numpy(m).to(DEV) for m in _ref_loc(arch, B, seed)] if deform else ()
 
 
-@functools.lru_cache(maxsize=None)
 def _targets():
-    gen = torch.Generator().manual_seed(77)
-    return tuple(torch.randn(1, P, w, generator=gen) for w in (4, 21))
+    return H.targets(P, (4, 21), TARGET_SEED)
 
 
-@functools.lru_cache(maxsize=None)
 def _reference(arch, deform, dtype, ref_loc_grad=False, onednn=True):
     """the restatement's SGD run on the CPU, computed once and never changed: STEPS steps for the temporal VGG net (the short run;
     its first step serves the forward and gradient tests), one step for the others.  onednn=False: torch's other float32
     evaluation of the same ops, one step"""
     steps = STEPS if (arch, deform, ref_loc_grad, onednn) == ("vgg", True, False, True) else 1
     seed = SEED64[arch, deform]
-    with torch.backends.mkldnn.flags(enabled=onednn):
-        return T.sgd_run(_state(arch, deform), _frames(1, seed), _targets(), arch, deform, dtype, steps, LR,
-                         _ref_loc(arch, 1, seed) if deform else None, ref_loc_grad)
+    return H.reference(H.ssd4scale(arch, deform), STATE_SEED, seed, SIZE, MAPS, TARGET_SEED, dtype, steps, LR, onednn,
+                       (arch, 1, seed, SIZE, MAPS, STATIC_SEED) if deform else None, ref_loc_grad)
 
 
 def _yardsticks(arch, deform, ref_loc_grad=False):
@@ -119,21 +103,9 @@ def _ours(net, arch, deform, compute="fp32", ref_loc=None):
     return out, T.smooth_loss(out, _targets())
 
 
-def _buffers(net):
-    return {k: v.detach().clone() for k, v in net.state_dict().items() if "running_" in k or k.endswith("num_batches_tracked")}
-
-
-def _train_atol(ref):
-    """train mode against float64: 1e-4 max(1, max|ref|)"""
-    return 1e-4 * max(1.0, float(torch.as_tensor(ref).abs().max()))
-
-
-def _rows_off(got, ref, allowed, atol=1e-3):
-    """test_gpu_net.py's rule: (rows over atol that are on no discontinuity, max |d| over the rows inside atol)"""
-    d = (got.detach().cpu().double() - torch.as_tensor(ref).double()).abs().reshape(-1, got.shape[-1]).numpy()
-    bad = (d > atol).any(1)
-    assert int(allowed.sum()) <= 30, "suspiciously many pixels on a discontinuity: %d rows" % int(allowed.sum())
-    return int((bad & ~allowed).sum()), float(d[~bad].max())
+def _gradient_check(label, grads, ref, yards, extra=()):
+    """the cancelling biases are those whose conv's grad_output the float64 run recorded: every conv bias in front of a BatchNorm"""
+    H.gradient_check(label, grads, ref, yards, extra, CAP, True, H.AbsGoRule(sorted(ref["abs_go"]), each=False))
 
 
 def _allowed(deform, offsets, B):
@@ -147,16 +119,16 @@ def _allowed(deform, offsets, B):
 def test_eval_mode_matches_the_oracle(arch, deform):
     B = 2
     net = _net(arch, deform).eval()
-    before = _buffers(net)
+    before = H.buffers(net)
     x = _frames(B, SEED)
     ref_loc = _ref_loc(arch, B, SEED) if deform else None
     with torch.no_grad():
         out = net.forward_train(torch.from_numpy(x).to(DEV), _ref_loc_dev(arch, deform, B, SEED), ret_loc=True)
     assert len(out) == 3 and tuple(out[0].shape) == (B, P, 4) and tuple(out[1].shape) == (B, P, 21)
-    want = ORACLE[arch](_state(arch, deform), x, 21, "train", deform_on=deform, ref_loc=ref_loc, ret_loc=True, ret_off=True)
+    want = H.ORACLE[arch](_state(arch, deform), x, 21, "train", deform_on=deform, ref_loc=ref_loc, ret_loc=True, ret_off=True)
     allowed = _allowed(deform, want[3], B)
-    bad_loc, d_loc = _rows_off(out[0], want[0], allowed)
-    bad_conf, d_conf = _rows_off(out[1], want[1], allowed)
+    bad_loc, d_loc = H.rows_off(out[0], want[0], allowed, 1e-3)
+    bad_conf, d_conf = H.rows_off(out[1], want[1], allowed, 1e-3)
     print("eval %s deform=%s: max|d| loc %.3e conf %.3e (atol 1e-3), rows on a discontinuity %d" % (arch, deform, d_loc, d_conf, int(allowed.sum())))
     assert bad_loc == 0 and bad_conf == 0
     if deform:
@@ -165,7 +137,7 @@ def test_eval_mode_matches_the_oracle(arch, deform):
         assert [tuple(m.shape) for m in out[2]] == [(B, 12, f, f) for f in MAPS]
         for m, r in zip(out[2], want[2]):
             assert float((m.cpu() - torch.as_tensor(r)).abs().max()) <= 1e-3
-    after = _buffers(net)
+    after = H.buffers(net)
     assert all(torch.equal(before[k], after[k]) for k in before), "eval mode changed a running buffer"
     # with an autograd graph when asked for one, in eval mode too; the loc maps carry it; self.phase does not matter
     net.phase = "test"
@@ -183,52 +155,13 @@ def test_train_mode_forward_and_running_statistics(arch, deform):
         out, _ = _ours(net, arch, deform)
     ref = _reference(arch, deform, torch.float64)[0][0]
     allowed = _allowed(deform, [ref["taps"]["offset.%d" % s] for s in range(4)] if deform else None, 1)
-    a_loc, a_conf = _train_atol(ref["outs"][0]), _train_atol(ref["outs"][1])
-    bad_loc, d_loc = _rows_off(out[0], ref["outs"][0], allowed, a_loc)
-    bad_conf, d_conf = _rows_off(out[1], ref["outs"][1], allowed, a_conf)
+    a_loc, a_conf = H.train_atol(ref["outs"][0]), H.train_atol(ref["outs"][1])
+    bad_loc, d_loc = H.rows_off(out[0], ref["outs"][0], allowed, a_loc)
+    bad_conf, d_conf = H.rows_off(out[1], ref["outs"][1], allowed, a_conf)
     print("train %s deform=%s: max|d| loc %.3e (bound %.3e) conf %.3e (bound %.3e), rows on a discontinuity %d, rows over the bound %d + %d"
           % (arch, deform, d_loc, a_loc, d_conf, a_conf, int(allowed.sum()), bad_loc, bad_conf))
     assert bad_loc == 0 and bad_conf == 0
-    worst = 0.0
-    for k, v in _buffers(net).items():
-        r = ref["buffers"][k]
-        if k.endswith("num_batches_tracked"):
-            assert int(v) == 1 and int(r) == 1, k
-            continue
-        d, bound = float((v.cpu().double() - r).abs().max()), 1e-4 * max(1.0, float(r.abs().max()))
-        worst = max(worst, d / bound)
-        assert d <= bound, (k, d, bound)
-    print("train %s deform=%s: running statistics, worst |d| / bound %.3e" % (arch, deform, worst))
-
-
-def _gradient_check(label, ours_grads, ref, yards, extra=()):
-    """ours_grads {name: tensor}; ref: one log entry of the float64 run; yards: the log entries of torch's float32 evaluations (a
-    tensor's yardstick is the larger of them); extra: [(name, ours, float64, [float32, ...])]"""
-    rel = lambda g, r: float((g.double() - r).norm() / r.norm())
-    cancelling = set(ref["abs_go"])
-    names = [n for n in ref["grads"] if n not in cancelling]
-    yardstick = {n: max(rel(y["grads"][n], ref["grads"][n]) for y in yards) for n in names}
-    ours = {}
-    for n in names:
-        assert ours_grads[n] is not None and bool(torch.isfinite(ours_grads[n]).all()), n
-        ours[n] = rel(ours_grads[n].cpu(), ref["grads"][n])
-    for n, g, r, ys in extra:
-        yardstick[n], ours[n] = max(rel(y, r) for y in ys), rel(g.cpu(), r)
-    y_name, o_name = max(yardstick, key=yardstick.get), max(ours, key=ours.get)
-    bound = 10 * yardstick[y_name]
-    print("gradients %s: ours worst %.3e (%s), float32 yardstick worst %.3e (%s), bound %.3e"
-          % (label, ours[o_name], o_name, yardstick[y_name], y_name, bound))
-    assert bound <= 0.1, "uninformative: the float32 yardstick itself is at %.3e; pick another frame" % yardstick[y_name]
-    bad = {n: v for n, v in ours.items() if not v <= bound}
-    assert not bad, bad
-    # the cancelling biases: the batch mean removes the bias, what is left is the fp32 noise of a sum of grad_output
-    worst = 0.0
-    for n in cancelling:
-        g, s = ours_grads[n].cpu().double().abs(), ref["abs_go"][n]
-        assert float(ref["grads"][n].abs().max()) <= 1e-12, n
-        worst = max(worst, float((g / (2e-6 * s)).max()))
-        assert bool((g <= 2e-6 * s).all()), (n, float((g / (2e-6 * s)).max()))
-    print("gradients %s: %d cancelling biases, worst |g| / (2e-6 sum|grad_output|) %.3e" % (label, len(cancelling), worst))
+    H.running_statistics_check("%s deform=%s" % (arch, deform), H.buffers(net), ref["buffers"])
 
 
 @CASE
@@ -251,7 +184,7 @@ def test_a_ref_loc_that_requires_grad_gets_its_gradient():
     loss.backward()
     ref, yards = _reference(arch, deform, torch.float64, True)[0][0], _yardsticks(arch, deform, True)
     assert all(t.grad is not None and bool(torch.isfinite(t.grad).all()) and float(t.grad.abs().max()) > 0 for t in ref_loc)
-    extra = [("ref_loc[%d]" % s, ref_loc[s].grad, ref["ref_loc_grads"][s], [y["ref_loc_grads"][s] for y in yards]) for s in range(4)]
+    extra = [("ref_loc[%d]" % s, ref_loc[s].grad, ref["extra_grads"][s], [y["extra_grads"][s] for y in yards]) for s in range(4)]
     _gradient_check("vgg temporal, ref_loc requires grad", {n: p.grad for n, p in net.named_parameters()}, ref, yards, extra)
     # a constant ref_loc gets none, and costs nothing: needs_input_grad gates the launch
     const = _ref_loc_dev(arch, deform, 1, SEED64[arch, deform])
@@ -264,32 +197,14 @@ def test_short_sgd_run_follows_float64():
     comparison can hold): the losses fall, in ours and in float64, and ours stays within 10 x the float32 yardstick's own distance from
     float64 at every step (floor: 1e-5 of the loss, the float32 evaluation of its means)."""
     arch, deform = "vgg", True
-    net = _net(arch, deform)
     want = [l["loss"] for l in _reference(arch, deform, torch.float64)[0]]
     yard = [l["loss"] for l in _reference(arch, deform, torch.float32)[0]]
-    losses = []
-    for _ in range(STEPS):
-        net.zero_grad()
-        _, loss = _ours(net, arch, deform)
-        loss.backward()
-        losses.append(float(loss.detach()))
-        with torch.no_grad():
-            for p in net.parameters():
-                p -= LR * p.grad
-    print("short run: losses ours %r, float64 %r, float32 yardstick %r" % (losses, want, yard))
-    assert len(want) == len(yard) == STEPS
-    assert all(b < a for a, b in zip(want, want[1:])) and all(b < a for a, b in zip(losses, losses[1:]))
-    for k, (a, b, y) in enumerate(zip(losses, want, yard)):
-        bound = max(10 * abs(y - b), 1e-5 * max(1.0, abs(b)))
-        print("short run: step %d |ours - float64| %.3e, yardstick %.3e, bound %.3e" % (k, abs(a - b), abs(y - b), bound))
-        assert abs(a - b) <= bound, (k, a, b, bound)
+    losses = H.short_run(_net(arch, deform), lambda net: _ours(net, arch, deform)[1], STEPS, LR)
+    H.short_run_check(losses, want, yard, STEPS)
 
 
 def _priors():
-    cfg = dict(mb_cfg["VOC_320"], min_dim=SIZE, feature_maps=list(MAPS), name="VOC_%d" % SIZE)
-    priors = PriorBox(cfg).forward().to(DEV)
-    assert priors.shape[0] == P
-    return priors
+    return H.priors(SIZE, MAPS)
 
 
 def _criterion():
@@ -321,28 +236,13 @@ def test_drop_in_trn_step(arch):
     x = torch.from_numpy(_frames(B, SEED)).to(DEV)
     with torch.no_grad():
         ref_loc = static(x, ret_loc=True)[2]
-        before = [t.clone() for t in net(x, ref_loc=ref_loc)]
-    opt = torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9, weight_decay=5e-4)
-    out32, losses = _trn_step(static, net, x, targets, priors, "fp32", opt)
-    assert all(np.isfinite(l) for l in losses), losses
-    for n, p in net.named_parameters():
-        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), n
+    step = lambda n, compute, opt: _trn_step(static, n, x, targets, priors, compute, opt)
+    H.drop_in_fp32(net, lambda n: n(x, ref_loc=ref_loc), step, torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9, weight_decay=5e-4))
     assert all(p.grad is None for p in static.parameters())
-    opt.step()
-    with torch.no_grad():
-        after = [t.clone() for t in net(x, ref_loc=ref_loc)]
-    # the engine re-packed by itself: no repack() call between the step and net(x)
-    assert all(float((a - b).abs().max()) > 0 for a, b in zip(before, after))
-    # the 16-bit compute types: the same pass is finite; their drift against fp32 is reported, not gated
     with torch.no_grad():
         ref = _net(arch, True).forward_train(x, ref_loc)
-    for compute in ("bf16", "fp16"):
-        fresh = _net(arch, True)
-        out, losses = _trn_step(static, fresh, x, targets, priors, compute, torch.optim.SGD(fresh.parameters(), lr=1e-3))
-        assert all(np.isfinite(l) for l in losses), (compute, losses)
-        assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in fresh.parameters()), compute
-        print("drop-in %s %s: losses %r, output drift against fp32: loc %.3e conf %.3e" % (
-            arch, compute, losses, *(float((a.detach() - b).abs().max()) for a, b in zip(out, ref))))
+    H.drop_in_16bit(lambda: _net(arch, True), step, ref, lambda compute, losses, drift: print(
+        "drop-in %s %s: losses %r, output drift against fp32: loc %.3e conf %.3e" % (arch, compute, losses, *drift)))
 
 
 def test_pair_path_step():

@@ -17,10 +17,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import _train_net_ref as N
+import _train_model_harness as H
+import _train_model_ref as N
 import _train_stage_k5 as K
 import _train_stage_ref as R
-import test_gpu_train_trn as A
 import test_train_stage_mobilenet_ref as M
 import test_train_stage_ref as V
 from tdrn_amd import _lib
@@ -107,7 +107,7 @@ def _step(which, mutated=False):
                 out = (out[0], out[2], out[3])
                 widths = (4, 4, 21)
             else:
-                out = net.forward_train(x, [torch.from_numpy(m) for m in A._ref_loc("vgg", 1, SEED)])
+                out = net.forward_train(x, [torch.from_numpy(m) for m in H.ref_loc("vgg", 1, SEED, SIZE, MAPS, 1)])
                 widths = (4, 21)
             targets = tuple(torch.randn(1, P, w, generator=gen) for w in widths)
             N.smooth_loss(out, targets).backward()

@@ -18,7 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import _train_mobilenet_ref as T
+import _train_model_ref as T
 import _train_stage_dw as W
 import _train_stage_ref as R
 import test_train_stage_ref as V
@@ -112,7 +112,7 @@ def test_the_ops_are_restored_and_the_stages_are_the_modules_holders():
     assert [st.name for st in dw] == ["backbone.%d.0" % i for i in range(1, 14)] + ["extras.0.3.0", "extras.1.3.0"]
     assert [st.args["stride"][0] for st in dw] == T.STRIDES + [2, 2]
     assert all(set(st.grad_input) == {"input"} and "bias" not in st.inputs for st in dw)
-    assert set(T.bn_after_conv_names(_state().keys())) == set(T.CANCELLING)
+    assert set(T.bn_after_conv(_state().keys())) == set(T.CANCELLING)
 
 
 def test_correct_fp32_ops_pass_every_stage():

@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 import _deform_grad_ref as D
-import _train_net_ref as T
+import _train_model_ref as T
 import _train_stage_ref as R
 from tdrn_amd import _lib
 from tdrn_amd.model import networks
