@@ -118,6 +118,12 @@ TDRN_API int tdrn_deform_conv_backward_parameters(const float *input, const floa
  *   grad_input like input, grad_weight like weight, grad_bias (Cout) or NULL: all fp32, contiguous, device.
  *   `compute` selects the MFMA input type as in (i): TDRN_F32 is exact fp32; TDRN_BF16 / TDRN_F16 round input, weight and
  *   grad_output ONCE, to nearest even, to the type (bias is not rounded).  Accumulation and every output are fp32.
+ *   At the ends of the range that rounding keeps the type's subnormals (nothing is flushed, neither by the packers nor as an MFMA
+ *   operand), turns a value past the largest finite one into +-inf (65520 is the first in fp16; nothing saturates) and leaves NaN a
+ *   NaN; in TDRN_F32 compute fp32 subnormals are kept as operands, in the accumulation and in every output.  A non-finite operand
+ *   meets the zeros of the other operand as IEEE says (inf * 0 = NaN), and the padding is explicit zeros: a non-finite weight at a
+ *   tap that reaches into the padding gives NaN there, as a non-finite value gives NaN under a zero weight
+ *   (tests/test_gpu_number_range.py measures all of this, bit for bit).
  *   forward:             output is OVERWRITTEN.
  *   backward_input:      grad_input is OVERWRITTEN (a stride-1 conv over grad_output with the kernel rotated and transposed).
  *   backward_parameters: grad_weight += scale * sum_p grad_output[p] input[p (+) tap], grad_bias += scale * sum_p grad_output[p],
@@ -429,7 +435,10 @@ TDRN_API int tdrn_sgd_step(const tdrn_sgd_tensor *tensors_host, int n_tensors, c
  *   contiguous in channels_last), C % 64 == 0, on a 16-byte boundary, fewer than 2^31 elements.  Activations and their gradients
  *   are resident tensors of the same type; parameters, their gradients, the BatchNorm buffers and all statistics stay fp32 as in
  *   (i-c) .. (i-e).  All accumulation is fp32; a conv output and a BatchNorm output are each rounded ONCE to the type, to nearest
- *   even.  Argument lists mirror the fp32 NCHW entries they stand beside.  Nothing allocates, nothing synchronises, everything is
+ *   even: a result in the type's subnormal range is kept at the subnormal spacing (never flushed), one past the largest finite value
+ *   becomes +-inf (65504 + 16 in fp16; nothing saturates), and subnormal activations are read as what they are
+ *   (tests/test_gpu_number_range_resident.py, on every route of the conv); at the layout boundary NaN stays NaN as well (NaN and
+ *   +-inf through the conv and BatchNorm epilogues are not measured).  Argument lists mirror the fp32 NCHW entries they stand beside.  Nothing allocates, nothing synchronises, everything is
  *   enqueued on `stream`; no float atomics, every output is bitwise reproducible.
  *   Errors, all decided before any launch, in this order per entry: a null pointer, an activation pointer off a 16-byte boundary, an
  *   fp32 pointer off a 4-byte one, a dtype other than TDRN_BF16 / TDRN_F16 (TDRN_F32 included), unknown flag bits -> TDRN_E_ARG; the

@@ -103,8 +103,9 @@ void conv_train_args(ConvArgs &a, int dtype)
     a.relu = 0; a.out_f32 = 1;
     a.dtype = dtype;
     // every shape on conv_igemm.hip: head3x3.hip would take the narrow 16-bit layers with another fp32 K order, and a layer's
-    // gradient should not change its rounding with its channel count
-    a.kdisable = KOFF_HEAD3X3;
+    // gradient should not change its rounding with its channel count; and every tap formed (tdrn_hip.h i-c: the padding's zeros meet
+    // a non-finite weight wherever the tiles fall)
+    a.kdisable = KOFF_HEAD3X3 | KOFF_TAP_SKIP;
     // the small-M layers (the 10 x 10 and 5 x 5 maps, the extras layer between them) fill the chip by K slices, as in the engine
     a.splitk = conv_splitk_choice(a);
 }
@@ -250,7 +251,7 @@ int conv_nhwc_plan(int N, int Cin, int H, int W, int Cout, int kH, int kW, int d
         // the K slices are those of the default route (a direct-conv layer has none), whatever the flag says: a split would add one
         // more difference in fp32 order to those the two routes already have (tdrn_hip.h section i-k: bit-equal only for one
         // 64-channel chunk and no bias), and the workspace size stays the same
-        a->kdisable = KOFF_HEAD3X3;
+        a->kdisable = KOFF_HEAD3X3 | KOFF_TAP_SKIP;
         a->splitk = 1;
         a->splitk = conv_splitk_choice(*a);
         if (flags & TDRN_CONV_NHWC_IGEMM_ONLY) a->kdisable |= KOFF_CONV_PATCH | KOFF_CONV_PP | KOFF_PW1X1;

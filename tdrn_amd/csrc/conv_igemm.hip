@@ -38,6 +38,7 @@ struct ConvParams {
     float *partial;   // [splits][phases][M][Npad] fp32
     int ablate;   // diagnostics only (TDRN_CONV_ABLATE): 1 = skip the K-loop loads, 2 = skip the MFMAs
     int batch_minor, B;   // batch_minor: GEMM row m = (ho*Wo + wo)*B + b instead of (b*Ho + ho)*Wo + wo (see conv_igemm_kernel)
+    int all_taps;         // KOFF_TAP_SKIP: no tap is skipped, the padding's zeros meet every weight
 };
 
 // COH = agent-coherent access (the `sc1` cache-policy bit: served by / written through to the memory side, past the XCD's own
@@ -120,7 +121,9 @@ __device__ __forceinline__ void igemm_tile(const ConvParams &p, const int wg, co
     // GEMM row -> (image, pixel).  Small maps with padding use the batch-minor order: the 128 / 256 rows of a tile are
     // then the same few pixel positions of many images, so a tap that falls into the padding does so for the WHOLE tile
     // and its K-steps are skipped (loads and MFMAs): fc6 (3x3, dilation 6 on a 10x10 map) has 64 % of its (pixel, tap)
-    // pairs in the padding.  A skipped step would have added exact zeros, so results are bit-identical either way.
+    // pairs in the padding.  A skipped step would have added exact zeros, so for FINITE weights results are bit-identical either
+    // way; a non-finite weight at a skipped tap misses its inf * 0 = NaN, so the training entries, whose contract (tdrn_hip.h i-c)
+    // forms that product, turn the skip off (p.all_taps).
     auto decode = [&](int m, int &b, int &rem) {
         if (p.batch_minor) { rem = m / p.B; b = m - rem * p.B; }
         else { b = m / HoWo; rem = m - b * HoWo; }
@@ -175,7 +178,7 @@ __device__ __forceinline__ void igemm_tile(const ConvParams &p, const int wg, co
     };
     // taps that touch the image for at least one row of this tile (bit = tr*kw + tq); all ones without padding
     unsigned tapmask = 0xFFFFFFFFu;
-    if (p.pad > 0 && p.kh * p.kw <= 32) {
+    if (p.pad > 0 && p.kh * p.kw <= 32 && !p.all_taps) {
         unsigned mine = 0u;
         for (int a = 0; a < p.kh; ++a)
             for (int c = 0; c < p.kw; ++c) {
@@ -557,6 +560,7 @@ static int make_params(const ConvArgs &a, ConvParams &p)
     p.batch_minor = (a.pad > 0 && a.phases == 1 && a.B > 1 && a.Ho * a.Wo <= 1600 && a.kh * a.kw <= 32) ? 1 : 0;
     p.splits = (a.splitk > 1 && a.partial) ? a.splitk : 1;
     p.partial = (float *)a.partial;
+    p.all_taps = (a.kdisable & KOFF_TAP_SKIP) ? 1 : 0;
     static int ablate = -1;
     if (ablate < 0) ablate = dev_ablate_env("TDRN_CONV_ABLATE");     // (developer builds only: common.h)
     p.ablate = ablate;

@@ -31,6 +31,9 @@ enum KernelOff {
     KOFF_HEAD3X3 = 256,        // TDRN_PLAN_NO_HEAD3X3: the narrow fp32 3x3 heads stay on conv_igemm.hip (not head3x3.hip)
     KOFF_TS_RANGES = 512,      // TDRN_PLAN_TS_ONE_RANGE: transform-then-sample heads take the whole batch as one range
     KOFF_PATCH_TAIL = 1024,    // TDRN_PLAN_NO_PATCH_TAIL: conv3x3_patch.hip and pw1x1_kernel run whole items only (no tail split)
+    KOFF_TAP_SKIP = 2048,      // (no plan flag: the training entries of api.hip) conv_igemm.hip forms every tap's products, those of a tap that
+                               // lies in the padding for a whole pixel tile included: the same bits for finite weights, and a non-finite weight
+                               // meets the padding's zeros (inf * 0 = NaN) at every tap, whatever the tiling
 };
 
 // Launch glue of the grid-stride kernels: workgroups of 256 threads for `total` elements, at most `cap` of them
