@@ -171,6 +171,14 @@ TDRN_API int tdrn_conv2d_backward_parameters(const float *input, const float *gr
  *   A channel's reduction is cut into splits that depend on (N, C, H*W) alone and merged in split order: no float atomics, every
  *   output of both entries is bitwise reproducible, and the same for a buffer on any 4-byte boundary.
  *   The query returns 12 C splits + 8 C bytes and serves both entries.
+ *   Range of the batch statistics, per channel (tests/test_gpu_number_range_stats.py; the bounds are derived in
+ *   tests/_number_range_stats.py): save_mean is right to a few u max|x| and M2 -- so save_invstd and running_var -- to a relative
+ *   c u (1 + |mean| / sigma), u = 2^-24, at any scale of the data and whatever the mean (a merge with an empty record returns the
+ *   other record, so a mean past 2^64 is no special case), while M (max x - min x)^2 < 2^128: then no d * d * n of a merge and no
+ *   squared deviation overflows.  Squared deviations below 2^-126 are kept at the subnormal spacing and vanish below 2^-150 (M2 = 0
+ *   for sigma < 2^-75: save_invstd = 1 / sqrt(eps)).  Past the range M2 is +inf, never NaN, for |x| < 2^123: variance inf ->
+ *   save_invstd = 0 -> output = bias (clipped by the ReLU), grad_input = 0 and grad_weight += 0 for that channel, running_var = +inf;
+ *   save_mean stays right.  Other channels are not touched.
  *   Errors, all decided before any launch: a null required pointer, a pointer off a 4-byte boundary, grad_weight without grad_bias,
  *   training = 0 without running buffers -> TDRN_E_ARG; N / C / H / W <= 0 -> query 0 and TDRN_E_SHAPE; training = 1 with M = 1 ->
  *   TDRN_E_SHAPE (M = 2 is legal); N*C*H*W >= 2^31 -> query 0 and TDRN_E_UNSUPPORTED; eps <= 0 or momentum outside [0, 1] -> TDRN_E_ARG;
@@ -207,6 +215,14 @@ TDRN_API int tdrn_batch_norm_backward(const float *input, const float *grad_outp
  *            weight input / eps there; torch's autograd returns NaN).  grad_weight (NULL: not computed) += scale sum_pixels go input / norm,
  *            summed per 64-pixel tile and over the tiles in tile order.  One of the two is required.  The workspace is needed for
  *            grad_weight only; the query returns 4 C ceil(N H W / 64) bytes, a pure function of (N, C, H W).
+ *   Range (tests/test_gpu_number_range_stats.py): the sum of squares is an fp32 sum, so norm is right to (C / 2 + 3) u while
+ *            sum_c input^2 < 2^128; a square below 2^-126 is kept at the subnormal spacing and vanishes below 2^-150, which moves norm
+ *            by at most sqrt(C 2^-149).  A pixel whose squares all vanish (|input| < 2^-75, subnormals included) has norm = eps and
+ *            r = 0 exactly and is treated as the all-zero pixel: output = weight input / eps, grad_input = weight go / eps.  Where
+ *            norm is within a few ulp of eps, r = norm - eps carries ulp(norm) / 2 of absolute error and the second term of
+ *            grad_input that much relative error over r.  Past 2^128 norm = +inf and output = +-0, as the fp32 formula gives; the
+ *            backward gives grad_input = +-0 at that pixel and adds 0 to grad_weight (1 / inf = 0; no NaN while sum_c weight go input
+ *            is finite).  Other pixels are not touched, whatever their neighbours' scale.
  *   No float atomics: every output of the four entries is bitwise reproducible, and the same for a buffer on any 4-byte boundary.
  *   Errors, all decided before any launch, in this order: a null required pointer, a float pointer off a 4-byte boundary, eps <= 0
  *   or NaN -> TDRN_E_ARG; N / C / H / W <= 0 or an empty output -> TDRN_E_SHAPE (queries: 0); 2^31 or more elements or a pool
@@ -322,6 +338,10 @@ TDRN_API int tdrn_conv2d_strided_backward_parameters(const float *input, const f
  *                        of ceil(K / S') elements, S' = max(1, min(ceil(2048 / C), ceil(K / 1024))), S = the ranges that are not
  *                        empty; the ranges are summed in range order.
  *   `compute` must be TDRN_F32: the op is bandwidth-bound and has no 16-bit mode.
+ *   forward and backward_input are that sentence bit for bit (tests/test_gpu_number_range_pointwise.py): each fmaf rounds once;
+ *   subnormal inputs, products and sums are kept, never flushed; a sum past the largest finite value is +-inf.  A skipped tap is not
+ *   read as 0 times its weight: a non-finite weight leaves the pixels finite for which its tap lies in the padding.  Elsewhere
+ *   inf and NaN follow IEEE through the nine fmaf.  backward_parameters sums in fp32 and keeps subnormal sums as well.
  *   All outputs are bitwise reproducible run to run, and the same for caller buffers on any 4-byte boundary: nothing on this path
  *   uses float atomics, and S depends on the geometry alone.
  *   Geometry (the argument order is the query's in all four functions): kH = kW = 3, dH = dW in {1, 2}, padH = padW = 1, dilation 1;
@@ -403,6 +423,9 @@ TDRN_API int tdrn_conv5x5_backward_parameters(const float *input, const float *g
  *   replay.  torch.optim.SGD starts with buf = clone(d) instead; b = mom*0 + d equals that except for the sign of a zero: where
  *   d = -0 the buffer holds +0.  momentum_buf is neither read nor written when mom == 0, but must be a valid pointer all the same
  *   (the host cannot read hyper_dev).  Dampening and maximize are not covered.
+ *   The five lines hold over the whole of fp32 (tests/test_gpu_number_range_pointwise.py): subnormal p, g, b, lr and products are
+ *   read and kept as what they are (lr*u below 2^-150 is +-0, nothing is flushed earlier), the sign of a zero follows IEEE, lr*u past
+ *   the largest finite value is +-inf, and inf / NaN in g reach p and b of that element by IEEE's rules and no other element.
  *   A record with numel = 0 or a null grad is skipped (torch skips grad is None the same way); nothing else of it is looked at but
  *   numel and group.  The other records go out in launches of up to TDRN_SGD_TENSORS_PER_LAUNCH tensors each, in chunks of
  *   TDRN_SGD_CHUNK elements, with 16-byte vector accesses where param, grad and momentum_buf are all 16-byte aligned and scalar
@@ -472,6 +495,9 @@ TDRN_API int tdrn_sgd_step(const tdrn_sgd_tensor *tensors_host, int n_tensors, c
  *   per_split pixel rows: S = clamp(floor(2048 / (C / 64)), 1, ceil(M / 256)), M = N H W, per_split = ceil(M / S) rounded up to 32,
  *   splits = ceil(M / per_split) (tdrn_batch_norm_nhwc_splits: a pure function of the shape; returns a status).  Statistics are
  *   (count, mean, M2) records merged by Chan's formula in a fixed order, the splits in float64.  Workspace: 12 C splits + 8 C bytes.
+ *   The records and their merge are (i-d)'s (bn_prims.h), and so is the range of the statistics: right at any scale and any mean
+ *   while M (max x - min x)^2 < 2^128, M2 = +inf -> save_invstd = 0 -> output = bias past it.  Every finite fp16 input is inside the
+ *   range (65504^2 M < 2^128); bf16 inputs past 2^63 can leave it.
  *
  *   tdrn_max_pool_nhwc_*: (i-e)'s three geometries, selection rule and one-byte codes, the codes laid out like the output
  *   ([N][Ho][Wo][C], on any byte; NULL in the forward: none are written).  backward reads grad_output and codes only and writes
