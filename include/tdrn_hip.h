@@ -584,6 +584,43 @@ TDRN_API int tdrn_deform_conv_ts_backward(const float *input, const float *weigh
                                           size_t workspace_bytes, void *stream);
 
 /* ========================================================================================
+ * (i-m) Dynamic loss scaling for fp16 training -- what torch.cuda.amp.GradScaler gives a CUDA user, with every decision taken on
+ *     the device: the loss is multiplied by a scale so that fp16 activation gradients stay above the type's smallest subnormal,
+ *     the SGD step of (i-j) divides the scale out again, and a step whose gradients hold inf or NaN is skipped and halves the scale.
+ *   state_dev: four DEVICE fp32 words on a 16-byte boundary, {scale, good_steps, found_inf, skipped}.  The two counts are held as
+ *   floats and are exact below 2^24; found_inf is 0 or 1.  The kernels read and write them when they run: a captured step replayed
+ *   after the scale moved uses the new scale.  tensors_host, hyper_dev, n_groups and flags are (i-j)'s.
+ *   tdrn_amp_check_finite: reads every gradient element of the records that (i-j) would not skip (16-byte vector loads where grad is
+ *   16-byte aligned, scalar ones elsewhere and in the numel % 4 tail) and, if one is +-inf or NaN, stores found_inf = 1.  It never
+ *   stores 0: the flag stays up over any number of checks until tdrn_amp_update, so two optimizers may share one state.  The
+ *   largest finite value and subnormals are finite.  param and momentum_buf are not looked at and may be null.
+ *   tdrn_sgd_step_scaled: (i-j)'s step with, read from state_dev when it runs,
+ *       inv = 1 / scale                       one fp32 division
+ *       g'  = g * inv                         one fp32 rounding; g' takes g's place in the four lines of (i-j)
+ *       if (found_inf != 0) no element of param or momentum_buf of any tensor of any launch of the call is written
+ *       if (flags & TDRN_SGD_ZERO_GRADS) g = +0, skipped or not
+ *   It writes nothing to state_dev.  With scale = 1 and found_inf = 0 its results are tdrn_sgd_step's bit for bit.  The check is
+ *   a call of its own because a list may go out in several launches: a non-finite gradient in the last launch must stop the first.
+ *   tdrn_amp_update: torch's _amp_update_scale_, in fp32, by one lane:
+ *       if (found_inf != 0) { scale = scale * backoff_factor;  good_steps = 0;  skipped += 1; }
+ *       else { good_steps += 1;
+ *              if (good_steps == growth_interval) { s = scale * growth_factor;  if (isfinite(s)) scale = s;  good_steps = 0; } }
+ *       found_inf = 0
+ *   (torch multiplies by the factor as a double; with factors that fp32 holds exactly the two agree bit for bit.)
+ *   All results are bitwise reproducible run to run: no atomics; every writer of found_inf stores the same word.
+ *   Errors, all decided before any launch, in (i-j)'s order: a null tensors_host or hyper_dev, n_tensors < 0, n_groups < 1, a null
+ *   state_dev or one off a 16-byte boundary, unknown flag bits, growth_factor <= 1, backoff_factor outside the open interval (0, 1),
+ *   growth_interval < 1 or >= 1 << 24, and the record errors of (i-j) -> TDRN_E_ARG (tdrn_amp_check_finite has no rows to hold a
+ *   group against: it rejects a negative group, and requires neither param nor momentum_buf); a numel of 2^31 or more ->
+ *   TDRN_E_UNSUPPORTED.  No workspace, no allocation and no host synchronisation: everything is enqueued on `stream`, and all three
+ *   entries are legal under stream capture.
+ * ====================================================================================== */
+TDRN_API int tdrn_amp_check_finite(const tdrn_sgd_tensor *tensors_host, int n_tensors, float *state_dev, void *stream);
+TDRN_API int tdrn_sgd_step_scaled(const tdrn_sgd_tensor *tensors_host, int n_tensors, const float *hyper_dev, int n_groups,
+                                  const float *state_dev, int flags, void *stream);
+TDRN_API int tdrn_amp_update(float *state_dev, float growth_factor, float backoff_factor, int growth_interval, void *stream);
+
+/* ========================================================================================
  * (ii) NMS / box utilities / Detect
  * ====================================================================================== */
 

@@ -168,6 +168,10 @@ _SIGS = {
     "tdrn_multibox_loss_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "tdrn_multibox_loss_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 3),
     "tdrn_sgd_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    # section (i-m): dynamic loss scaling
+    "tdrn_amp_check_finite": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "tdrn_sgd_step_scaled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "tdrn_amp_update": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "tdrn_augment_sample": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_uint64] + [C.c_void_p] * 7),
     "tdrn_augment_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tdrn_augment_pair_sample": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_double, C.c_uint64] + [C.c_void_p] * 8),

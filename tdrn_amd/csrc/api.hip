@@ -1298,6 +1298,22 @@ int tdrn_sgd_step(const tdrn_sgd_tensor *tensors_host, int n_tensors, const floa
     return launch_sgd_step(tensors_host, n_tensors, hyper_dev, n_groups, flags, (hipStream_t)stream);
 }
 
+int tdrn_amp_check_finite(const tdrn_sgd_tensor *tensors_host, int n_tensors, float *state_dev, void *stream)
+{
+    return launch_amp_check_finite(tensors_host, n_tensors, state_dev, (hipStream_t)stream);
+}
+
+int tdrn_sgd_step_scaled(const tdrn_sgd_tensor *tensors_host, int n_tensors, const float *hyper_dev, int n_groups,
+                         const float *state_dev, int flags, void *stream)
+{
+    return launch_sgd_step_scaled(tensors_host, n_tensors, hyper_dev, n_groups, state_dev, flags, (hipStream_t)stream);
+}
+
+int tdrn_amp_update(float *state_dev, float growth_factor, float backoff_factor, int growth_interval, void *stream)
+{
+    return launch_amp_update(state_dev, growth_factor, backoff_factor, growth_interval, (hipStream_t)stream);
+}
+
 int tdrn_augment_sample(const int32_t *hw, const double *truths, const int32_t *truth_off, int T_total, int max_truths, int B,
                         uint64_t seed, const int64_t *sample_ids, const double *tape, const int32_t *tape_off,
                         tdrn_augment_params *params, float *out_truths, int32_t *out_off, void *stream)

@@ -467,6 +467,11 @@ int launch_multibox_loss_backward(const float *loc, const float *conf, const flo
 // SGD, one fused multi-tensor step (sgd.hip; semantics: tdrn_hip.h section i-j)
 // ---------------------------------------------------------------------------------------------
 int launch_sgd_step(const tdrn_sgd_tensor *tensors, int n_tensors, const float *hyper_dev, int n_groups, int flags, hipStream_t s);
+// dynamic loss scaling on top of it (sgd.hip; semantics: tdrn_hip.h section i-m)
+int launch_amp_check_finite(const tdrn_sgd_tensor *tensors, int n_tensors, float *state_dev, hipStream_t s);
+int launch_sgd_step_scaled(const tdrn_sgd_tensor *tensors, int n_tensors, const float *hyper_dev, int n_groups, const float *state_dev,
+                           int flags, hipStream_t s);
+int launch_amp_update(float *state_dev, float growth_factor, float backoff_factor, int growth_interval, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // SSDAugmentation on the device (augment.hip; semantics: tdrn_hip.h section ii-c)

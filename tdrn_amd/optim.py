@@ -15,6 +15,9 @@ The hyper-parameters live in one small device tensor, (groups, 4) rows of {lr, m
 reads when it runs.  sync_hyper() brings that tensor up to date with param_groups; an eager step() calls it, so the reference's
 adjust_learning_rate (it writes param_group['lr']) works unchanged.  A captured step cannot: call sync_hyper() before the capture
 and before every replay whose hyper-parameters changed.  The replay then uses the new values.
+
+fp16 training: tdrn_amd.amp.GradScaler.step(optimizer) calls step(grad_scaler=scaler), which checks the gradients for inf / NaN and
+runs the same step with the unscale and the skip decided on the device (tdrn_hip.h section i-m).
 """
 import array
 import ctypes as C
@@ -131,7 +134,10 @@ class SGD(torch.optim.Optimizer):
                              "of that shape on its device" % (tuple(p.shape),))
         return b
 
-    def step(self, closure=None):
+    def step(self, closure=None, *, grad_scaler=None):
+        """grad_scaler: a tdrn_amd.amp.GradScaler (scaler.step(optimizer) passes itself).  The gradients are then those of the scaled
+        loss: they are checked for inf / NaN, all of them before the first launch of the step, and the step divides the scale out
+        and writes nothing if the check found one (tdrn_hip.h section i-m).  Without it the step is the plain one."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -171,10 +177,16 @@ class SGD(torch.optim.Optimizer):
         # tdrn_sgd_tensor as five 8-byte words (little-endian: group is the low half of the last)
         recs = array.array("q", flat)
         assert recs.itemsize == 8 and C.sizeof(_lib.SgdTensor) == 40
+        at, n, flags = recs.buffer_info()[0], len(flat) // 5, _lib.SGD_ZERO_GRADS if self.zero_grads else 0
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tdrn_sgd_step(recs.buffer_info()[0], len(flat) // 5, hyper.data_ptr(), len(self.param_groups),
-                                                _lib.SGD_ZERO_GRADS if self.zero_grads else 0, _lib.current_stream(dev)),
-                       "tdrn_sgd_step")
+            if grad_scaler is None:
+                _lib.check(_lib.lib().tdrn_sgd_step(at, n, hyper.data_ptr(), len(self.param_groups), flags, _lib.current_stream(dev)),
+                           "tdrn_sgd_step")
+            else:
+                state, stream = grad_scaler.state_for_step(dev).data_ptr(), _lib.current_stream(dev)
+                _lib.check(_lib.lib().tdrn_amp_check_finite(at, n, state, stream), "tdrn_amp_check_finite")
+                _lib.check(_lib.lib().tdrn_sgd_step_scaled(at, n, hyper.data_ptr(), len(self.param_groups), state, flags, stream),
+                           "tdrn_sgd_step_scaled")
         return loss
 
     def load_state_dict(self, state_dict):
